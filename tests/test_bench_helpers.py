@@ -61,3 +61,16 @@ def test_host_cores_states_the_cpu_share():
     assert h["nproc"] == os.cpu_count() and h["nproc"] >= 1
     assert h["affinity_cpus"] is None or 1 <= h["affinity_cpus"] <= h["nproc"]
     assert h["sockets"] is None or h["sockets"] >= 1
+
+
+def test_dump_columns_is_a_fixed_sample():
+    """--dump-outputs: every column of a small rank, beyond DUMP_COLUMNS a sample that is the same in every
+    run (fixed seed), ascending, without repeats, and within the 64 MB the dump may take in fp64."""
+    import numpy as np
+    assert bench.dump_columns(100, np).tolist() == list(range(100))
+    assert bench.dump_columns(bench.DUMP_COLUMNS, np).tolist() == list(range(bench.DUMP_COLUMNS))
+    a, b = bench.dump_columns(163840, np), bench.dump_columns(163840, np)
+    assert a.tolist() == b.tolist() and len(a) == bench.DUMP_COLUMNS
+    assert (np.diff(a) > 0).all() and a[0] >= 0 and a[-1] < 163840
+    assert a[-1] > 163840 // 2          # drawn from the whole range, not its head
+    assert bench.DUMP_COLUMNS * (bench.BYTES_PER_COL[8] - bench.IN_BYTES_PER_COL[8]) <= 64e6

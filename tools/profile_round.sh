@@ -27,7 +27,7 @@ d.update(json.load(open(src)))
 json.dump(d, open(dst, "w"), indent=1, sort_keys=True)
 PY
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $out/stats_${variant}_${prec} -o bench --output-format csv \
-  -- python3 $R/bench.py --steps 100 --warmup 5 --no-transfer --no-cpu-baseline --variant $variant --precision $prec \
+  -- python3 $R/bench.py --full --steps 100 --warmup 5 --no-transfer --no-cpu-baseline --variant $variant --precision $prec \
   --nproma $nproma > $out/bench_under_rocprof_${variant}_${prec}.log 2>&1 || exit $?
 # the --stats summary averages every launch of the kernel (placement probes, first step, prewarm, energy
 # window); the timed launches alone, selected with the counts the bench line reports:
