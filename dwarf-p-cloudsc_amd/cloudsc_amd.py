@@ -83,23 +83,26 @@ class Params(C.Structure):
 # ---------------------------------------------------------------------------
 # field inventory
 # ---------------------------------------------------------------------------
+# One (member, kind, direction) row per cloudsc_fields_t member, in member order: csrc/cloudsc_fields.def in
+# Python (tests/test_field_inventory.py holds the two together).
 # kind: "2d" [lev][klon], "2dh" [lev+1][klon], "3d" [nclv][lev][klon], "1d" [klon]
-INPUT_FIELDS = {
-    "pt": "2d", "pq": "2d", "tendency_tmp_t": "2d", "tendency_tmp_q": "2d", "tendency_tmp_a": "2d",
-    "tendency_tmp_cld": "3d", "pvfl": "2d", "pvfi": "2d", "phrsw": "2d", "phrlw": "2d",
-    "pvervel": "2d", "pap": "2d", "paph": "2dh", "plsm": "1d", "ktype": "1d", "plu": "2d",
-    "psnde": "2d", "pmfu": "2d", "pmfd": "2d", "pa": "2d", "pclv": "3d", "psupsat": "2d",
-}
-AEROSOL_FIELDS = {"plcrit_aer": "2d", "picrit_aer": "2d", "pre_ice": "2d", "pccn": "2d", "pnice": "2d"}
-INOUT_FIELDS = {"plude": "2d"}
-OUTPUT_FIELDS = {
-    "tendency_loc_t": "2d", "tendency_loc_q": "2d", "tendency_loc_a": "2d", "tendency_loc_cld": "3d",
-    "pcovptot": "2d", "prainfrac_toprfz": "1d",
-    "pfsqlf": "2dh", "pfsqif": "2dh", "pfcqnng": "2dh", "pfcqlng": "2dh", "pfsqrf": "2dh",
-    "pfsqsf": "2dh", "pfcqrng": "2dh", "pfcqsng": "2dh", "pfsqltur": "2dh", "pfsqitur": "2dh",
-    "pfplsl": "2dh", "pfplsn": "2dh", "pfhpsl": "2dh", "pfhpsn": "2dh",
-}
-ALL_FIELDS = {**INPUT_FIELDS, **AEROSOL_FIELDS, **INOUT_FIELDS, **OUTPUT_FIELDS}
+FIELD_INVENTORY = [
+    ("pt", "2d", "in"), ("pq", "2d", "in"), ("tendency_tmp_t", "2d", "in"), ("tendency_tmp_q", "2d", "in"),
+    ("tendency_tmp_a", "2d", "in"), ("tendency_tmp_cld", "3d", "in"), ("pvfl", "2d", "in"), ("pvfi", "2d", "in"),
+    ("phrsw", "2d", "in"), ("phrlw", "2d", "in"), ("pvervel", "2d", "in"), ("pap", "2d", "in"), ("paph", "2dh", "in"),
+    ("plsm", "1d", "in"), ("ktype", "1d", "in"), ("plu", "2d", "in"), ("psnde", "2d", "in"), ("pmfu", "2d", "in"),
+    ("pmfd", "2d", "in"), ("pa", "2d", "in"), ("pclv", "3d", "in"), ("psupsat", "2d", "in"),
+    ("plcrit_aer", "2d", "aerosol"), ("picrit_aer", "2d", "aerosol"), ("pre_ice", "2d", "aerosol"),
+    ("pccn", "2d", "aerosol"), ("pnice", "2d", "aerosol"), ("plude", "2d", "inout"), ("tendency_loc_t", "2d", "out"),
+    ("tendency_loc_q", "2d", "out"), ("tendency_loc_a", "2d", "out"), ("tendency_loc_cld", "3d", "out"),
+    ("pcovptot", "2d", "out"), ("prainfrac_toprfz", "1d", "out"), ("pfsqlf", "2dh", "out"), ("pfsqif", "2dh", "out"),
+    ("pfcqnng", "2dh", "out"), ("pfcqlng", "2dh", "out"), ("pfsqrf", "2dh", "out"), ("pfsqsf", "2dh", "out"),
+    ("pfcqrng", "2dh", "out"), ("pfcqsng", "2dh", "out"), ("pfsqltur", "2dh", "out"), ("pfsqitur", "2dh", "out"),
+    ("pfplsl", "2dh", "out"), ("pfplsn", "2dh", "out"), ("pfhpsl", "2dh", "out"), ("pfhpsn", "2dh", "out"),
+]
+INPUT_FIELDS, AEROSOL_FIELDS, INOUT_FIELDS, OUTPUT_FIELDS = (
+    {n: k for n, k, d in FIELD_INVENTORY if d == direction} for direction in ("in", "aerosol", "inout", "out"))
+ALL_FIELDS = {n: k for n, k, _ in FIELD_INVENTORY}
 
 # The 21 validated fields in the dwarf's print order (cloudsc_validate.c:193-216).
 VALIDATED = [
@@ -114,16 +117,10 @@ VALIDATED = [
 # Fortran NDIM printed by ERROR_PRINT (VALIDATE_R1/R2/R3)
 VALIDATED_NDIM = {n: (1 if ALL_FIELDS[k] == "1d" else 3 if ALL_FIELDS[k] == "3d" else 2) for n, k in VALIDATED}
 
+
 class Fields(C.Structure):
     """cloudsc_fields_t (pointer order == include/cloudsc_amd.h)."""
-    _fields_ = [(n, C.c_void_p) for n in (
-        "pt pq tendency_tmp_t tendency_tmp_q tendency_tmp_a tendency_tmp_cld "
-        "pvfl pvfi phrsw phrlw pvervel pap paph plsm ktype "
-        "plu psnde pmfu pmfd pa pclv psupsat "
-        "plcrit_aer picrit_aer pre_ice pccn pnice plude "
-        "tendency_loc_t tendency_loc_q tendency_loc_a tendency_loc_cld pcovptot prainfrac_toprfz "
-        "pfsqlf pfsqif pfcqnng pfcqlng pfsqrf pfsqsf pfcqrng pfcqsng "
-        "pfsqltur pfsqitur pfplsl pfplsn pfhpsl pfhpsn").split()]
+    _fields_ = [(n, C.c_void_p) for n in ALL_FIELDS]
 
 
 class Placement(C.Structure):
@@ -144,12 +141,13 @@ PLACE_NONE = 1
 ALLOC_AEROSOLS = 2
 
 
+TEMPLATE_ORDER = list(INPUT_FIELDS)
+TEMPLATE_ORDER.insert(TEMPLATE_ORDER.index("plu") + 1, "plude")   # where the reference's files have it
+TEMPLATE_ORDER += AEROSOL_FIELDS
+
+
 class Template(C.Structure):
-    _fields_ = [("klon", C.c_int), ("klev", C.c_int)] + [(n, C.c_void_p) for n in (
-        "pt pq tendency_tmp_t tendency_tmp_q tendency_tmp_a tendency_tmp_cld "
-        "pvfl pvfi phrsw phrlw pvervel pap paph plsm ktype "
-        "plu plude psnde pmfu pmfd pa pclv psupsat "
-        "plcrit_aer picrit_aer pre_ice pccn pnice").split()]
+    _fields_ = [("klon", C.c_int), ("klev", C.c_int)] + [(n, C.c_void_p) for n in TEMPLATE_ORDER]
 
 
 class Reference(C.Structure):
@@ -512,7 +510,7 @@ def validate_host_state(ds: "Dataset", st: "HostState") -> float:
 
 # the translation unit of the CLOUDSC kernels (cloudsc_gpu.hip and what it includes)
 KERNEL_SOURCES = ("cloudsc_gpu.hip", "cloudsc_kcache.h", "cloudsc_scc.h", "cloudsc_dev.h", "cloudsc_params.h",
-                  "cloudsc_libm.h", "cloudsc_libm_tab.h", "cloudsc_internal.h")
+                  "cloudsc_libm.h", "cloudsc_libm_tab.h", "cloudsc_internal.h", "cloudsc_fields.def")
 
 
 def kernel_source_hash() -> str:

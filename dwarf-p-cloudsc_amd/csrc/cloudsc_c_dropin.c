@@ -45,6 +45,7 @@
 
 #include "cloudsc_c.h"      /* the reference declaration (and yomcst_c.h, yoethf_c.h, yoecldp_c.h) */
 #include "cloudsc_amd.h"
+#include "cloudsc_fields.def"
 
 static void params_from_modules(cloudsc_params_t *p, double ptsphy) {
   const struct TECLDP *y = yrecldp;
@@ -127,16 +128,9 @@ int cloudsc_c(int kidia, int kfdia, int klon, int klev, double ptsphy, double * 
   cloudsc_params_t p;
   params_from_modules(&p, ptsphy);
   const long o = kidia - 1;   /* first computed column: every array starts there */
-  cloudsc_fields_t f = {
-      v_pt + o, v_pq + o, v_tendency_tmp_t + o, v_tendency_tmp_q + o, v_tendency_tmp_a + o, v_tendency_tmp_cld + o,
-      v_pvfl + o, v_pvfi + o, v_phrsw + o, v_phrlw + o, v_pvervel + o, v_pap + o, v_paph + o, v_plsm + o,
-      v_ktype + o, v_plu + o, v_psnde + o, v_pmfu + o, v_pmfd + o, v_pa + o, v_pclv + o, v_psupsat + o,
-      v_plcrit_aer + o, v_picrit_aer + o, v_pre_ice + o, v_pccn + o, v_pnice + o,
-      v_plude + o,
-      v_tendency_loc_t + o, v_tendency_loc_q + o, v_tendency_loc_a + o, v_tendency_loc_cld + o,
-      v_pcovptot + o, v_prainfrac_toprfz + o,
-      v_pfsqlf + o, v_pfsqif + o, v_pfcqnng + o, v_pfcqlng + o, v_pfsqrf + o, v_pfsqsf + o, v_pfcqrng + o,
-      v_pfcqsng + o, v_pfsqltur + o, v_pfsqitur + o, v_pfplsl + o, v_pfplsn + o, v_pfhpsl + o, v_pfhpsn + o};
+  /* every member from the argument of its name (the inventory's member names are the reference's) */
+#define FROM_ARGUMENT(n, N, k, d, i) .n = v_##n + o,
+  cloudsc_fields_t f = {CLOUDSC_FIELDS(FROM_ARGUMENT)};
   const int ncols = kfdia - kidia + 1;
 #ifdef CLOUDSC_DROPIN_PROFILE
   pthread_once(&g_prof_once, start_profile);

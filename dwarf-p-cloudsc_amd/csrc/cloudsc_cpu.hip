@@ -95,33 +95,6 @@ void run_block(const DevParams<real>& c, const KArgs<real>& A, int b, std::vecto
   for (int jl = 0; jl < bsize; jl++) stg(A.prainfrac, u1, (unsigned)jl * (unsigned)sizeof(real), col[jl].cs.rainfrac);
 }
 
-KArgs<double> host_args(const cloudsc_fields_t* f, int ngptot, int nproma, int klev) {
-  KArgs<double> a;
-  std::memset(&a, 0, sizeof(a));
-  a.pt = (const double*)f->pt; a.pq = (const double*)f->pq;
-  a.ttt = (const double*)f->tendency_tmp_t; a.ttq = (const double*)f->tendency_tmp_q;
-  a.tta = (const double*)f->tendency_tmp_a; a.ttcld = (const double*)f->tendency_tmp_cld;
-  a.pvfl = (const double*)f->pvfl; a.pvfi = (const double*)f->pvfi;
-  a.phrsw = (const double*)f->phrsw; a.phrlw = (const double*)f->phrlw; a.pvervel = (const double*)f->pvervel;
-  a.pap = (const double*)f->pap; a.paph = (const double*)f->paph; a.plsm = (const double*)f->plsm;
-  a.ktype = f->ktype;
-  a.plu = (const double*)f->plu; a.psnde = (const double*)f->psnde; a.pmfu = (const double*)f->pmfu;
-  a.pmfd = (const double*)f->pmfd; a.pa = (const double*)f->pa; a.pclv = (const double*)f->pclv;
-  a.psupsat = (const double*)f->psupsat; a.picrit_aer = (const double*)f->picrit_aer;
-  a.pre_ice = (const double*)f->pre_ice; a.pnice = (const double*)f->pnice;
-  a.plude = (double*)f->plude; a.plude_in = (const double*)f->plude;
-  a.tlt = (double*)f->tendency_loc_t; a.tlq = (double*)f->tendency_loc_q;
-  a.tla = (double*)f->tendency_loc_a; a.tlcld = (double*)f->tendency_loc_cld;
-  a.pcovptot = (double*)f->pcovptot; a.prainfrac = (double*)f->prainfrac_toprfz;
-  a.pfsqlf = (double*)f->pfsqlf; a.pfsqif = (double*)f->pfsqif; a.pfcqnng = (double*)f->pfcqnng;
-  a.pfcqlng = (double*)f->pfcqlng; a.pfsqrf = (double*)f->pfsqrf; a.pfsqsf = (double*)f->pfsqsf;
-  a.pfcqrng = (double*)f->pfcqrng; a.pfcqsng = (double*)f->pfcqsng; a.pfsqltur = (double*)f->pfsqltur;
-  a.pfsqitur = (double*)f->pfsqitur; a.pfplsl = (double*)f->pfplsl; a.pfplsn = (double*)f->pfplsn;
-  a.pfhpsl = (double*)f->pfhpsl; a.pfhpsn = (double*)f->pfhpsn;
-  a.ngptot = ngptot; a.nproma = nproma; a.klev = klev;
-  return a;
-}
-
 }  // namespace
 
 extern "C" int cloudsc_cpu_run_threads(int nthreads, int ngptot, int nproma, int klev,
@@ -134,7 +107,7 @@ extern "C" int cloudsc_cpu_run_threads(int nthreads, int ngptot, int nproma, int
   if (aer && (!f->pre_ice || !f->picrit_aer || !f->pnice)) return CLOUDSC_EINVAL;
   if (nthreads <= 0 && (thread_seconds || thread_blocks || thread_columns)) return CLOUDSC_EINVAL;
   const DevParams<double> c = fold_params<double>(*params);
-  const KArgs<double> A = host_args(f, ngptot, nproma, klev);
+  const KArgs<double> A = make_kargs<double>(f, ngptot, nproma, klev, nullptr);
   const int nblocks = ngptot / nproma + (ngptot % nproma ? 1 : 0);
   if (nthreads <= 0) nthreads = (int)std::max(1u, std::thread::hardware_concurrency());
   const int nreq = nthreads;                 // the caller's per-thread arrays have nreq entries

@@ -134,48 +134,15 @@ const ParamSet* device_default_params(int device) {
 }
 
 bool fields_complete(const cloudsc_fields_t* f) {
-  const void* req[] = {f->pt, f->pq, f->tendency_tmp_t, f->tendency_tmp_q, f->tendency_tmp_a,
-                       f->tendency_tmp_cld, f->pvfl, f->pvfi, f->phrsw, f->phrlw, f->pvervel, f->pap,
-                       f->paph, f->plsm, f->ktype, f->plu, f->psnde, f->pmfu, f->pmfd, f->pa, f->pclv,
-                       f->psupsat, f->plude, f->tendency_loc_t, f->tendency_loc_q, f->tendency_loc_a,
-                       f->tendency_loc_cld, f->pcovptot, f->prainfrac_toprfz, f->pfsqlf, f->pfsqif,
-                       f->pfcqnng, f->pfcqlng, f->pfsqrf, f->pfsqsf, f->pfcqrng, f->pfcqsng,
-                       f->pfsqltur, f->pfsqitur, f->pfplsl, f->pfplsn, f->pfhpsl, f->pfhpsn};
-  for (const void* q : req)
-    if (!q) return false;
+  const void* const* p = (const void* const*)f;
+  for (int m = 0; m < kNumFields; m++)
+    if (!p[m] && kFieldTable[m].dir != CLOUDSC_FD_AEROSOL) return false;
   return true;
 }
 
 }  // namespace cloudsc_impl
 
 namespace {
-
-template <typename real>
-KArgs<real> make_args(const cloudsc_fields_t* f, int ngptot, int nproma, int klev, const ParamSet& ps) {
-  KArgs<real> a;
-  a.pt = (const real*)f->pt; a.pq = (const real*)f->pq;
-  a.ttt = (const real*)f->tendency_tmp_t; a.ttq = (const real*)f->tendency_tmp_q;
-  a.tta = (const real*)f->tendency_tmp_a; a.ttcld = (const real*)f->tendency_tmp_cld;
-  a.pvfl = (const real*)f->pvfl; a.pvfi = (const real*)f->pvfi;
-  a.phrsw = (const real*)f->phrsw; a.phrlw = (const real*)f->phrlw; a.pvervel = (const real*)f->pvervel;
-  a.pap = (const real*)f->pap; a.paph = (const real*)f->paph; a.plsm = (const real*)f->plsm;
-  a.ktype = f->ktype;
-  a.plu = (const real*)f->plu; a.psnde = (const real*)f->psnde; a.pmfu = (const real*)f->pmfu;
-  a.pmfd = (const real*)f->pmfd; a.pa = (const real*)f->pa; a.pclv = (const real*)f->pclv;
-  a.psupsat = (const real*)f->psupsat; a.picrit_aer = (const real*)f->picrit_aer;
-  a.pre_ice = (const real*)f->pre_ice; a.pnice = (const real*)f->pnice;
-  a.plude = (real*)f->plude; a.plude_in = (const real*)f->plude; a.tlt = (real*)f->tendency_loc_t; a.tlq = (real*)f->tendency_loc_q;
-  a.tla = (real*)f->tendency_loc_a; a.tlcld = (real*)f->tendency_loc_cld;
-  a.pcovptot = (real*)f->pcovptot; a.prainfrac = (real*)f->prainfrac_toprfz;
-  a.pfsqlf = (real*)f->pfsqlf; a.pfsqif = (real*)f->pfsqif; a.pfcqnng = (real*)f->pfcqnng;
-  a.pfcqlng = (real*)f->pfcqlng; a.pfsqrf = (real*)f->pfsqrf; a.pfsqsf = (real*)f->pfsqsf;
-  a.pfcqrng = (real*)f->pfcqrng; a.pfcqsng = (real*)f->pfcqsng; a.pfsqltur = (real*)f->pfsqltur;
-  a.pfsqitur = (real*)f->pfsqitur; a.pfplsl = (real*)f->pfplsl; a.pfplsn = (real*)f->pfplsn;
-  a.pfhpsl = (real*)f->pfhpsl; a.pfhpsn = (real*)f->pfhpsn;
-  a.par = (const DevParams<real>*)((const char*)ps.dev + (sizeof(real) == 8 ? 0 : kSpOffset));
-  a.ngptot = ngptot; a.nproma = nproma; a.klev = klev;
-  return a;
-}
 
 // the launch's parameter block, as a constant-address-space pointer (scalar
 // loads), typed with the kernel's choice of single-precision exp/pow forms
@@ -454,7 +421,8 @@ int launch_v(hipStream_t st, int variant, const cloudsc_fields_t* f, int ngptot,
 #ifdef CLOUDSC_ONLY_KSEG
   if (variant != CLOUDSC_VARIANT_KSEG || ps.aer || sizeof(real) != CLOUDSC_ONLY_KSEG) return CLOUDSC_EINVAL;
 #endif
-  KArgs<real> a = make_args<real>(f, ngptot, nproma, klev, ps);
+  KArgs<real> a = make_kargs<real>(
+      f, ngptot, nproma, klev, (const DevParams<real>*)((const char*)ps.dev + (sizeof(real) == 8 ? 0 : kSpOffset)));
   if (plude_in) a.plude_in = (const real*)plude_in;
   const int nblocks = ngptot / nproma + (ngptot % nproma ? 1 : 0);
   const bool aer = ps.aer;

@@ -8,45 +8,34 @@
 #include <functional>
 
 #include "cloudsc_amd.h"
+#include "cloudsc_fields.def"
 
 namespace cloudsc_impl {
 
 constexpr int kMaxDevices = 64;
 
-// The fields of cloudsc_fields_t: shape kind, direction, element type, in
-// member order (include/cloudsc_amd.h).
-enum FieldKind { FK_LEVEL, FK_HALF, FK_SPECIES, FK_SURFACE };
-enum FieldDir { FD_IN, FD_INOUT, FD_OUT, FD_AEROSOL };
-struct FieldDesc { int kind, dir, is_int; };
-// cloudsc_fields_t member order (include/cloudsc_amd.h)
-inline constexpr FieldDesc kFieldTable[] = {
-    {FK_LEVEL, FD_IN, 0},   {FK_LEVEL, FD_IN, 0},   {FK_LEVEL, FD_IN, 0},   {FK_LEVEL, FD_IN, 0},
-    {FK_LEVEL, FD_IN, 0},   {FK_SPECIES, FD_IN, 0}, {FK_LEVEL, FD_IN, 0},   {FK_LEVEL, FD_IN, 0},
-    {FK_LEVEL, FD_IN, 0},   {FK_LEVEL, FD_IN, 0},   {FK_LEVEL, FD_IN, 0},   {FK_LEVEL, FD_IN, 0},
-    {FK_HALF, FD_IN, 0},    {FK_SURFACE, FD_IN, 0}, {FK_SURFACE, FD_IN, 1}, {FK_LEVEL, FD_IN, 0},
-    {FK_LEVEL, FD_IN, 0},   {FK_LEVEL, FD_IN, 0},   {FK_LEVEL, FD_IN, 0},   {FK_LEVEL, FD_IN, 0},
-    {FK_SPECIES, FD_IN, 0}, {FK_LEVEL, FD_IN, 0},
-    {FK_LEVEL, FD_AEROSOL, 0}, {FK_LEVEL, FD_AEROSOL, 0}, {FK_LEVEL, FD_AEROSOL, 0},
-    {FK_LEVEL, FD_AEROSOL, 0}, {FK_LEVEL, FD_AEROSOL, 0},
-    {FK_LEVEL, FD_INOUT, 0},
-    {FK_LEVEL, FD_OUT, 0},  {FK_LEVEL, FD_OUT, 0},  {FK_LEVEL, FD_OUT, 0},  {FK_SPECIES, FD_OUT, 0},
-    {FK_LEVEL, FD_OUT, 0},  {FK_SURFACE, FD_OUT, 0},
-    {FK_HALF, FD_OUT, 0},   {FK_HALF, FD_OUT, 0},   {FK_HALF, FD_OUT, 0},   {FK_HALF, FD_OUT, 0},
-    {FK_HALF, FD_OUT, 0},   {FK_HALF, FD_OUT, 0},   {FK_HALF, FD_OUT, 0},   {FK_HALF, FD_OUT, 0},
-    {FK_HALF, FD_OUT, 0},   {FK_HALF, FD_OUT, 0},   {FK_HALF, FD_OUT, 0},   {FK_HALF, FD_OUT, 0},
-    {FK_HALF, FD_OUT, 0},   {FK_HALF, FD_OUT, 0}};
-inline constexpr int kNumFields = (int)(sizeof(kFieldTable) / sizeof(kFieldTable[0]));
-static_assert(sizeof(cloudsc_fields_t) == kNumFields * sizeof(void*), "field table out of sync with the header");
+// The fields of cloudsc_fields_t in member order, generated from the one inventory (cloudsc_fields.def,
+// which also holds CLOUDSC_FK_* / CLOUDSC_FD_* and binds its lists to include/cloudsc_amd.h)
+struct FieldDesc { const char* name; int kind, dir, is_int; };
+#define CLOUDSC_FIELD_DESC(n, N, k, d, i) {#n, CLOUDSC_FK_##k, CLOUDSC_FD_##d, i},
+inline constexpr FieldDesc kFieldTable[] = {CLOUDSC_FIELDS(CLOUDSC_FIELD_DESC)};
+inline constexpr int kNumFields = CLOUDSC_NFIELDS;
+
+// fields of `kind` whose direction is in the bit set dirs (1 << FD_*)
+constexpr int count_fields(int kind, int dirs) {
+  int n = 0;
+  for (const FieldDesc& d : kFieldTable) n += d.kind == kind && (dirs >> d.dir & 1);
+  return n;
+}
 
 inline size_t per_block_elems(int kind, int nproma, int klev) {
   switch (kind) {
-    case FK_LEVEL: return (size_t)klev * nproma;
-    case FK_HALF: return (size_t)(klev + 1) * nproma;
-    case FK_SPECIES: return (size_t)CLOUDSC_NCLV * klev * nproma;
+    case CLOUDSC_FK_LEVEL: return (size_t)klev * nproma;
+    case CLOUDSC_FK_HALF: return (size_t)(klev + 1) * nproma;
+    case CLOUDSC_FK_SPECIES: return (size_t)CLOUDSC_NCLV * klev * nproma;
     default: return (size_t)nproma;
   }
 }
-
 
 // One parameter set on one device: the host-folded fp64 and fp32 DevParams
 // blocks in device memory (read by the kernels through a KArgs pointer), plus

@@ -29,23 +29,23 @@ static void set_err(const char *fmt, ...) {
 }
 const char *cloudsc_io_last_error(void) { return g_err; }
 
-const char *const cloudsc_io_input_names[CLOUDSC_IO_NIN] = {
-    "PT", "PQ", "TENDENCY_TMP_T", "TENDENCY_TMP_Q", "TENDENCY_TMP_A", "TENDENCY_TMP_CLD",
-    "PVFL", "PVFI", "PHRSW", "PHRLW", "PVERVEL", "PAP", "PAPH", "PLSM", "KTYPE",
-    "PLU", "PLUDE", "PSNDE", "PMFU", "PMFD", "PA", "PCLV", "PSUPSAT",
-    "PLCRIT_AER", "PICRIT_AER", "PRE_ICE", "PCCN", "PNICE"};
-const int cloudsc_io_input_kind[CLOUDSC_IO_NIN] = {
-    0, 0, 0, 0, 0, 2, 0, 0, 0, 0, 0, 0, 1, 3, 3, 0, 0, 0, 0, 0, 0, 2, 0, 0, 0, 0, 0, 0};
-
-const char *const cloudsc_io_ref_names[CLOUDSC_NVALID] = {
-    "PLUDE", "PCOVPTOT", "PRAINFRAC_TOPRFZ", "PFSQLF", "PFSQIF", "PFCQLNG", "PFCQNNG",
-    "PFSQRF", "PFSQSF", "PFCQRNG", "PFCQSNG", "PFSQLTUR", "PFSQITUR", "PFPLSL", "PFPLSN",
-    "PFHPSL", "PFHPSN", "TENDENCY_LOC_A", "TENDENCY_LOC_Q", "TENDENCY_LOC_T", "TENDENCY_LOC_CLD"};
-const char *const cloudsc_io_print_names[CLOUDSC_NVALID] = {
-    "PLUDE", "PCOVPTOT", "PRAINFRAC_TOPRFZ", "PFSQLF", "PFSQIF", "PFCQLNG", "PFCQNNG",
-    "PFSQRF", "PFSQSF", "PFCQRNG", "PFCQSNG", "PFSQLTUR", "PFSQITUR", "PFPLSL", "PFPLSN",
-    "PFHPSL", "PFHPSN", "TENDENCY_LOC%A", "TENDENCY_LOC%Q", "TENDENCY_LOC%T", "TENDENCY_LOC%CLD"};
-const int cloudsc_io_ref_kind[CLOUDSC_NVALID] = {0, 0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 2};
+/* the name / kind tables, generated from the inventory (cloudsc_fields.def): the
+ * template's rows at their template position, the validated rows at their id */
+#define IN_NAME(n, N, k, d, i) CLOUDSC_IF_TEMPLATE_##d([CLOUDSC_T_##n] = #N, )
+#define IN_KIND(n, N, k, d, i) CLOUDSC_IF_TEMPLATE_##d([CLOUDSC_T_##n] = CLOUDSC_FK_##k, )
+#define REF_NAME(n, N, k, d, i) CLOUDSC_IF_VALIDATED_##d([CLOUDSC_F_##N] = #N, )
+#define REF_KIND(n, N, k, d, i) CLOUDSC_IF_VALIDATED_##d([CLOUDSC_F_##N] = CLOUDSC_FK_##k, )
+#define PRINT_NAME(N, p) [CLOUDSC_F_##N] = p,
+const char *const cloudsc_io_input_names[CLOUDSC_IO_NIN] = {CLOUDSC_FIELDS(IN_NAME)};
+const int cloudsc_io_input_kind[CLOUDSC_IO_NIN] = {CLOUDSC_FIELDS(IN_KIND)};
+const char *const cloudsc_io_ref_names[CLOUDSC_NVALID] = {CLOUDSC_FIELDS(REF_NAME)};
+const int cloudsc_io_ref_kind[CLOUDSC_NVALID] = {CLOUDSC_FIELDS(REF_KIND)};
+const char *const cloudsc_io_print_names[CLOUDSC_NVALID] = {CLOUDSC_VALIDATED_ORDER(PRINT_NAME)};
+/* the aerosol inputs are the template's last (CLOUDSC_IO_FIRST_AEROSOL) */
+#define AEROSOLS_LAST(n, N, k, d, i)                                                                        \
+  CLOUDSC_IF_TEMPLATE_##d(_Static_assert((CLOUDSC_FD_##d == CLOUDSC_FD_AEROSOL) ==                          \
+                                         ((int)CLOUDSC_T_##n >= (int)CLOUDSC_IO_FIRST_AEROSOL), #n);)
+CLOUDSC_FIELDS(AEROSOLS_LAST)
 
 /* HDF5 scalar names, in cloudsc_params_t order (doubles ptsphy..nshapeq, then
  * the ints); the raw params.txt uses the same names lower-cased without the
@@ -102,9 +102,9 @@ static void raw_key(const char *h5name, char *out, size_t n) {
 
 long long cloudsc_io_elems(int kind, int klev, int klon) {
   switch (kind) {
-    case 0: return (long long)klev * klon;
-    case 1: return (long long)(klev + 1) * klon;
-    case 2: return (long long)CLOUDSC_NCLV * klev * klon;
+    case CLOUDSC_FK_LEVEL: return (long long)klev * klon;
+    case CLOUDSC_FK_HALF: return (long long)(klev + 1) * klon;
+    case CLOUDSC_FK_SPECIES: return (long long)CLOUDSC_NCLV * klev * klon;
     default: return klon;
   }
 }
@@ -737,13 +737,9 @@ void cloudsc_io_template(const cloudsc_dataset_t *ds, cloudsc_template_t *t) {
   memset(t, 0, sizeof(*t));
   t->klon = ds->klon;
   t->klev = ds->klev;
-  const double *const *in = (const double *const *)ds->in;
-  t->pt = in[0]; t->pq = in[1]; t->tendency_tmp_t = in[2]; t->tendency_tmp_q = in[3];
-  t->tendency_tmp_a = in[4]; t->tendency_tmp_cld = in[5]; t->pvfl = in[6]; t->pvfi = in[7];
-  t->phrsw = in[8]; t->phrlw = in[9]; t->pvervel = in[10]; t->pap = in[11]; t->paph = in[12];
-  t->plsm = in[13]; t->ktype = ds->ktype; t->plu = in[15]; t->plude = in[16]; t->psnde = in[17];
-  t->pmfu = in[18]; t->pmfd = in[19]; t->pa = in[20]; t->pclv = in[21]; t->psupsat = in[22];
-  t->plcrit_aer = in[23]; t->picrit_aer = in[24]; t->pre_ice = in[25]; t->pccn = in[26]; t->pnice = in[27];
+#define TEMPLATE_VIEW(n) t->n = (const void *)ds->in[CLOUDSC_T_##n];
+  CLOUDSC_TEMPLATE_ORDER(TEMPLATE_VIEW)
+  t->ktype = ds->ktype;   /* the one int array: not in ds->in */
 }
 
 void cloudsc_io_reference(const cloudsc_dataset_t *ds, cloudsc_reference_t *r) {
@@ -755,13 +751,9 @@ void cloudsc_io_reference(const cloudsc_dataset_t *ds, cloudsc_reference_t *r) {
 /* ------------------------------------------------------------------------ */
 /* host block layout: expansion and statistics                               */
 /* ------------------------------------------------------------------------ */
-static int kind_nlev(int kind, int klev) {
-  return kind == 0 ? klev : kind == 1 ? klev + 1 : kind == 2 ? CLOUDSC_NCLV * klev : 1;
-}
-
 void cloudsc_io_expand(const void *src, int kind, int is_int, int klev, int klon, int ngptot, int nproma,
                        long long col_offset, int elem_size, void *dst) {
-  const int nlev = kind_nlev(kind, klev);
+  const int nlev = (int)cloudsc_io_elems(kind, klev, 1);   /* rows per column */
   const long long nb = ngptot / nproma + (ngptot % nproma ? 1 : 0);
   for (long long b = 0; b < nb; b++)
     for (int l = 0; l < nlev; l++)
@@ -788,7 +780,7 @@ static void dd_acc(double *hi, double *lo, double x) {
 
 void cloudsc_io_field_stats(const double *ref, int kind, int klev, int klon, const void *field, int elem_size,
                             int ngptot, int nproma, long long col_offset, cloudsc_stats_t *st) {
-  const int nlev = kind_nlev(kind, klev);
+  const int nlev = (int)cloudsc_io_elems(kind, klev, 1);   /* rows per column */
   const long long nb = ngptot / nproma + (ngptot % nproma ? 1 : 0);
   double mn = DBL_MAX, mx = -DBL_MAX, me = 0.0;
   double es = 0.0, es_lo = 0.0, rs = 0.0, rs_lo = 0.0;   /* double-double sums, as the device statistics */

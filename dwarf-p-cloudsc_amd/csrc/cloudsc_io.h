@@ -23,13 +23,17 @@
 #define CLOUDSC_IO_H
 
 #include "cloudsc_amd.h"
+#include "cloudsc_fields.def"
 
 #ifdef __cplusplus
 extern "C" {
 #endif
 
-/* input fields of the template, in cloudsc_template_t order */
-#define CLOUDSC_IO_NIN 28
+/* input fields of the template, in cloudsc_template_t order (the template order of cloudsc_fields.def): KTYPE
+ * is index CLOUDSC_IO_KTYPE, the aerosol inputs (optional) are the last, from CLOUDSC_IO_FIRST_AEROSOL on */
+#define CLOUDSC_IO_IS_AEROSOL(n, N, k, d, i) +(CLOUDSC_FD_##d == CLOUDSC_FD_AEROSOL)
+enum { CLOUDSC_IO_NIN = CLOUDSC_NTEMPLATE, CLOUDSC_IO_KTYPE = CLOUDSC_T_ktype,
+       CLOUDSC_IO_FIRST_AEROSOL = CLOUDSC_NTEMPLATE - (0 CLOUDSC_FIELDS(CLOUDSC_IO_IS_AEROSOL)) };
 typedef struct cloudsc_dataset {
   int klon, klev;
   cloudsc_params_t params;
@@ -42,13 +46,10 @@ typedef struct cloudsc_dataset {
   char source[512];                /* what was read, for the log */
 } cloudsc_dataset_t;
 
-/* Upper-case dataset / file names: inputs (KTYPE is index CLOUDSC_IO_KTYPE). */
+/* Upper-case dataset / file names: inputs. */
 extern const char *const cloudsc_io_input_names[CLOUDSC_IO_NIN];
-#define CLOUDSC_IO_KTYPE 14
-/* field kind: 0 = [lev][klon], 1 = [lev+1][klon], 2 = [nclv][lev][klon], 3 = [klon] */
+/* field kind (enum cloudsc_field_kind): 0 = [lev][klon], 1 = [lev+1][klon], 2 = [nclv][lev][klon], 3 = [klon] */
 extern const int cloudsc_io_input_kind[CLOUDSC_IO_NIN];
-/* aerosol inputs (optional) are the last five */
-#define CLOUDSC_IO_FIRST_AEROSOL 23
 /* HDF5 / file names of the 21 validated fields (cloudsc_field_id order) and
  * the names the dwarf prints (cloudsc_validate.c:195-215) */
 extern const char *const cloudsc_io_ref_names[CLOUDSC_NVALID];

@@ -3,11 +3,14 @@
 // variant).  Products and reciprocals the reference evaluates per point are
 // computed once here with the SAME single IEEE operation, so results do not
 // change (each member of DevParams cites the reference line it replaces).
+// And the one place cloudsc_fields_t becomes the kernels' argument block: KArgs
+// (cloudsc_kcache.h) keeps its own short names, read at fixed kernarg offsets,
+// so that mapping is written by hand.
 #pragma once
 #include <cstring>
 
 #include "cloudsc_amd.h"
-#include "cloudsc_dev.h"
+#include "cloudsc_kcache.h"
 
 namespace cloudsc {
 
@@ -53,6 +56,29 @@ inline DevParams<real> fold_params(const cloudsc_params_t& p) {
   d.laericesed = p.laericesed;
   d.laericeauto = p.laericeauto;
   return d;
+}
+
+// plude read in place (plude_in == plude); par: the launch's device parameter block, NULL for the host build
+template <typename real>
+KArgs<real> make_kargs(const cloudsc_fields_t* f, int ngptot, int nproma, int klev, const DevParams<real>* par) {
+  using in = const real*;
+  using out = real*;
+  KArgs<real> a{};
+  a.pt = (in)f->pt; a.pq = (in)f->pq; a.ttt = (in)f->tendency_tmp_t; a.ttq = (in)f->tendency_tmp_q;
+  a.tta = (in)f->tendency_tmp_a; a.ttcld = (in)f->tendency_tmp_cld; a.pvfl = (in)f->pvfl; a.pvfi = (in)f->pvfi;
+  a.phrsw = (in)f->phrsw; a.phrlw = (in)f->phrlw; a.pvervel = (in)f->pvervel; a.pap = (in)f->pap;
+  a.paph = (in)f->paph; a.plsm = (in)f->plsm; a.ktype = f->ktype; a.plu = (in)f->plu; a.psnde = (in)f->psnde;
+  a.pmfu = (in)f->pmfu; a.pmfd = (in)f->pmfd; a.pa = (in)f->pa; a.pclv = (in)f->pclv; a.psupsat = (in)f->psupsat;
+  a.picrit_aer = (in)f->picrit_aer; a.pre_ice = (in)f->pre_ice; a.pnice = (in)f->pnice;   // plcrit_aer, pccn: not read
+  a.plude_in = (in)f->plude; a.plude = (out)f->plude; a.tlt = (out)f->tendency_loc_t; a.tlq = (out)f->tendency_loc_q;
+  a.tla = (out)f->tendency_loc_a; a.tlcld = (out)f->tendency_loc_cld; a.pcovptot = (out)f->pcovptot;
+  a.prainfrac = (out)f->prainfrac_toprfz; a.pfsqlf = (out)f->pfsqlf; a.pfsqif = (out)f->pfsqif;
+  a.pfcqnng = (out)f->pfcqnng; a.pfcqlng = (out)f->pfcqlng; a.pfsqrf = (out)f->pfsqrf; a.pfsqsf = (out)f->pfsqsf;
+  a.pfcqrng = (out)f->pfcqrng; a.pfcqsng = (out)f->pfcqsng; a.pfsqltur = (out)f->pfsqltur;
+  a.pfsqitur = (out)f->pfsqitur; a.pfplsl = (out)f->pfplsl; a.pfplsn = (out)f->pfplsn; a.pfhpsl = (out)f->pfhpsl;
+  a.pfhpsn = (out)f->pfhpsn;
+  a.par = par; a.ngptot = ngptot; a.nproma = nproma; a.klev = klev;
+  return a;
 }
 
 }  // namespace cloudsc

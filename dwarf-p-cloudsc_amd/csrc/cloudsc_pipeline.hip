@@ -399,8 +399,8 @@ int run_on_engines(cloudsc_host_pipeline* p, int variant, int vk, double* ms) {
     const int nb = (b0 + p->chunk_blocks <= p->nblocks) ? p->chunk_blocks : p->nblocks - b0;
     void* const* df = (void* const*)&s.dev;
     auto selected = [&](int dir, int pt) {
-      if (!in) return dir == FD_OUT || dir == FD_INOUT;
-      return dir != FD_OUT && (pt < 0 || (pt == 0) == (dir != FD_INOUT));
+      if (!in) return dir == CLOUDSC_FD_OUT || dir == CLOUDSC_FD_INOUT;
+      return dir != CLOUDSC_FD_OUT && (pt < 0 || (pt == 0) == (dir != CLOUDSC_FD_INOUT));
     };
     int n = 0;                 // copies of this call not yet issued
     for (int i = 0; i < kNumFields; i++)
@@ -461,7 +461,7 @@ int run_on_engines(cloudsc_host_pipeline* p, int variant, int vk, double* ms) {
         // or the final wait below would never see the signal reach zero
         int n1 = 0;
         for (int i = 0; i < kNumFields; i++)
-          if (hf[i] && kFieldTable[i].dir == FD_INOUT) n1++;
+          if (hf[i] && kFieldTable[i].dir == CLOUDSC_FD_INOUT) n1++;
         hsa_signal_subtract_screlease(p->sig_in[c % nslots], n1);
         break;
       }
@@ -529,12 +529,13 @@ int copies_only_on_engines(cloudsc_host_pipeline* p, double* ms) {
       int n = 0;
       for (int i = 0; i < kNumFields; i++) {
         const int dir = kFieldTable[i].dir;
-        if (hf[i] && (in ? dir != FD_OUT : (dir == FD_OUT || dir == FD_INOUT))) n++;
+        if (hf[i] && (in ? dir != CLOUDSC_FD_OUT : (dir == CLOUDSC_FD_OUT || dir == CLOUDSC_FD_INOUT))) n++;
       }
       hsa_signal_store_screlease(sg, n);
       for (int i = 0; i < kNumFields; i++) {
         const FieldDesc& d = kFieldTable[i];
-        if (!hf[i] || !(in ? d.dir != FD_OUT : (d.dir == FD_OUT || d.dir == FD_INOUT))) continue;
+        const bool moved = in ? d.dir != CLOUDSC_FD_OUT : (d.dir == CLOUDSC_FD_OUT || d.dir == CLOUDSC_FD_INOUT);
+        if (!hf[i] || !moved) continue;
         const size_t per = per_block_elems(d.kind, p->nproma, p->klev) * (d.is_int ? sizeof(int) : p->es);
         char* h = (char*)p->host_dev[i] + (size_t)b0 * per;
         const hsa_status_t st =
@@ -684,7 +685,7 @@ int cloudsc_host_pipeline_run(cloudsc_host_pipeline_t* p, int variant, double* m
       if (part == 1 && reuse) HIPCHK(hipStreamWaitEvent(p->st_in, s.out_done, 0));
       for (int i = 0; i < kNumFields; i++) {
         const FieldDesc& d = kFieldTable[i];
-        if (!hf[i] || d.dir == FD_OUT || (part == 0) != (d.dir != FD_INOUT)) continue;
+        if (!hf[i] || d.dir == CLOUDSC_FD_OUT || (part == 0) != (d.dir != CLOUDSC_FD_INOUT)) continue;
         const size_t eb = d.is_int ? sizeof(int) : p->es;
         const size_t per = per_block_elems(d.kind, p->nproma, p->klev) * eb;
         HIPCHK(hipMemcpyAsync(df[i], (const char*)hf[i] + (size_t)b0 * per, (size_t)nb * per, hipMemcpyHostToDevice,
@@ -705,7 +706,7 @@ int cloudsc_host_pipeline_run(cloudsc_host_pipeline_t* p, int variant, double* m
     const bool blit = g_pipe_copy.load(std::memory_order_relaxed) == PC_HIP_BLIT;
     for (int i = 0; i < kNumFields; i++) {
       const FieldDesc& d = kFieldTable[i];
-      if (!hf[i] || !(d.dir == FD_OUT || d.dir == FD_INOUT)) continue;
+      if (!hf[i] || !(d.dir == CLOUDSC_FD_OUT || d.dir == CLOUDSC_FD_INOUT)) continue;
       const size_t per = per_block_elems(d.kind, p->nproma, p->klev) * p->es;
       if (blit && p->host_dev[i] && bs.n < kMaxBlitSeg) {
         bs.src[bs.n] = (const char*)df[i];
@@ -958,7 +959,7 @@ extern "C" int cloudsc_host_run(int device, int precision, int variant, int ngpt
   for (int pass = 0; pass < 2; pass++)
     for (int i = 0; i < kNumFields; i++) {
       const FieldDesc& d = kFieldTable[i];
-      if (!hf[i] || (pass == 0) != (d.dir != FD_OUT)) continue;
+      if (!hf[i] || (pass == 0) != (d.dir != CLOUDSC_FD_OUT)) continue;
       bytes[i] = (size_t)nblocks * per_block_elems(d.kind, nproma, klev) * (d.is_int ? sizeof(int) : es);
       off[i] = total;
       total += (bytes[i] + 255) & ~(size_t)255;
@@ -992,7 +993,7 @@ extern "C" int cloudsc_host_run(int device, int precision, int variant, int ngpt
     const size_t eb = d.is_int ? sizeof(int) : es;
     const size_t per = per_block_elems(d.kind, nproma, klev) * eb;
     df[i] = ctx->dbuf + off[i];
-    if (d.dir != FD_OUT)
+    if (d.dir != CLOUDSC_FD_OUT)
       pack_active(ctx->stage + off[i], (const char*)hf[i], per, (size_t)(nblocks - 1) * per, (size_t)nproma * eb,
                   (size_t)bsize * eb, true);
   }
@@ -1039,7 +1040,7 @@ extern "C" int cloudsc_host_run(int device, int precision, int variant, int ngpt
   // while the device works: fault in the caller's output pages the unpack will write
   for (int i = 0; i < kNumFields; i++) {
     const FieldDesc& d = kFieldTable[i];
-    if (!hf[i] || !(d.dir == FD_OUT || d.dir == FD_INOUT)) continue;
+    if (!hf[i] || !(d.dir == CLOUDSC_FD_OUT || d.dir == CLOUDSC_FD_INOUT)) continue;
     const size_t per = per_block_elems(d.kind, nproma, klev) * es;
     prefault_active((const char*)hf[i], per, (size_t)(nblocks - 1) * per, (size_t)nproma * es, (size_t)bsize * es);
   }
@@ -1048,7 +1049,7 @@ extern "C" int cloudsc_host_run(int device, int precision, int variant, int ngpt
   if (vk == CLOUDSC_VARIANT_KSEG && (rc = kseg_check(device, ctx->st, ctx->scratch))) return rc;
   for (int i = 0; i < kNumFields; i++) {
     const FieldDesc& d = kFieldTable[i];
-    if (!hf[i] || !(d.dir == FD_OUT || d.dir == FD_INOUT)) continue;
+    if (!hf[i] || !(d.dir == CLOUDSC_FD_OUT || d.dir == CLOUDSC_FD_INOUT)) continue;
     const size_t per = per_block_elems(d.kind, nproma, klev) * es;
     pack_active(ctx->stage + off[i], (const char*)hf[i], per, (size_t)(nblocks - 1) * per, (size_t)nproma * es,
                 (size_t)bsize * es, false);

@@ -27,9 +27,14 @@ using namespace cloudsc_impl;
 
 namespace {
 
-constexpr int kProbeInLevel = 17;   // level inputs, one plane each
-constexpr int kProbeOutLevel = 5;   // level outputs, one plane each (plude, tendency_loc_t/q/a, pcovptot)
-constexpr int kProbeOutHalf = 14;   // flux outputs, written at level k+1
+// what the probe streams, counted from the field table (not the aerosol and surface inputs)
+constexpr int kRead = 1 << CLOUDSC_FD_IN, kWritten = 1 << CLOUDSC_FD_INOUT | 1 << CLOUDSC_FD_OUT;
+constexpr int kProbeInLevel = count_fields(CLOUDSC_FK_LEVEL, kRead);      // level inputs, one plane each
+constexpr int kProbeOutLevel = count_fields(CLOUDSC_FK_LEVEL, kWritten);  // level outputs, one plane each (plude, ...)
+constexpr int kProbeOutHalf = count_fields(CLOUDSC_FK_HALF, kWritten);    // flux outputs, written at level k+1
+static_assert(count_fields(CLOUDSC_FK_SPECIES, kRead) == 2 && count_fields(CLOUDSC_FK_HALF, kRead) == 1 &&
+              count_fields(CLOUDSC_FK_SPECIES, kWritten) == 1 && count_fields(CLOUDSC_FK_SURFACE, kWritten) == 1,
+              "ProbeArgs' other slots");
 constexpr int kPlaceSetsFields = 8; // whole output sets tried by cloudsc_fields_alloc
 
 struct ProbeArgs {
@@ -141,22 +146,21 @@ __global__ void __launch_bounds__(64) place_probe_kernel(const ProbeArgs a) {
 ProbeArgs probe_args(const cloudsc_fields_t* f, int ngptot, int nproma, int klev, bool read) {
   ProbeArgs a;
   std::memset(&a, 0, sizeof(a));
-  if (read) {
-    const void* lv[kProbeInLevel] = {f->pt, f->pq, f->tendency_tmp_t, f->tendency_tmp_q, f->tendency_tmp_a,
-                                     f->pvfl, f->pvfi, f->phrsw, f->phrlw, f->pvervel, f->pap, f->plu,
-                                     f->psnde, f->pmfu, f->pmfd, f->pa, f->psupsat};
-    for (int q = 0; q < kProbeInLevel; q++) a.in_level[q] = lv[q];
-    a.in_species[0] = f->tendency_tmp_cld;
-    a.in_species[1] = f->pclv;
-    a.paph = f->paph;
+  int nil = 0, nis = 0, nol = 0, noh = 0;
+  for (int m = 0; m < kNumFields; m++) {
+    const FieldDesc& d = kFieldTable[m];
+    void* p = ((void* const*)f)[m];
+    if (d.dir == CLOUDSC_FD_IN && read) {
+      if (d.kind == CLOUDSC_FK_LEVEL) a.in_level[nil++] = p;
+      else if (d.kind == CLOUDSC_FK_SPECIES) a.in_species[nis++] = p;
+      else if (d.kind == CLOUDSC_FK_HALF) a.paph = p;
+    } else if (d.dir == CLOUDSC_FD_INOUT || d.dir == CLOUDSC_FD_OUT) {
+      if (d.kind == CLOUDSC_FK_LEVEL) a.out_level[nol++] = p;
+      else if (d.kind == CLOUDSC_FK_SPECIES) a.out_species = p;
+      else if (d.kind == CLOUDSC_FK_HALF) a.out_half[noh++] = p;
+      else a.out_surf = p;
+    }
   }
-  void* ol[kProbeOutLevel] = {f->plude, f->tendency_loc_t, f->tendency_loc_q, f->tendency_loc_a, f->pcovptot};
-  for (int q = 0; q < kProbeOutLevel; q++) a.out_level[q] = ol[q];
-  a.out_species = f->tendency_loc_cld;
-  void* oh[kProbeOutHalf] = {f->pfsqlf, f->pfsqif, f->pfcqnng, f->pfcqlng, f->pfsqrf, f->pfsqsf, f->pfcqrng,
-                             f->pfcqsng, f->pfsqltur, f->pfsqitur, f->pfplsl, f->pfplsn, f->pfhpsl, f->pfhpsn};
-  for (int q = 0; q < kProbeOutHalf; q++) a.out_half[q] = oh[q];
-  a.out_surf = f->prainfrac_toprfz;
   a.ngptot = ngptot;
   a.nproma = nproma;
   a.klev = klev;
@@ -486,7 +490,7 @@ extern "C" int cloudsc_fields_alloc(int device, int precision, int ngptot, int n
   HIPCHK(hipSetDevice(device));
   void** df = (void**)out;
   for (int m = 0; m < kNumFields; m++) {
-    if (kFieldTable[m].dir == FD_AEROSOL && !(flags & CLOUDSC_ALLOC_AEROSOLS)) continue;
+    if (kFieldTable[m].dir == CLOUDSC_FD_AEROSOL && !(flags & CLOUDSC_ALLOC_AEROSOLS)) continue;
     void* p = nullptr;
     const hipError_t e = dev_malloc(&p, member_bytes(m, precision, ngptot, nproma, klev));
     if (e != hipSuccess) {
@@ -503,7 +507,7 @@ extern "C" int cloudsc_fields_alloc(int device, int precision, int ngptot, int n
   size_t bytes[kNumFields], set_bytes = 0;
   int n = 0;
   for (int m = 0; m < kNumFields; m++)
-    if (kFieldTable[m].dir == FD_OUT || kFieldTable[m].dir == FD_INOUT) {
+    if (kFieldTable[m].dir == CLOUDSC_FD_OUT || kFieldTable[m].dir == CLOUDSC_FD_INOUT) {
       members[n] = m;
       bytes[n] = member_bytes(m, precision, ngptot, nproma, klev);
       set_bytes += bytes[n++];

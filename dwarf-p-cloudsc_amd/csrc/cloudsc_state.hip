@@ -115,7 +115,7 @@ struct cloudsc_gpu_state {
   cloudsc_impl::KsegEpoch kseg_epoch;   // where the last launch on kseg_ws left its counter and flag stamps
   ParamSet params;                // the state's own parameter set (never shared)
   std::vector<void*> allocs;
-  size_t fbytes[sizeof(cloudsc_fields_t) / sizeof(void*)];   // bytes of each field, cloudsc_fields_t order
+  size_t fbytes[kNumFields];      // bytes of each field, cloudsc_fields_t order
   float place_first_ms = 0.f, place_final_ms = 0.f;           // output write probe before / after the search
   int place_tries = 0, place_moves = 0;
   cloudsc_impl::PlaceCost pcost;                              // the search's cost (both phases)
@@ -123,25 +123,17 @@ struct cloudsc_gpu_state {
 
 namespace {
 
-size_t field_elems(const cloudsc_gpu_state* s, int kind /*0 2d,1 2dh,2 3d,3 1d*/) {
-  const size_t nb = s->nblocks, np = s->nproma, kl = s->klev;
-  switch (kind) {
-    case 0: return nb * kl * np;
-    case 1: return nb * (kl + 1) * np;
-    case 2: return nb * 5 * kl * np;
-    default: return nb * np;
-  }
+size_t field_elems(const cloudsc_gpu_state* s, int kind) {
+  return (size_t)s->nblocks * per_block_elems(kind, s->nproma, s->klev);
 }
-// validated field table: pointer slot and shape kind, in cloudsc_field_id order
+
+// pointer slot and shape kind of a validated field (cloudsc_field_id), from the inventory
 void* const* valid_slot(const cloudsc_gpu_state* s, int id, int* kind) {
-  const cloudsc_fields_t& f = s->f;
-  static const int kinds[CLOUDSC_NVALID] = {0, 0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 2};
-  void* const* slots[CLOUDSC_NVALID] = {
-      &f.plude, &f.pcovptot, &f.prainfrac_toprfz, &f.pfsqlf, &f.pfsqif, &f.pfcqlng, &f.pfcqnng,
-      &f.pfsqrf, &f.pfsqsf, &f.pfcqrng, &f.pfcqsng, &f.pfsqltur, &f.pfsqitur, &f.pfplsl, &f.pfplsn,
-      &f.pfhpsl, &f.pfhpsn, &f.tendency_loc_a, &f.tendency_loc_q, &f.tendency_loc_t, &f.tendency_loc_cld};
-  *kind = kinds[id];
-  return slots[id];
+  int member[CLOUDSC_NVALID];
+#define VALID_MEMBER(n, N, k, d, i) CLOUDSC_IF_VALIDATED_##d(member[CLOUDSC_F_##N] = CLOUDSC_M_##n;)
+  CLOUDSC_FIELDS(VALID_MEMBER)
+  *kind = kFieldTable[member[id]].kind;
+  return (void* const*)&s->f + member[id];
 }
 
 #ifdef CLOUDSC_DEBUG_KNOBS
@@ -448,12 +440,13 @@ int cloudsc_state_create(cloudsc_gpu_state_t** out, int device, int precision, i
   rc = validate_run_args(device, precision, CLOUDSC_VARIANT_KSEG, ngptot, nproma, t->klev);
   if (rc) return rc;
   if (t->klon <= 0) return CLOUDSC_EINVAL;
-  const void* req[] = {t->pt, t->pq, t->tendency_tmp_t, t->tendency_tmp_q, t->tendency_tmp_a,
-                       t->tendency_tmp_cld, t->pvfl, t->pvfi, t->phrsw, t->phrlw, t->pvervel, t->pap,
-                       t->paph, t->plsm, t->ktype, t->plu, t->plude, t->psnde, t->pmfu, t->pmfd, t->pa,
-                       t->pclv, t->psupsat};
-  for (const void* q : req)
-    if (!q) return CLOUDSC_EINVAL;
+  const void* tmpl[kNumFields] = {};   // the template array of each cloudsc_fields_t member (NULL: none, or absent)
+#define TEMPLATE_OF(n) tmpl[CLOUDSC_M_##n] = t->n;
+  CLOUDSC_TEMPLATE_ORDER(TEMPLATE_OF)
+  for (int m = 0; m < kNumFields; m++) {
+    const int dir = kFieldTable[m].dir;
+    if (dir != CLOUDSC_FD_OUT && dir != CLOUDSC_FD_AEROSOL && !tmpl[m]) return CLOUDSC_EINVAL;
+  }
   if (params->laericesed && !t->pre_ice) return CLOUDSC_EINVAL;
   if (params->laericeauto && (!t->picrit_aer || !t->pnice)) return CLOUDSC_EINVAL;
 
@@ -469,98 +462,67 @@ int cloudsc_state_create(cloudsc_gpu_state_t** out, int device, int precision, i
   if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) return fail(CLOUDSC_EHIP);
   if (hipEventCreate(&s->ev0) != hipSuccess || hipEventCreate(&s->ev1) != hipSuccess) return fail(CLOUDSC_EHIP);
 
-  const size_t n2 = field_elems(s, 0) * s->es, n2h = field_elems(s, 1) * s->es;
-  const size_t n3 = field_elems(s, 2) * s->es, n1 = field_elems(s, 3) * s->es;
   const int kl = s->klev;
-  struct In { const void** dst; const void* src; int nlev; size_t bytes; bool is_int; };
-  cloudsc_fields_t& f = s->f;
-  void* plude_dev = nullptr;
-  In ins[] = {
-      {&f.pt, t->pt, kl, n2, false}, {&f.pq, t->pq, kl, n2, false},
-      {&f.tendency_tmp_t, t->tendency_tmp_t, kl, n2, false}, {&f.tendency_tmp_q, t->tendency_tmp_q, kl, n2, false},
-      {&f.tendency_tmp_a, t->tendency_tmp_a, kl, n2, false}, {&f.tendency_tmp_cld, t->tendency_tmp_cld, 5 * kl, n3, false},
-      {&f.pvfl, t->pvfl, kl, n2, false}, {&f.pvfi, t->pvfi, kl, n2, false}, {&f.phrsw, t->phrsw, kl, n2, false},
-      {&f.phrlw, t->phrlw, kl, n2, false}, {&f.pvervel, t->pvervel, kl, n2, false}, {&f.pap, t->pap, kl, n2, false},
-      {&f.paph, t->paph, kl + 1, n2h, false}, {&f.plsm, t->plsm, 1, n1, false},
-      {(const void**)&f.ktype, t->ktype, 1, (size_t)s->nblocks * nproma * sizeof(int), true},
-      {&f.plu, t->plu, kl, n2, false}, {&f.psnde, t->psnde, kl, n2, false}, {&f.pmfu, t->pmfu, kl, n2, false},
-      {&f.pmfd, t->pmfd, kl, n2, false}, {&f.pa, t->pa, kl, n2, false}, {&f.pclv, t->pclv, 5 * kl, n3, false},
-      {&f.psupsat, t->psupsat, kl, n2, false},
-      {&f.plcrit_aer, t->plcrit_aer, kl, n2, false}, {&f.picrit_aer, t->picrit_aer, kl, n2, false},
-      {&f.pre_ice, t->pre_ice, kl, n2, false}, {&f.pccn, t->pccn, kl, n2, false}, {&f.pnice, t->pnice, kl, n2, false},
-      {(const void**)&plude_dev, t->plude, kl, n2, false},
+  void** fp = (void**)&s->f;
+  for (int m = 0; m < kNumFields; m++)
+    s->fbytes[m] = field_elems(s, kFieldTable[m].kind) * (kFieldTable[m].is_int ? sizeof(int) : s->es);
+  // The order of the device allocations is behaviour, and the placement searches get it too: the
+  // template's inputs in member order, the pristine plude copy (member -1) last among them, plude and the outputs
+  int imem[kNumFields + 1], irow[kNumFields + 1], outs[kNumFields], nin = 0, no = 0;
+  size_t ibytes[kNumFields + 1], obytes[kNumFields], in_set = 0, out_set = 0;
+  auto add_input = [&](int member, int row) {   // row: the table row of its shape and template array
+    imem[nin] = member;
+    irow[nin] = row;
+    in_set += ibytes[nin++] = s->fbytes[row];
   };
-  struct Out { void** dst; size_t bytes; };
-  Out outs[] = {{&f.plude, n2}, {&f.tendency_loc_t, n2}, {&f.tendency_loc_q, n2}, {&f.tendency_loc_a, n2},
-                {&f.tendency_loc_cld, n3}, {&f.pcovptot, n2}, {&f.prainfrac_toprfz, n1},
-                {&f.pfsqlf, n2h}, {&f.pfsqif, n2h}, {&f.pfcqnng, n2h}, {&f.pfcqlng, n2h}, {&f.pfsqrf, n2h},
-                {&f.pfsqsf, n2h}, {&f.pfcqrng, n2h}, {&f.pfcqsng, n2h}, {&f.pfsqltur, n2h}, {&f.pfsqitur, n2h},
-                {&f.pfplsl, n2h}, {&f.pfplsn, n2h}, {&f.pfhpsl, n2h}, {&f.pfhpsn, n2h}};
+  for (int m = 0; m < kNumFields; m++) {
+    const int dir = kFieldTable[m].dir;
+    if ((dir == CLOUDSC_FD_IN || dir == CLOUDSC_FD_AEROSOL) && tmpl[m]) add_input(m, m);
+    if (dir == CLOUDSC_FD_INOUT || dir == CLOUDSC_FD_OUT) {
+      outs[no] = m;
+      out_set += obytes[no++] = s->fbytes[m];
+    }
+  }
+  add_input(-1, CLOUDSC_M_plude);
   Arena ar;
   ar.stagger = g_layout_stagger.load();
   if (ar.stagger >= 0) {
     size_t total = 0;
-    for (const In& in : ins)
-      if (in.src) total += arena_span(in.bytes);
-    for (const Out& o : outs) total += arena_span(o.bytes);
+    for (int q = 0; q < nin; q++) total += arena_span(ibytes[q]);
+    for (int q = 0; q < no; q++) total += arena_span(obytes[q]);
     void* base = nullptr;
     if ((rc = dalloc(s, &base, total))) return fail(rc);
     ar.base = (char*)base;
   }
-  std::memset(s->fbytes, 0, sizeof(s->fbytes));
-  auto member = [&](const void* slot) {
-    const ptrdiff_t m = (const void* const*)slot - (const void* const*)&s->f;
-    return m >= 0 && m < (ptrdiff_t)(sizeof(s->fbytes) / sizeof(s->fbytes[0])) ? (int)m : -1;
-  };
-  for (In& in : ins) {
-    if (!in.src) continue;
+  for (int q = 0; q < nin; q++) {
+    const FieldDesc& d = kFieldTable[irow[q]];
     void* p = nullptr;
-    if ((rc = field_alloc(s, ar, &p, in.bytes))) return fail(rc);
-    if ((rc = expand_into(s, p, in.src, in.nlev, in.is_int))) return fail(rc);
-    *in.dst = p;
-    if (member(in.dst) >= 0) s->fbytes[member(in.dst)] = in.bytes;
+    if ((rc = field_alloc(s, ar, &p, ibytes[q]))) return fail(rc);
+    if ((rc = expand_into(s, p, tmpl[irow[q]], (int)per_block_elems(d.kind, 1, kl), d.is_int))) return fail(rc);
+    (imem[q] < 0 ? s->plude_pristine : fp[imem[q]]) = p;
   }
-  s->plude_pristine = plude_dev;
-  for (Out& o : outs) {
-    if ((rc = field_alloc(s, ar, o.dst, o.bytes))) return fail(rc);
-    if (member(o.dst) >= 0) s->fbytes[member(o.dst)] = o.bytes;
-  }
+  for (int q = 0; q < no; q++)
+    if ((rc = field_alloc(s, ar, &fp[outs[q]], obytes[q]))) return fail(rc);
   if (!ar.base && g_place_passes.load() > 0) {   // one allocation per field: search for a fast placement
     // the KSEG workspace the search's launches use (and later KSEG runs)
     const long long wsb = cloudsc_gpu_scratch_bytes(s->precision, CLOUDSC_VARIANT_KSEG, ngptot, nproma, kl);
     if (wsb <= 0) return fail(CLOUDSC_EINVAL);
     if ((rc = dalloc(s, &s->kseg_ws, (size_t)wsb))) return fail(rc);
     if (hipMemsetAsync(s->kseg_ws, 0, 256, s->stream) != hipSuccess) return fail(CLOUDSC_EHIP);
-    constexpr int no = (int)(sizeof(outs) / sizeof(outs[0]));
-    int members[no];
-    size_t bytes[no], out_set = 0, in_set = 0;
-    for (int q = 0; q < no; q++) { members[q] = member(outs[q].dst); bytes[q] = outs[q].bytes; out_set += bytes[q]; }
-    for (const In& in : ins)
-      if (in.src) in_set += in.bytes;
     // no room for two candidate sets and their spacers next to the state: no
     // search (cloudsc_state_placement_report then says NONE)
-    int nin_set = 0;
-    for (const In& in : ins) nin_set += in.src ? 1 : 0;
     const size_t budget = std::max(search_transient_bytes(out_set, no, kPlaceSets),
-                                   search_transient_bytes(in_set, nin_set, kPlaceInputSets));
+                                   search_transient_bytes(in_set, nin, kPlaceInputSets));
     const bool room = search_fits(budget);
     if (room) s->pcost.budget_bytes = (long long)budget;
-    if (room && (rc = place_outputs(s, members, bytes, no))) return fail(rc);
+    if (room && (rc = place_outputs(s, outs, obytes, no))) return fail(rc);
     // then the inputs (contents copied) and the pristine plude copy
-    constexpr int ni = (int)(sizeof(ins) / sizeof(ins[0]));
-    int imem[ni];
-    size_t ibytes[ni];
-    int nin = 0;
-    for (const In& in : ins) {
-      if (!in.src) continue;
-      imem[nin] = in.dst == (const void**)&plude_dev ? -1 : member(in.dst);
-      ibytes[nin++] = in.bytes;
-    }
     if (room && (rc = place_inputs(s, imem, ibytes, nin))) return fail(rc);
   }
-  for (Out& o : outs)
-    if (hipMemsetAsync(*o.dst, 0xff, o.bytes, s->stream) != hipSuccess) return fail(CLOUDSC_EHIP);  // NaN
-  if (hipMemcpyAsync(f.plude, s->plude_pristine, n2, hipMemcpyDeviceToDevice, s->stream) != hipSuccess)
+  for (int q = 0; q < no; q++)   // NaN
+    if (hipMemsetAsync(fp[outs[q]], 0xff, obytes[q], s->stream) != hipSuccess) return fail(CLOUDSC_EHIP);
+  if (hipMemcpyAsync(s->f.plude, s->plude_pristine, s->fbytes[CLOUDSC_M_plude], hipMemcpyDeviceToDevice, s->stream) !=
+      hipSuccess)
     return fail(CLOUDSC_EHIP);
   if (hipStreamSynchronize(s->stream) != hipSuccess) return fail(CLOUDSC_EHIP);
   *out = s;
@@ -653,7 +615,7 @@ int cloudsc_debug_state_relocate_aux(cloudsc_gpu_state_t* s, int which) {
   void** slot = which == 0 ? &s->plude_pristine : which == 1 ? &s->kseg_ws : &s->scratch;
   if (!*slot) return CLOUDSC_EINVAL;
   const size_t bytes =
-      which == 0 ? field_elems(s, 0) * s->es
+      which == 0 ? s->fbytes[CLOUDSC_M_plude]
                  : (size_t)cloudsc_gpu_scratch_bytes(s->precision, which == 1 ? CLOUDSC_VARIANT_KSEG : CLOUDSC_VARIANT_SCC,
                                                      s->ngptot, s->nproma, s->klev);
   HIPCHK(hipSetDevice(s->device));
@@ -680,7 +642,7 @@ int cloudsc_state_fields(const cloudsc_gpu_state_t* s, cloudsc_fields_t* out) {
 int cloudsc_state_reset(cloudsc_gpu_state_t* s) {
   if (!s) return CLOUDSC_EINVAL;
   HIPCHK(hipSetDevice(s->device));
-  HIPCHK(hipMemcpyAsync(s->f.plude, s->plude_pristine, field_elems(s, 0) * s->es, hipMemcpyDeviceToDevice,
+  HIPCHK(hipMemcpyAsync(s->f.plude, s->plude_pristine, s->fbytes[CLOUDSC_M_plude], hipMemcpyDeviceToDevice,
                         s->stream));
   return CLOUDSC_OK;
 }
@@ -876,7 +838,7 @@ int cloudsc_state_validate(cloudsc_gpu_state_t* s, const cloudsc_reference_t* re
   for (int id = 0; id < CLOUDSC_NVALID && e == hipSuccess; id++) {
     int kind;
     void* const* slot = valid_slot(s, id, &kind);
-    const int nlev = kind == 0 ? s->klev : kind == 1 ? s->klev + 1 : kind == 2 ? 5 * s->klev : 1;
+    const int nlev = (int)per_block_elems(kind, 1, s->klev);   // rows per column
     if (!ref->field[id]) { e = hipErrorInvalidValue; break; }
     // on the state's stream, ordered before the kernel that reads it (a null-stream
     // hipMemcpy from pageable memory can still be in flight when it returns)

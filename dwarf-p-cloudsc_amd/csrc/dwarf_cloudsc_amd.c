@@ -353,20 +353,14 @@ static double print_error(const char *name, int ndim, const cloudsc_stats_t *s, 
 }
 
 /* ---- host-memory paths: --transfer (GPU, H2D/D2H per chunk) and --variant cpu ---- */
-/* cloudsc_io input index -> cloudsc_fields_t member index */
-static int input_field_index(int i) {
-  if (i < 16) return i;                 /* pt .. plu */
-  if (i == 16) return 27;               /* plude (INOUT) */
-  if (i < 23) return i - 1;             /* psnde .. psupsat */
-  return i - 1;                         /* aerosols 22..26 */
-}
-/* validated field id -> cloudsc_fields_t member index */
-static const int k_valid_field[CLOUDSC_NVALID] = {27, 32, 33, 34, 35, 37, 36, 38, 39, 40, 41,
-                                                  42, 43, 44, 45, 46, 47, 30, 29, 28, 31};
-/* kinds of the outputs 28..47 */
-static const int k_out_kind[20] = {0, 0, 0, 2, 0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1};
-
-static double print_error(const char *name, int ndim, const cloudsc_stats_t *s, int ngptot);
+/* from the inventory (cloudsc_fields.def): cloudsc_io input index and validated field id ->
+ * cloudsc_fields_t member index; the kind of every output member (-1 for the others) */
+#define INPUT_FIELD(n, N, k, d, i) CLOUDSC_IF_TEMPLATE_##d([CLOUDSC_T_##n] = CLOUDSC_M_##n, )
+#define VALID_FIELD(n, N, k, d, i) CLOUDSC_IF_VALIDATED_##d([CLOUDSC_F_##N] = CLOUDSC_M_##n, )
+#define OUT_KIND(n, N, k, d, i) CLOUDSC_FD_##d == CLOUDSC_FD_OUT ? CLOUDSC_FK_##k : -1,
+static const int k_input_field[CLOUDSC_IO_NIN] = {CLOUDSC_FIELDS(INPUT_FIELD)};
+static const int k_valid_field[CLOUDSC_NVALID] = {CLOUDSC_FIELDS(VALID_FIELD)};
+static const int k_out_kind[CLOUDSC_NFIELDS] = {CLOUDSC_FIELDS(OUT_KIND)};
 
 static int run_host(const options_t *o, const cloudsc_dataset_t *ds) {
   const int cpu = o->variant == VARIANT_CPU;
@@ -390,20 +384,21 @@ static int run_host(const options_t *o, const cloudsc_dataset_t *ds) {
     void *dst = aligned_alloc(4096, (bytes + 4095) & ~(size_t)4095);
     if (!dst) { rc = CLOUDSC_ENOMEM; break; }
     cloudsc_io_expand(src, kind, is_int, ds->klev, ds->klon, o->ngptot, o->nproma, 0, is_int ? 4 : es, dst);
-    fp[input_field_index(i)] = dst;
+    fp[k_input_field[i]] = dst;
     host_bytes += bytes;
-    if (i == 16) {
+    if (i == CLOUDSC_T_plude) {
       plude0 = (double *)malloc(bytes);
       if (!plude0) { rc = CLOUDSC_ENOMEM; break; }
       memcpy(plude0, dst, bytes);
     }
   }
-  for (int j = 0; j < 20 && !rc; j++) {
-    const size_t bytes = (size_t)nb * (size_t)cloudsc_io_elems(k_out_kind[j], ds->klev, o->nproma) * es;
+  for (int m = 0; m < CLOUDSC_NFIELDS && !rc; m++) {
+    if (k_out_kind[m] < 0) continue;
+    const size_t bytes = (size_t)nb * (size_t)cloudsc_io_elems(k_out_kind[m], ds->klev, o->nproma) * es;
     void *dst = aligned_alloc(4096, (bytes + 4095) & ~(size_t)4095);
     if (!dst) { rc = CLOUDSC_ENOMEM; break; }
     memset(dst, 0xff, bytes);            /* NaN: the callee must write every element */
-    fp[28 + j] = dst;
+    fp[m] = dst;
     host_bytes += bytes;
   }
   const size_t plude_bytes = (size_t)nb * ds->klev * o->nproma * es;
@@ -488,7 +483,7 @@ static int run_host(const options_t *o, const cloudsc_dataset_t *ds) {
     fprintf(stderr, "dwarf-cloudsc-amd %s: %s (%s)\n", cpu ? "--variant cpu" : "--transfer", cloudsc_strerror(rc),
             cloudsc_last_hip_error());
   }
-  for (int i = 0; i < 48; i++) free(fp[i]);
+  for (int i = 0; i < CLOUDSC_NFIELDS; i++) free(fp[i]);
   free(plude0);
   free(th_s); free(th_step); free(th_blk); free(th_col); free(th_blk_step); free(th_col_step);
   return rc ? EXIT_FAILURE : (bad ? EXIT_FAILURE : EXIT_SUCCESS);
