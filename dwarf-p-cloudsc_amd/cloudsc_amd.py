@@ -35,6 +35,13 @@ DATA_DIR = os.path.join(REPO, "data", "cloudsc100")   # the reference's data/ ar
 
 NCLV = 5
 FP64, FP32 = 8, 4
+# float fields, double arithmetic: out == float32(fp64_kernel(float64(in))) bit for bit (cloudsc_amd.h)
+MIXED = 12
+
+
+def storage_dtype(precision: int):
+    """Element type of the real fields of a precision code in memory."""
+    return np.float64 if precision == FP64 else np.float32
 VARIANT_SCC, VARIANT_KCACHE, VARIANT_KSEG, VARIANT_SCC_PRIVATE = 1, 2, 3, 4
 
 # ---------------------------------------------------------------------------
@@ -321,7 +328,7 @@ def io_lib():
 
 def make_host_state(ds: Dataset, ngptot: int, nproma: int, precision: int = FP64,
                     col_offset: int = 0) -> HostState:
-    real = np.float64 if precision == FP64 else np.float32
+    real = storage_dtype(precision)
     nb = nblocks_of(ngptot, nproma)
     arrays = {}
     io = io_lib()
@@ -442,6 +449,8 @@ def gpu_lib(path: Optional[str] = None):
         lib.cloudsc_pcie_gbps.argtypes = [C.c_int, C.c_longlong, C.c_int] + [C.POINTER(C.c_double)] * 3
     lib.cloudsc_cpu_run.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Params), C.POINTER(Fields),
                                     C.POINTER(C.c_double)]
+    lib.cloudsc_cpu_run_precision.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Params),
+                                              C.POINTER(Fields), C.POINTER(C.c_double)]
     lib.cloudsc_debug_set_kseg_spin_limit.argtypes = [C.c_longlong]
     lib.cloudsc_debug_set_kseg_schedule.argtypes = [C.c_int, C.c_int]
     lib.cloudsc_debug_host_pipeline_mapping.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -467,22 +476,25 @@ def kseg_spin_limit(limit: int = -1) -> None:
     check(gpu_lib().cloudsc_debug_set_kseg_spin_limit(limit))
 
 
-def cpu_run(ds: "Dataset", ngptot: int, nproma: int = 32, nthreads: int = 0, col_offset: int = 0):
+def cpu_run(ds: "Dataset", ngptot: int, nproma: int = 32, nthreads: int = 0, col_offset: int = 0,
+            precision: int = FP64):
     """The library's CPU variant (cloudsc_cpu_run, BASELINE.json config 1) on a
     host block-layout state expanded from ds.  Returns (HostState, seconds).
-    Explicitly a CPU run -- it is never used in place of a GPU run."""
-    st = make_host_state(ds, ngptot, nproma, FP64, col_offset)
+    Explicitly a CPU run -- it is never used in place of a GPU run.
+    precision: FP64, or MIXED (float arrays, double arithmetic)."""
+    st = make_host_state(ds, ngptot, nproma, precision, col_offset)
     return st, cpu_run_state(ds, st, nthreads)
 
 
 def cpu_run_state(ds: "Dataset", st: "HostState", nthreads: int = 0) -> float:
-    """cloudsc_cpu_run on an already expanded host state (plude is INOUT: the
-    caller restores it between runs).  Returns seconds of the block loop."""
+    """cloudsc_cpu_run_precision on an already expanded host state of precision
+    FP64 or MIXED (plude is INOUT: the caller restores it between runs).
+    Returns seconds of the block loop."""
     p = Params.from_dict(ds.params)
     f = st.fields()
     secs = C.c_double()
-    check(gpu_lib().cloudsc_cpu_run(nthreads, st.ngptot, st.nproma, st.klev, C.byref(p), C.byref(f),
-                                    C.byref(secs)))
+    check(gpu_lib().cloudsc_cpu_run_precision(nthreads, st.precision, st.ngptot, st.nproma, st.klev, C.byref(p),
+                                              C.byref(f), C.byref(secs)))
     return secs.value
 
 
@@ -789,7 +801,7 @@ class DeviceFields:
         self.hip = _hip()
 
     def nbytes(self, name: str) -> int:
-        es = 4 if name == "ktype" or self.precision == FP32 else 8
+        es = 4 if name == "ktype" else np.dtype(storage_dtype(self.precision)).itemsize
         return nblocks_of(self.ngptot, self.nproma) * int(np.prod(field_shape(ALL_FIELDS[name], self.klev,
                                                                              self.nproma))) * es
 
@@ -818,7 +830,7 @@ class DeviceFields:
         """One field in block layout as float64."""
         self.hip.hipSetDevice(self.device)
         self.hip.hipDeviceSynchronize()
-        dt = np.int32 if name == "ktype" else (np.float64 if self.precision == FP64 else np.float32)
+        dt = np.int32 if name == "ktype" else storage_dtype(self.precision)
         nb = nblocks_of(self.ngptot, self.nproma)
         out = np.empty((nb,) + field_shape(ALL_FIELDS[name], self.klev, self.nproma), dtype=dt)
         rc = self.hip.hipMemcpy(out.ctypes.data, getattr(self.f, name), out.nbytes, 2)

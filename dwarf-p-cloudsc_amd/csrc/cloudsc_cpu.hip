@@ -37,8 +37,9 @@ struct HostColumn {
   ColConst<real> cc;
 };
 
-template <typename real, bool AER>
-void run_block(const DevParams<real>& c, const KArgs<real>& A, int b, std::vector<HostColumn<real>>& col) {
+// real: the compute type, S: the fields' element type (float under double = CLOUDSC_MIXED)
+template <typename real, bool AER, typename S>
+void run_block(const DevParams<real>& c, const KArgs<real, S>& A, int b, std::vector<HostColumn<real>>& col) {
   const int nproma = A.nproma, klev = A.klev;
   const int bsize = std::min(nproma, A.ngptot - b * nproma);
   const size_t u1 = (size_t)b * nproma;
@@ -48,7 +49,7 @@ void run_block(const DevParams<real>& c, const KArgs<real>& A, int b, std::vecto
   const int ncldtop0 = c.ncldtop - 1;
   const int l1 = 1 < klev ? 1 : klev - 1;
   for (int jl = 0; jl < bsize; jl++) {
-    const unsigned lo = (unsigned)jl * (unsigned)sizeof(real);
+    const unsigned lo = (unsigned)jl * (unsigned)sizeof(S);
     HostColumn<real>& h = col[jl];
     init_carry<real>(h.cs);
     flux_top(c, A, uh, lo);
@@ -66,7 +67,7 @@ void run_block(const DevParams<real>& c, const KArgs<real>& A, int b, std::vecto
     const int k2 = k + 2 < klev ? k + 2 : klev - 1;
     const int kh2 = k + 2 < klev + 1 ? k + 2 : klev;
     for (int jl = 0; jl < bsize; jl++) {
-      const unsigned lo = (unsigned)jl * (unsigned)sizeof(real);
+      const unsigned lo = (unsigned)jl * (unsigned)sizeof(S);
       HostColumn<real>& h = col[jl];
       LevelIn<real> cur;
       load_level<real, AER>(cur, A, u2, u3, k, klev, nproma, lo);
@@ -92,14 +93,14 @@ void run_block(const DevParams<real>& c, const KArgs<real>& A, int b, std::vecto
       h.nb.plu_n = ldg(A.plu, u2 + (size_t)k2 * nproma, lo);
     }
   }
-  for (int jl = 0; jl < bsize; jl++) stg(A.prainfrac, u1, (unsigned)jl * (unsigned)sizeof(real), col[jl].cs.rainfrac);
+  for (int jl = 0; jl < bsize; jl++) stg(A.prainfrac, u1, (unsigned)jl * (unsigned)sizeof(S), col[jl].cs.rainfrac);
 }
 
-}  // namespace
-
-extern "C" int cloudsc_cpu_run_threads(int nthreads, int ngptot, int nproma, int klev,
-                                       const cloudsc_params_t* params, const cloudsc_fields_t* f, double* seconds,
-                                       double* thread_seconds, int* thread_blocks, int* thread_columns) {
+// the block loop over fields of element type S, computed in double
+template <typename S>
+int cpu_run(int nthreads, int ngptot, int nproma, int klev, const cloudsc_params_t* params,
+            const cloudsc_fields_t* f, double* seconds, double* thread_seconds, int* thread_blocks,
+            int* thread_columns) {
   int rc = cloudsc_impl::check_params(params);
   if (rc) return rc;
   if (!f || !cloudsc_impl::fields_complete(f) || ngptot <= 0 || nproma <= 0 || klev < 2) return CLOUDSC_EINVAL;
@@ -107,7 +108,7 @@ extern "C" int cloudsc_cpu_run_threads(int nthreads, int ngptot, int nproma, int
   if (aer && (!f->pre_ice || !f->picrit_aer || !f->pnice)) return CLOUDSC_EINVAL;
   if (nthreads <= 0 && (thread_seconds || thread_blocks || thread_columns)) return CLOUDSC_EINVAL;
   const DevParams<double> c = fold_params<double>(*params);
-  const KArgs<double> A = make_kargs<double>(f, ngptot, nproma, klev, nullptr);
+  const KArgs<double, S> A = make_kargs<double, S>(f, ngptot, nproma, klev, nullptr);
   const int nblocks = ngptot / nproma + (ngptot % nproma ? 1 : 0);
   if (nthreads <= 0) nthreads = (int)std::max(1u, std::thread::hardware_concurrency());
   const int nreq = nthreads;                 // the caller's per-thread arrays have nreq entries
@@ -153,7 +154,29 @@ extern "C" int cloudsc_cpu_run_threads(int nthreads, int ngptot, int nproma, int
   return rc;
 }
 
+}  // namespace
+
+extern "C" int cloudsc_cpu_run_threads(int nthreads, int ngptot, int nproma, int klev,
+                                       const cloudsc_params_t* params, const cloudsc_fields_t* f, double* seconds,
+                                       double* thread_seconds, int* thread_blocks, int* thread_columns) {
+  return cpu_run<double>(nthreads, ngptot, nproma, klev, params, f, seconds, thread_seconds, thread_blocks,
+                         thread_columns);
+}
+
+extern "C" int cloudsc_cpu_run_precision(int nthreads, int precision, int ngptot, int nproma, int klev,
+                                         const cloudsc_params_t* params, const cloudsc_fields_t* f,
+                                         double* seconds) {
+  if (!cloudsc_impl::precision_computes_double(precision)) return CLOUDSC_EINVAL;   // the host form computes in double
+  switch (cloudsc_impl::precision_storage_bytes(precision)) {
+    case sizeof(double):
+      return cpu_run<double>(nthreads, ngptot, nproma, klev, params, f, seconds, nullptr, nullptr, nullptr);
+    case sizeof(float):
+      return cpu_run<float>(nthreads, ngptot, nproma, klev, params, f, seconds, nullptr, nullptr, nullptr);
+    default: return CLOUDSC_EINVAL;
+  }
+}
+
 extern "C" int cloudsc_cpu_run(int nthreads, int ngptot, int nproma, int klev, const cloudsc_params_t* params,
                                const cloudsc_fields_t* f, double* seconds) {
-  return cloudsc_cpu_run_threads(nthreads, ngptot, nproma, klev, params, f, seconds, nullptr, nullptr, nullptr);
+  return cloudsc_cpu_run_precision(nthreads, CLOUDSC_FP64, ngptot, nproma, klev, params, f, seconds);
 }

@@ -146,9 +146,9 @@ namespace {
 
 // the launch's parameter block, as a constant-address-space pointer (scalar
 // loads), typed with the kernel's choice of single-precision exp/pow forms
-template <typename real, bool FAST>
-__device__ __forceinline__ cptr<DevParamsT<real, FAST>> params_of(cptr<KArgs<real>> ka) {
-  return (cptr<DevParamsT<real, FAST>>)((const KArgs<real>*)ka)->par;
+template <typename real, bool FAST, typename S>
+__device__ __forceinline__ cptr<DevParamsT<real, FAST>> params_of(cptr<KArgs<real, S>> ka) {
+  return (cptr<DevParamsT<real, FAST>>)((const KArgs<real, S>*)ka)->par;
 }
 
 }  // namespace
@@ -171,6 +171,24 @@ __global__ void __launch_bounds__(256, WAVES) kseg_entry(const KArgs<real> a, co
   libm_tables_to_lds<real>();
   const cptr<KArgs<real>> ka = (cptr<KArgs<real>>)__builtin_amdgcn_kernarg_segment_ptr();
   cloudsc_kcache_persistent_body<real, PF, AER, LDSC>(ka, params_of<real, FAST>(ka), pa);
+}
+// CLOUDSC_MIXED: the fp64 physics on float fields (KArgs<double, float>), the
+// fp64 configuration, parameter block and workspace.  Entry points of their
+// own, so the fp64 and fp32 kernels keep their names and their code.
+template <int WAVES, int PF, bool AER, bool LDSC>
+__global__ void __launch_bounds__(256, WAVES) kcache_mixed_entry(const KArgs<double, float> a) {
+  (void)a;
+  libm_tables_to_lds<double>();
+  const cptr<KArgs<double, float>> ka = (cptr<KArgs<double, float>>)__builtin_amdgcn_kernarg_segment_ptr();
+  cloudsc_kcache_body<double, PF, AER, LDSC>(ka, params_of<double, false>(ka));
+}
+template <int WAVES, int PF, bool AER, bool LDSC>
+__global__ void __launch_bounds__(256, WAVES) kseg_mixed_entry(const KArgs<double, float> a,
+                                                               const PersistArgs<double> pa) {
+  (void)a;
+  libm_tables_to_lds<double>();
+  const cptr<KArgs<double, float>> ka = (cptr<KArgs<double, float>>)__builtin_amdgcn_kernarg_segment_ptr();
+  cloudsc_kcache_persistent_body<double, PF, AER, LDSC>(ka, params_of<double, false>(ka), pa);
 }
 template <typename real, bool AER, bool FAST = false>
 __global__ void __launch_bounds__(256) scc_entry(const KArgs<real> a, const SccScratch<real> s) {
@@ -238,13 +256,26 @@ void launch_physics(void (*kern)(Args...), dim3 grid, dim3 block, size_t lds, hi
   else hipLaunchKernelGGL(kern, grid, block, lds, st, args...);
 }
 
-template <typename real, bool AER, bool FAST>
-int launch_kcache(hipStream_t st, const KArgs<real>& a, int nblocks, int nproma, const LaunchEvents* ev) {
+// the k-caching kernels of a (compute, storage) pair: the plain entries when
+// the two are one type, the mixed entries otherwise
+template <typename real, typename S, int WAVES, int PF, bool AER, bool LDSC, bool FAST>
+constexpr auto kcache_kernel() {
+  if constexpr (std::is_same<real, S>::value) return kcache_entry<real, WAVES, PF, AER, LDSC, FAST>;
+  else return kcache_mixed_entry<WAVES, PF, AER, LDSC>;
+}
+template <typename real, typename S, int WAVES, int PF, bool AER, bool LDSC, bool FAST>
+constexpr auto kseg_kernel() {
+  if constexpr (std::is_same<real, S>::value) return kseg_entry<real, WAVES, PF, AER, LDSC, FAST>;
+  else return kseg_mixed_entry<WAVES, PF, AER, LDSC>;
+}
+
+template <typename real, bool AER, bool FAST, typename S>
+int launch_kcache(hipStream_t st, const KArgs<real, S>& a, int nblocks, int nproma, const LaunchEvents* ev) {
 #ifdef CLOUDSC_DEBUG_KNOBS
   switch (env_int("CLOUDSC_KCACHE_CFG", DefaultCfg<real>::code)) {
 #define X(code, w, pf, ldsc)                                                                                 \
   case code:                                                                                                 \
-    launch_physics(kcache_entry<real, w, pf, AER, ldsc, FAST>, dim3(nblocks), dim3(nproma),                 \
+    launch_physics(kcache_kernel<real, S, w, pf, AER, ldsc, FAST>(), dim3(nblocks), dim3(nproma),            \
                    ldsc ? carry_lds_bytes<real>(nproma) : 0, st, ev, a);                                     \
     return CLOUDSC_OK;
     CLOUDSC_FOR_EACH_CFG(X)
@@ -252,8 +283,8 @@ int launch_kcache(hipStream_t st, const KArgs<real>& a, int nblocks, int nproma,
     default: return CLOUDSC_EINVAL;
   }
 #else
-  launch_physics(kcache_entry<real, DefaultCfg<real>::waves, DefaultCfg<real>::pf, AER, false, FAST>, dim3(nblocks),
-                 dim3(nproma), 0, st, ev, a);
+  launch_physics(kcache_kernel<real, S, DefaultCfg<real>::waves, DefaultCfg<real>::pf, AER, false, FAST>(),
+                 dim3(nblocks), dim3(nproma), 0, st, ev, a);
   return CLOUDSC_OK;
 #endif
 }
@@ -341,11 +372,11 @@ __global__ void __launch_bounds__(256) kseg_prepare_kernel(unsigned* ws, int nfl
 
 namespace {
 
-template <typename real, int WAVES, int PF, bool AER, bool LDSC, bool FAST>
-int launch_kseg_cfg(hipStream_t st, const KArgs<real>& a, const PersistArgs<real>& pa, int nproma, int nitems,
+template <typename real, int WAVES, int PF, bool AER, bool LDSC, bool FAST, typename S>
+int launch_kseg_cfg(hipStream_t st, const KArgs<real, S>& a, const PersistArgs<real>& pa, int nproma, int nitems,
                     int* grid_out, const LaunchEvents* ev) {
   const int nseg = pa.nseg;
-  auto kern = kseg_entry<real, WAVES, PF, AER, LDSC, FAST>;
+  auto kern = kseg_kernel<real, S, WAVES, PF, AER, LDSC, FAST>();
   const int wg = kseg_wg(nproma);
   const size_t lds = LDSC ? carry_lds_bytes<real>(wg) : 0;
   // Waves per SIMD: as many as fit, but no more than whole rounds of the work
@@ -388,8 +419,8 @@ int launch_kseg_cfg(hipStream_t st, const KArgs<real>& a, const PersistArgs<real
   return CLOUDSC_OK;
 }
 
-template <typename real, bool AER, bool FAST>
-int launch_kseg(hipStream_t st, const KArgs<real>& a, const PersistArgs<real>& pa, int nproma, int nitems,
+template <typename real, bool AER, bool FAST, typename S>
+int launch_kseg(hipStream_t st, const KArgs<real, S>& a, const PersistArgs<real>& pa, int nproma, int nitems,
                 int* grid_out, const LaunchEvents* ev) {
 #ifdef CLOUDSC_DEBUG_KNOBS
   switch (env_int("CLOUDSC_KCACHE_CFG", DefaultCfg<real>::code)) {
@@ -410,20 +441,26 @@ int launch_kseg(hipStream_t st, const KArgs<real>& a, const PersistArgs<real>& p
 // compile instead of twelve, for the per-phase ablation builds of
 // tools/ablation.sh; every other combination returns CLOUDSC_EINVAL.
 #ifdef CLOUDSC_ONLY_KSEG
-#define CLOUDSC_KEEP_KERNEL(real_, kseg_, aer_) (sizeof(real_) == CLOUDSC_ONLY_KSEG && (kseg_) && !(aer_))
+#define CLOUDSC_KEEP_KERNEL(real_, kseg_, aer_) \
+  (sizeof(real_) == CLOUDSC_ONLY_KSEG && sizeof(ST) == CLOUDSC_ONLY_KSEG && (kseg_) && !(aer_))
 #else
 #define CLOUDSC_KEEP_KERNEL(real_, kseg_, aer_) true
 #endif
 
-template <typename real, bool FAST>
+// real: the compute type; ST: the fields' element type (float under a double
+// `real` is CLOUDSC_MIXED: the k-caching kernels only)
+template <typename real, bool FAST, typename ST = real>
 int launch_v(hipStream_t st, int variant, const cloudsc_fields_t* f, int ngptot, int nproma, int klev,
              void* scratch, const void* plude_in, const ParamSet& ps, KsegEpoch* ep, const LaunchEvents* ev) {
 #ifdef CLOUDSC_ONLY_KSEG
-  if (variant != CLOUDSC_VARIANT_KSEG || ps.aer || sizeof(real) != CLOUDSC_ONLY_KSEG) return CLOUDSC_EINVAL;
+  if (variant != CLOUDSC_VARIANT_KSEG || ps.aer || sizeof(real) != CLOUDSC_ONLY_KSEG || sizeof(ST) != sizeof(real))
+    return CLOUDSC_EINVAL;
 #endif
-  KArgs<real> a = make_kargs<real>(
+  constexpr bool kPlain = std::is_same<real, ST>::value;
+  if (!kPlain && variant != CLOUDSC_VARIANT_KCACHE && variant != CLOUDSC_VARIANT_KSEG) return CLOUDSC_EINVAL;
+  KArgs<real, ST> a = make_kargs<real, ST>(
       f, ngptot, nproma, klev, (const DevParams<real>*)((const char*)ps.dev + (sizeof(real) == 8 ? 0 : kSpOffset)));
-  if (plude_in) a.plude_in = (const real*)plude_in;
+  if (plude_in) a.plude_in = (const ST*)plude_in;
   const int nblocks = ngptot / nproma + (ngptot % nproma ? 1 : 0);
   const bool aer = ps.aer;
   if (aer && (!f->pre_ice || !f->picrit_aer || !f->pnice)) return CLOUDSC_EINVAL;
@@ -501,13 +538,13 @@ int launch_v(hipStream_t st, int variant, const cloudsc_fields_t* f, int ngptot,
     }
   } else if (variant == CLOUDSC_VARIANT_SCC_PRIVATE) {
     if (klev > kPrivKlev) return CLOUDSC_EINVAL;    // the private arrays are sized at compile time
-    if constexpr (CLOUDSC_KEEP_KERNEL(real, false, false)) {
+    if constexpr (kPlain && CLOUDSC_KEEP_KERNEL(real, false, false)) {
       if (aer) launch_physics(scc_private_entry<real, true, FAST>, dim3(nblocks), dim3(nproma), 0, st, ev, a);
       else launch_physics(scc_private_entry<real, false, FAST>, dim3(nblocks), dim3(nproma), 0, st, ev, a);
     }
   } else {
     if (!scratch) return CLOUDSC_EINVAL;
-    if constexpr (CLOUDSC_KEEP_KERNEL(real, false, false)) {
+    if constexpr (kPlain && CLOUDSC_KEEP_KERNEL(real, false, false)) {
       SccScratch<real> s = scc_scratch_carve<real>((char*)scratch, nblocks, nproma, klev);
       if (aer) launch_physics(scc_entry<real, true, FAST>, dim3(nblocks), dim3(nproma), 0, st, ev, a, s);
       else launch_physics(scc_entry<real, false, FAST>, dim3(nblocks), dim3(nproma), 0, st, ev, a, s);
@@ -528,6 +565,22 @@ int launch(hipStream_t st, int variant, bool exact_libm, const cloudsc_fields_t*
   }
   (void)exact_libm;
   return launch_v<real, false>(st, variant, f, ngptot, nproma, klev, scratch, plude_in, ps, ep, ev);
+}
+
+// The launch of a precision code.  CLOUDSC_MIXED is the fp64 launch (exp/pow,
+// parameter mirror, configuration, workspace) over float fields.
+int launch_precision(int precision, hipStream_t st, int variant, bool exact_libm, const cloudsc_fields_t* f,
+                     int ngptot, int nproma, int klev, void* scratch, const void* plude_in, const ParamSet& ps,
+                     KsegEpoch* ep, const LaunchEvents* ev) {
+  switch (precision) {
+    case CLOUDSC_FP64:
+      return launch<double>(st, variant, exact_libm, f, ngptot, nproma, klev, scratch, plude_in, ps, ep, ev);
+    case CLOUDSC_FP32:
+      return launch<float>(st, variant, exact_libm, f, ngptot, nproma, klev, scratch, plude_in, ps, ep, ev);
+    case CLOUDSC_MIXED:
+      return launch_v<double, false, float>(st, variant, f, ngptot, nproma, klev, scratch, plude_in, ps, ep, ev);
+    default: return CLOUDSC_EINVAL;
+  }
 }
 
 }  // namespace
@@ -564,14 +617,14 @@ long long cloudsc_gpu_scratch_bytes(int precision, int variant, int ngptot, int 
   if (ngptot <= 0 || nproma <= 0 || klev < 2) return -1;
   variant = variant_kind(variant);
   if (variant == CLOUDSC_VARIANT_KCACHE || variant == CLOUDSC_VARIANT_SCC_PRIVATE) return 0;
-  if (precision != CLOUDSC_FP64 && precision != CLOUDSC_FP32) return -1;
+  if (!precision_storage_bytes(precision)) return -1;
   const int nblocks = ngptot / nproma + (ngptot % nproma ? 1 : 0);
+  // workspaces hold values of the compute type (the KSEG carried state, the SCC temporaries)
+  const bool dbl = precision_computes_double(precision);
   if (variant == CLOUDSC_VARIANT_KSEG)
-    return precision == CLOUDSC_FP64 ? kseg_scratch_bytes<double>(nblocks, nproma)
-                                     : kseg_scratch_bytes<float>(nblocks, nproma);
-  if (variant != CLOUDSC_VARIANT_SCC) return -1;
-  return precision == CLOUDSC_FP64 ? scc_scratch_bytes<double>(nblocks, nproma, klev)
-                                   : scc_scratch_bytes<float>(nblocks, nproma, klev);
+    return dbl ? kseg_scratch_bytes<double>(nblocks, nproma) : kseg_scratch_bytes<float>(nblocks, nproma);
+  if (variant != CLOUDSC_VARIANT_SCC || precision == CLOUDSC_MIXED) return -1;
+  return dbl ? scc_scratch_bytes<double>(nblocks, nproma, klev) : scc_scratch_bytes<float>(nblocks, nproma, klev);
 }
 
 }  // extern "C"
@@ -583,9 +636,12 @@ int validate_run_args(int device, int precision, int variant, int ngptot, int np
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return CLOUDSC_ENODEV;
   if (device < 0 || device >= n || device >= kMaxDevices) return CLOUDSC_ENODEV;
-  if (precision != CLOUDSC_FP64 && precision != CLOUDSC_FP32) return CLOUDSC_EINVAL;
+  if (!precision_storage_bytes(precision)) return CLOUDSC_EINVAL;
   if (variant != CLOUDSC_VARIANT_KCACHE && variant != CLOUDSC_VARIANT_SCC && variant != CLOUDSC_VARIANT_KSEG &&
       variant != CLOUDSC_VARIANT_SCC_PRIVATE)
+    return CLOUDSC_EINVAL;
+  // mixed precision exists for the k-caching kernels only
+  if (precision == CLOUDSC_MIXED && variant != CLOUDSC_VARIANT_KCACHE && variant != CLOUDSC_VARIANT_KSEG)
     return CLOUDSC_EINVAL;
   // KCACHE and SCC run one workgroup of nproma threads per block; KSEG runs
   // 64-column sub-blocks of any block width
@@ -610,9 +666,7 @@ int gpu_run_impl(int device, void* stream, int precision, int variant, int ngpto
   if (!f || !fields_complete(f)) return CLOUDSC_EINVAL;
   HIPCHK(hipSetDevice(device));
   hipStream_t st = (hipStream_t)stream;
-  return precision == CLOUDSC_FP64
-             ? launch<double>(st, variant, exact_libm, f, ngptot, nproma, klev, scratch, plude_in, *ps, ep, lev)
-             : launch<float>(st, variant, exact_libm, f, ngptot, nproma, klev, scratch, plude_in, *ps, ep, lev);
+  return launch_precision(precision, st, variant, exact_libm, f, ngptot, nproma, klev, scratch, plude_in, *ps, ep, lev);
 }
 
 int kseg_clock(int device, void* stream, void* scratch, bool reset, double* ghz, double* seconds) {

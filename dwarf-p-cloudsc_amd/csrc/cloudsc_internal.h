@@ -28,6 +28,19 @@ constexpr int count_fields(int kind, int dirs) {
   return n;
 }
 
+// What a precision code means, in one place: the bytes of a real field element
+// in memory (0: not a precision code) and the type the physics computes in.
+// CLOUDSC_MIXED stores float and computes double.
+inline size_t precision_storage_bytes(int precision) {
+  switch (precision) {
+    case CLOUDSC_FP64: return sizeof(double);
+    case CLOUDSC_FP32:
+    case CLOUDSC_MIXED: return sizeof(float);
+    default: return 0;
+  }
+}
+inline bool precision_computes_double(int precision) { return precision != CLOUDSC_FP32; }
+
 inline size_t per_block_elems(int kind, int nproma, int klev) {
   switch (kind) {
     case CLOUDSC_FK_LEVEL: return (size_t)klev * nproma;

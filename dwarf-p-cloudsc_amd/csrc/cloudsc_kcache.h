@@ -31,16 +31,22 @@
 
 namespace cloudsc {
 
-template <typename real>
+// `real` is the type the physics computes in, `store` the element type of the
+// fields in memory.  They differ only for CLOUDSC_MIXED (double arithmetic on
+// float fields): a load widens (exact), a store narrows with one conversion
+// (round to nearest even, gradual underflow), and everything between --
+// LevelIn, Neighbors, CarryState, the parameter block, the KSEG workspace --
+// is `real`.  The access helpers below are typed by the pointer they are given.
+template <typename real, typename store = real>
 struct KArgs {
-  const real *pt, *pq, *ttt, *ttq, *tta, *ttcld, *pvfl, *pvfi, *phrsw, *phrlw, *pvervel;
-  const real *pap, *paph, *plsm;
+  const store *pt, *pq, *ttt, *ttq, *tta, *ttcld, *pvfl, *pvfi, *phrsw, *phrlw, *pvervel;
+  const store *pap, *paph, *plsm;
   const int *ktype;
-  const real *plu, *psnde, *pmfu, *pmfd, *pa, *pclv, *psupsat, *picrit_aer, *pre_ice, *pnice;
-  const real *plude_in;   // plude as read: == plude (in place, the C ABI) or a pristine copy (state runs)
-  real *plude, *tlt, *tlq, *tla, *tlcld, *pcovptot, *prainfrac;
-  real *pfsqlf, *pfsqif, *pfcqnng, *pfcqlng, *pfsqrf, *pfsqsf, *pfcqrng, *pfcqsng;
-  real *pfsqltur, *pfsqitur, *pfplsl, *pfplsn, *pfhpsl, *pfhpsn;
+  const store *plu, *psnde, *pmfu, *pmfd, *pa, *pclv, *psupsat, *picrit_aer, *pre_ice, *pnice;
+  const store *plude_in;   // plude as read: == plude (in place, the C ABI) or a pristine copy (state runs)
+  store *plude, *tlt, *tlq, *tla, *tlcld, *pcovptot, *prainfrac;
+  store *pfsqlf, *pfsqif, *pfcqnng, *pfcqlng, *pfsqrf, *pfsqsf, *pfcqrng, *pfcqsng;
+  store *pfsqltur, *pfsqitur, *pfplsl, *pfplsn, *pfhpsl, *pfhpsn;
   const DevParams<real>* par;   // the launch's parameter set (device memory, read with scalar loads)
   int ngptot, nproma, klev;
 };
@@ -118,15 +124,22 @@ CLOUDSC_HD void stg_u(T* ubase, size_t uidx, unsigned lane_bytes, typename std::
   stg(ubase, uidx, lane_bytes, v);
 #endif
 }
-// species planes: the opaque-pointer form in fp32, the plain one in fp64
-template <typename T>
+// species planes: the opaque-pointer form in fp32, the plain one in fp64.
+// Mixed (float fields, double arithmetic) has fp32's addresses and fp64's
+// VALU load; which form it takes is CLOUDSC_MIXED_SP_OPAQUE.
+#ifndef CLOUDSC_MIXED_SP_OPAQUE
+#define CLOUDSC_MIXED_SP_OPAQUE 1
+#endif
+template <typename real, typename store>
+constexpr bool kSpOpaque = sizeof(store) == 4 && (sizeof(real) == 4 || CLOUDSC_MIXED_SP_OPAQUE);
+template <bool OPAQUE, typename T>
 CLOUDSC_HD T ldg1_sp(const T* ubase, size_t uidx, unsigned lane_bytes) {
-  if constexpr (sizeof(T) == 4) return ldg1_u(ubase, uidx, lane_bytes);
+  if constexpr (OPAQUE) return ldg1_u(ubase, uidx, lane_bytes);
   else return ldg1(ubase, uidx, lane_bytes);
 }
-template <typename T>
+template <bool OPAQUE, typename T>
 CLOUDSC_HD void stg_sp(T* ubase, size_t uidx, unsigned lane_bytes, typename std::common_type<T>::type v) {
-  if constexpr (sizeof(T) == 4) stg_u(ubase, uidx, lane_bytes, v);
+  if constexpr (OPAQUE) stg_u(ubase, uidx, lane_bytes, v);
   else stg(ubase, uidx, lane_bytes, v);
 }
 
@@ -146,8 +159,8 @@ struct EarlyIn {
   real pt, pq, ttt, ttq, tta, pa, pap;
   real pclv[4], ttcld[4];
 };
-template <typename real>
-CLOUDSC_HD void load_early(EarlyIn<real>& E, const KArgs<real>& A, size_t u2, size_t u3, int k, int klev,
+template <typename real, typename S>
+CLOUDSC_HD void load_early(EarlyIn<real>& E, const KArgs<real, S>& A, size_t u2, size_t u3, int k, int klev,
                            int nproma, unsigned lo) {
   const size_t i = u2 + (size_t)k * nproma;
   E.pt = ldg1(A.pt, i, lo); E.pq = ldg1(A.pq, i, lo); E.ttt = ldg1(A.ttt, i, lo); E.ttq = ldg1(A.ttq, i, lo);
@@ -155,12 +168,12 @@ CLOUDSC_HD void load_early(EarlyIn<real>& E, const KArgs<real>& A, size_t u2, si
 #pragma unroll
   for (int m = 0; m < 4; m++) {
     const size_t j = u3 + ((size_t)m * klev + k) * nproma;
-    E.pclv[m] = ldg1_sp(A.pclv, j, lo);
-    E.ttcld[m] = ldg1_sp(A.ttcld, j, lo);
+    E.pclv[m] = ldg1_sp<kSpOpaque<real, S>>(A.pclv, j, lo);
+    E.ttcld[m] = ldg1_sp<kSpOpaque<real, S>>(A.ttcld, j, lo);
   }
 }
-template <typename real, bool AER>
-CLOUDSC_HD void load_late(LevelIn<real>& L, const KArgs<real>& A, size_t u2, int k, int nproma, unsigned lo) {
+template <typename real, bool AER, typename S>
+CLOUDSC_HD void load_late(LevelIn<real>& L, const KArgs<real, S>& A, size_t u2, int k, int nproma, unsigned lo) {
   const size_t i = u2 + (size_t)k * nproma;
   L.plude = ldg1(A.plude_in, i, lo); L.pvfl = ldg1(A.pvfl, i, lo); L.pvfi = ldg1(A.pvfi, i, lo);
   L.phrsw = ldg1(A.phrsw, i, lo); L.phrlw = ldg1(A.phrlw, i, lo); L.pvervel = ldg1(A.pvervel, i, lo);
@@ -262,8 +275,8 @@ struct PhysOut {
 // All loads of a level are unconditional (the physics-only fields are read at
 // every level): branches around memory operations make hipcc's vmcnt
 // bookkeeping fall back to vmcnt(0), which drains the software pipeline.
-template <typename real, bool AER>
-CLOUDSC_HD void load_level(LevelIn<real>& L, const KArgs<real>& A, size_t u2, size_t u3, int k,
+template <typename real, bool AER, typename S>
+CLOUDSC_HD void load_level(LevelIn<real>& L, const KArgs<real, S>& A, size_t u2, size_t u3, int k,
                                            int klev, int nproma, unsigned lo) {
   const size_t i = u2 + (size_t)k * nproma;
   L.pt = ldg1(A.pt, i, lo); L.pq = ldg1(A.pq, i, lo); L.ttt = ldg1(A.ttt, i, lo); L.ttq = ldg1(A.ttq, i, lo);
@@ -272,8 +285,8 @@ CLOUDSC_HD void load_level(LevelIn<real>& L, const KArgs<real>& A, size_t u2, si
 #pragma unroll
   for (int m = 0; m < 4; m++) {
     const size_t j = u3 + ((size_t)m * klev + k) * nproma;
-    L.pclv[m] = ldg1_sp(A.pclv, j, lo);
-    L.ttcld[m] = ldg1_sp(A.ttcld, j, lo);
+    L.pclv[m] = ldg1_sp<kSpOpaque<real, S>>(A.pclv, j, lo);
+    L.ttcld[m] = ldg1_sp<kSpOpaque<real, S>>(A.ttcld, j, lo);
   }
   L.phrsw = ldg1(A.phrsw, i, lo); L.phrlw = ldg1(A.phrlw, i, lo); L.pvervel = ldg1(A.pvervel, i, lo);
   L.psnde = ldg1(A.psnde, i, lo); L.psupsat = ldg1(A.psupsat, i, lo);
@@ -1040,8 +1053,8 @@ CLOUDSC_HD void physics_level(const P& c, const int k, const int klev,
 }
 
 // ===== 8. flux diagnostics of one level (cloudsc_c.c:2521-2582), written at half level k+1 =====
-template <typename real, typename P, typename CS>
-CLOUDSC_HD void flux_level(const P& c, const KArgs<real>& A, size_t h, unsigned lo,
+template <typename real, typename P, typename CS, typename S>
+CLOUDSC_HD void flux_level(const P& c, const KArgs<real, S>& A, size_t h, unsigned lo,
                                            const LevelIn<real>& in, const LevelState<real>& ls,
                                            const PhysOut<real>& po, real paph_k, real paph_n,
                                            CS& cs) {
@@ -1072,8 +1085,8 @@ CLOUDSC_HD void flux_level(const P& c, const KArgs<real>& A, size_t h, unsigned 
 }
 
 // level-0 half-level outputs (cloudsc_c.c:2523-2543, 2578-2579)
-template <typename real, typename P>
-CLOUDSC_HD void flux_top(const P& c, const KArgs<real>& A, size_t h0, unsigned lo) {
+template <typename real, typename P, typename S>
+CLOUDSC_HD void flux_top(const P& c, const KArgs<real, S>& A, size_t h0, unsigned lo) {
   stg(A.pfsqlf, h0, lo, R(0.0)); stg(A.pfsqif, h0, lo, R(0.0)); stg(A.pfsqrf, h0, lo, R(0.0));
   stg(A.pfsqsf, h0, lo, R(0.0)); stg(A.pfcqlng, h0, lo, R(0.0)); stg(A.pfcqnng, h0, lo, R(0.0));
   stg(A.pfcqrng, h0, lo, R(0.0)); stg(A.pfcqsng, h0, lo, R(0.0));
@@ -1083,12 +1096,12 @@ CLOUDSC_HD void flux_top(const P& c, const KArgs<real>& A, size_t h0, unsigned l
   stg(A.pfhpsl, h0, lo, -c.rlvtt * plsl); stg(A.pfhpsn, h0, lo, -c.rlstt * plsn);
 }
 
-template <typename real, typename P>
-CLOUDSC_HD ColConst<real> column_constants(const P& c, const KArgs<real>& A,
+template <typename real, typename P, typename S>
+CLOUDSC_HD ColConst<real> column_constants(const P& c, const KArgs<real, S>& A,
                                                            size_t u1, size_t uh, unsigned lo) {
   ColConst<real> cc;
   const real plsm = ldg(A.plsm, u1, lo);
-  cc.ktype = ldg(A.ktype, u1, lo * (unsigned)(sizeof(int)) / (unsigned)sizeof(real));
+  cc.ktype = ldg(A.ktype, u1, lo * (unsigned)(sizeof(int)) / (unsigned)sizeof(S));
   cc.paph_sfc = ldg(A.paph, uh + (size_t)A.klev * A.nproma, lo);
   const bool land = plsm > R(0.5);
   cc.kk_const = land ? pval(c, c.rcl_kk_cloud_num_land) : pval(c, c.rcl_kk_cloud_num_sea);
@@ -1097,8 +1110,8 @@ CLOUDSC_HD ColConst<real> column_constants(const P& c, const KArgs<real>& A,
   return cc;
 }
 
-template <typename real>
-CLOUDSC_HD void store_level(const KArgs<real>& A, size_t u2, size_t u3, int k, int klev,
+template <typename real, typename S>
+CLOUDSC_HD void store_level(const KArgs<real, S>& A, size_t u2, size_t u3, int k, int klev,
                                             int nproma, unsigned lo, bool physics, const LevelState<real>& ls,
                                             const PhysOut<real>& po) {
   const size_t i = u2 + (size_t)k * nproma;
@@ -1108,8 +1121,9 @@ CLOUDSC_HD void store_level(const KArgs<real>& A, size_t u2, size_t u3, int k, i
   stg(A.pcovptot, i, lo, po.zcovptot_out);
   stg(A.plude, i, lo, po.plude_k);   // INOUT: rewritten unchanged where not rescaled (no branch on a store)
 #pragma unroll
-  for (int m = 0; m < 4; m++) stg_sp(A.tlcld, u3 + ((size_t)m * klev + k) * nproma, lo, po.ctend[m]);
-  stg_sp(A.tlcld, u3 + ((size_t)4 * klev + k) * nproma, lo, R(0.0));
+  for (int m = 0; m < 4; m++)
+    stg_sp<kSpOpaque<real, S>>(A.tlcld, u3 + ((size_t)m * klev + k) * nproma, lo, po.ctend[m]);
+  stg_sp<kSpOpaque<real, S>>(A.tlcld, u3 + ((size_t)4 * klev + k) * nproma, lo, R(0.0));
 }
 
 template <typename real, typename CS>
@@ -1139,8 +1153,8 @@ __device__ __forceinline__ const auto& params_here(const PV& pv, cptr<PT> cpar) 
 // kcache_levels runs levels [lev0, lev1) of block b for one (active) lane with
 // the carried state `cs`; the plain kernel runs [0, klev) in one go, the
 // persistent kernel (below) runs a column in level segments.
-template <typename real, int PF, bool AER, typename PT, typename CS>
-__device__ __forceinline__ void kcache_levels(cptr<KArgs<real>> ka, cptr<PT> cpar, int b,
+template <typename real, int PF, bool AER, typename S, typename PT, typename CS>
+__device__ __forceinline__ void kcache_levels(cptr<KArgs<real, S>> ka, cptr<PT> cpar, int b,
                                               unsigned lo0, int lev0, int lev1, CS& cs) {
   if (lev0 >= lev1) return;
   const unsigned lo = lo0;                         // empty segment: no loads at lev0 (may be == klev)
@@ -1152,7 +1166,7 @@ __device__ __forceinline__ void kcache_levels(cptr<KArgs<real>> ka, cptr<PT> cpa
   // of level k (the physics' mid hook), the rest at the top of level k+1;
   // 4 = all inputs of level k+1 issued in the middle of level k
   constexpr bool PFX = PF == 1, NBR = PF == 2, PFM = PF == 3, PFA = PF == 4;
-  const KArgs<real>& A0 = *(const KArgs<real>*)ka;
+  const KArgs<real, S>& A0 = *(const KArgs<real, S>*)ka;
   const int nproma = A0.nproma, klev = A0.klev;
   const size_t u1 = (size_t)b * nproma;                            // [nblocks][nproma]
   const size_t u2 = (size_t)b * klev * nproma;                     // [nblocks][klev][nproma]
@@ -1166,7 +1180,7 @@ __device__ __forceinline__ void kcache_levels(cptr<KArgs<real>> ka, cptr<PT> cpa
   int ncldtop0;
   {
     CLOUDSC_PARAMS_HERE;
-    const KArgs<real>& A = A0;
+    const KArgs<real, S>& A = A0;
     ncldtop0 = c.ncldtop - 1;
     cc = column_constants(c, A, u1, uh, lo);
     const int l1 = lev0 + 1 < klev ? lev0 + 1 : klev - 1;
@@ -1220,7 +1234,7 @@ __device__ __forceinline__ void kcache_levels(cptr<KArgs<real>> ka, cptr<PT> cpa
     // ---- issue the loads of the next levels (software pipelining) ----
     real paph_nn, pmfu_nn, pmfd_nn, plu_nn;
     {
-      const KArgs<real>& A = *(const KArgs<real>*)launder_uniform(ka);
+      const KArgs<real, S>& A = *(const KArgs<real, S>*)launder_uniform(ka);
       // indices clamped instead of branched: the last levels re-read valid data
       const int k1 = k + 1 < klev ? k + 1 : klev - 1;
       const int k2 = k + 2 < klev ? k + 2 : klev - 1;
@@ -1264,10 +1278,10 @@ __device__ __forceinline__ void kcache_levels(cptr<KArgs<real>> ka, cptr<PT> cpa
         if (PFM || PFA) {
           const int k1 = k + 1 < klev ? k + 1 : klev - 1;
           if (PFM)
-            load_early<real>(nxt_e, *(const KArgs<real>*)launder_uniform(ka), u2, u3, k1, klev, nproma,
+            load_early<real>(nxt_e, *(const KArgs<real, S>*)launder_uniform(ka), u2, u3, k1, klev, nproma,
                              launder_vgpr(lo0));
           else
-            load_level<real, AER>(nxt, *(const KArgs<real>*)launder_uniform(ka), u2, u3, k1, klev, nproma,
+            load_level<real, AER>(nxt, *(const KArgs<real, S>*)launder_uniform(ka), u2, u3, k1, klev, nproma,
                                   launder_vgpr(lo0));
         }
       };
@@ -1283,7 +1297,7 @@ __device__ __forceinline__ void kcache_levels(cptr<KArgs<real>> ka, cptr<PT> cpa
 #endif
     }
     {
-      const KArgs<real>& A = *(const KArgs<real>*)launder_uniform(ka);
+      const KArgs<real, S>& A = *(const KArgs<real, S>*)launder_uniform(ka);
       const auto& c = params_here<PVR>(pv, cpar);
       const unsigned los = PVR ? launder_vgpr(lo0) : lo;
       store_level(A, u2, u3, k, klev, nproma, los, physics, ls, po);
@@ -1309,12 +1323,12 @@ struct CarryRegs : CarryState<real> {
 template <typename real, bool LDSC>
 using CarryOf = typename std::conditional<LDSC, CarryLds<real>, CarryRegs<real>>::type;
 
-template <typename real, int PF, bool AER, bool LDSC, typename PT>
-__device__ __forceinline__ void cloudsc_kcache_body(cptr<KArgs<real>> ka, cptr<PT> cpar) {
-  const KArgs<real>& A = *(const KArgs<real>*)ka;
+template <typename real, int PF, bool AER, bool LDSC, typename S, typename PT>
+__device__ __forceinline__ void cloudsc_kcache_body(cptr<KArgs<real, S>> ka, cptr<PT> cpar) {
+  const KArgs<real, S>& A = *(const KArgs<real, S>*)ka;
   const int b = blockIdx.x, jl = threadIdx.x;
   if (jl >= A.nproma || b * A.nproma + jl >= A.ngptot) return;
-  const unsigned lo = (unsigned)jl * (unsigned)sizeof(real);
+  const unsigned lo = (unsigned)jl * (unsigned)sizeof(S);   // the lane's byte offset in a field plane
   CarryOf<real, LDSC> cs(carry_lds_base<real>());
   init_carry<real>(cs);
   {
@@ -1322,7 +1336,7 @@ __device__ __forceinline__ void cloudsc_kcache_body(cptr<KArgs<real>> ka, cptr<P
     flux_top(c, A, (size_t)b * (A.klev + 1) * A.nproma, lo);
   }
   kcache_levels<real, PF, AER>(ka, cpar, b, lo, 0, A.klev, cs);
-  stg(((const KArgs<real>*)launder_uniform(ka))->prainfrac, (size_t)b * A.nproma, lo, cs.rainfrac);
+  stg(((const KArgs<real, S>*)launder_uniform(ka))->prainfrac, (size_t)b * A.nproma, lo, cs.rainfrac);
 }
 
 // ===================== persistent (work-queue) SCC-k-caching =====================
@@ -1408,11 +1422,11 @@ __device__ __forceinline__ void carry_io(real* st, size_t u, size_t plane, unsig
 #undef CLOUDSC_CARRY_IO
 }
 
-template <typename real, int PF, bool AER, bool LDSC, typename PT>
-__device__ __forceinline__ void cloudsc_kcache_persistent_body(cptr<KArgs<real>> ka, cptr<PT> cpar,
+template <typename real, int PF, bool AER, bool LDSC, typename ST, typename PT>
+__device__ __forceinline__ void cloudsc_kcache_persistent_body(cptr<KArgs<real, ST>> ka, cptr<PT> cpar,
                                                                const PersistArgs<real>& P) {
   __shared__ int s_item;
-  const KArgs<real>& A = *(const KArgs<real>*)ka;
+  const KArgs<real, ST>& A = *(const KArgs<real, ST>*)ka;
   const int nproma = A.nproma, nsub = P.nsub;
   // Every branch around a barrier is wave-uniform, and visibly so to the
   // compiler (SGPR conditions): the first wave of the workgroup does the
@@ -1450,7 +1464,10 @@ __device__ __forceinline__ void cloudsc_kcache_persistent_body(cptr<KArgs<real>>
     const int b = lb * S + st;
     const int sb = b * nsub + hh;
     const int jl = hh * 64 + (int)threadIdx.x;
-    const unsigned lo = (unsigned)jl * (unsigned)sizeof(real);
+    // the lane's byte offset in a field plane (storage type) and in a plane of
+    // the carried state in the workspace (compute type): one value unless mixed
+    const unsigned lo = (unsigned)jl * (unsigned)sizeof(ST);
+    const unsigned lo_c = (unsigned)jl * (unsigned)sizeof(real);
 #ifdef CLOUDSC_KSEG_TRACE
     const unsigned long long t_start = __builtin_amdgcn_s_memrealtime();
     unsigned long long t_ready = t_start;
@@ -1485,18 +1502,18 @@ __device__ __forceinline__ void cloudsc_kcache_persistent_body(cptr<KArgs<real>>
 #ifdef CLOUDSC_KSEG_TRACE
       t_ready = __builtin_amdgcn_s_memrealtime();
 #endif
-      if (active) carry_io(P.state, ust, (size_t)nproma, lo, cs, false);
+      if (active) carry_io(P.state, ust, (size_t)nproma, lo_c, cs, false);
     }
     if (active) kcache_levels<real, PF, AER>(ka, cpar, b, lo, P.lev[seg], P.lev[seg + 1], cs);
     if (seg + 1 < P.nseg) {
       // producer (G16 R1): sc1 payload stores, every wave drains, barrier, the
       // flag stored with an agent atomic
-      if (active) carry_io(P.state, ust, (size_t)nproma, lo, cs, true);
+      if (active) carry_io(P.state, ust, (size_t)nproma, lo_c, cs, true);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
       if (wave0) __hip_atomic_store(P.flags + sb, P.stamp + (unsigned)(seg + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     } else if (active) {
-      stg(((const KArgs<real>*)launder_uniform(ka))->prainfrac, (size_t)b * nproma, lo, cs.rainfrac);
+      stg(((const KArgs<real, ST>*)launder_uniform(ka))->prainfrac, (size_t)b * nproma, lo, cs.rainfrac);
     }
 #ifdef CLOUDSC_KSEG_TRACE
     const int gitem = seg * P.nblocks * nsub + sb;   // the item's index in the unstriped order

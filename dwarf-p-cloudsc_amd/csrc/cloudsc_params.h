@@ -59,11 +59,12 @@ inline DevParams<real> fold_params(const cloudsc_params_t& p) {
 }
 
 // plude read in place (plude_in == plude); par: the launch's device parameter block, NULL for the host build
-template <typename real>
-KArgs<real> make_kargs(const cloudsc_fields_t* f, int ngptot, int nproma, int klev, const DevParams<real>* par) {
-  using in = const real*;
-  using out = real*;
-  KArgs<real> a{};
+template <typename real, typename store = real>
+KArgs<real, store> make_kargs(const cloudsc_fields_t* f, int ngptot, int nproma, int klev,
+                              const DevParams<real>* par) {
+  using in = const store*;
+  using out = store*;
+  KArgs<real, store> a{};
   a.pt = (in)f->pt; a.pq = (in)f->pq; a.ttt = (in)f->tendency_tmp_t; a.ttq = (in)f->tendency_tmp_q;
   a.tta = (in)f->tendency_tmp_a; a.ttcld = (in)f->tendency_tmp_cld; a.pvfl = (in)f->pvfl; a.pvfi = (in)f->pvfi;
   a.phrsw = (in)f->phrsw; a.phrlw = (in)f->phrlw; a.pvervel = (in)f->pvervel; a.pap = (in)f->pap;

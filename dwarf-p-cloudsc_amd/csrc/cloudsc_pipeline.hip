@@ -576,13 +576,14 @@ int cloudsc_host_pipeline_create(cloudsc_host_pipeline_t** out, int device, int 
   *out = nullptr;
   int rc = validate_run_args(device, precision, CLOUDSC_VARIANT_KCACHE, ngptot, nproma, klev);
   if (rc) return rc;
+  if (precision == CLOUDSC_MIXED) return CLOUDSC_EINVAL;   // host-buffer paths: fp64 and fp32 only
   if (!fields_complete(host)) return CLOUDSC_EINVAL;
   cloudsc_host_pipeline* p = new cloudsc_host_pipeline();
   p->device = device; p->precision = precision; p->ngptot = ngptot; p->nproma = nproma; p->klev = klev;
   p->nblocks = ngptot / nproma + (ngptot % nproma ? 1 : 0);
   p->chunk_blocks = chunk_blocks < p->nblocks ? chunk_blocks : p->nblocks;
   p->nstreams = nstreams;
-  p->es = precision == CLOUDSC_FP64 ? sizeof(double) : sizeof(float);
+  p->es = precision_storage_bytes(precision);
   p->host = *host;
   auto fail = [&](int r) { cloudsc_host_pipeline_destroy(p); return r; };
   if (hipSetDevice(device) != hipSuccess) return fail(CLOUDSC_ENODEV);
@@ -926,6 +927,7 @@ extern "C" int cloudsc_host_run(int device, int precision, int variant, int ngpt
   HrClock::time_point t_packed{}, t_enq{}, t_synced{};
   int rc = validate_run_args(device, precision, variant, ngptot, nproma, klev);
   if (rc) return rc;
+  if (precision == CLOUDSC_MIXED) return CLOUDSC_EINVAL;   // host-buffer paths: fp64 and fp32 only
   if (!params || !host || !fields_complete(host)) return CLOUDSC_EINVAL;
   if ((rc = check_params(params))) return rc;
   const bool aer = params->laericesed || params->laericeauto;
@@ -951,7 +953,7 @@ extern "C" int cloudsc_host_run(int device, int precision, int variant, int ngpt
   const bool first_call = ctx->calls++ == 0;   // this call created the context (profiled apart)
   const int nblocks = ngptot / nproma + (ngptot % nproma ? 1 : 0);
   const int bsize = ngptot - (nblocks - 1) * nproma;   // active lanes of the last block
-  const size_t es = precision == CLOUDSC_FP64 ? sizeof(double) : sizeof(float);
+  const size_t es = precision_storage_bytes(precision);
   const void* const* hf = (const void* const*)host;
   // image layout: the inputs (and plude) first, then the outputs; 256-byte aligned fields
   size_t off[kNumFields] = {}, bytes[kNumFields] = {};

@@ -189,7 +189,7 @@ int memory_probe(int device, hipStream_t stream, int precision, int ngptot, int 
   float best = -1.f;
   for (int r = 0; r <= reps; r++) {
     HIPCHK(hipEventRecord(e0, stream));
-    if (precision == CLOUDSC_FP64) {
+    if (precision_storage_bytes(precision) == sizeof(double)) {   // a memory pattern: only the element size counts
       if (mode == 1) hipLaunchKernelGGL((place_probe_kernel<double, true>), grid, dim3(64), 0, stream, a);
       else hipLaunchKernelGGL((place_probe_kernel<double, false>), grid, dim3(64), 0, stream, a);
     } else {
@@ -472,7 +472,7 @@ bool fields_unregister(void* p, int device) {
 size_t member_bytes(int m, int precision, int ngptot, int nproma, int klev) {
   const FieldDesc& d = kFieldTable[m];
   const size_t nb = (size_t)(ngptot / nproma + (ngptot % nproma ? 1 : 0));
-  const size_t es = d.is_int ? sizeof(int) : precision == CLOUDSC_FP64 ? sizeof(double) : sizeof(float);
+  const size_t es = d.is_int ? sizeof(int) : precision_storage_bytes(precision);
   return nb * per_block_elems(d.kind, nproma, klev) * es;
 }
 

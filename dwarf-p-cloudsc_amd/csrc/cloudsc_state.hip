@@ -105,7 +105,7 @@ __global__ void __launch_bounds__(256) stats_kernel(const real* __restrict__ fld
 struct cloudsc_gpu_state {
   int device, precision, ngptot, nproma, klev, klon, nblocks;
   long long col_offset;
-  size_t es;                      // element size
+  size_t es;                      // bytes of a real field element in memory (precision_storage_bytes)
   hipStream_t stream;
   hipEvent_t ev0, ev1;
   cloudsc_fields_t f;             // device pointers
@@ -413,7 +413,7 @@ int expand_into(cloudsc_gpu_state* s, void* dst, const void* host_src, int nlev,
     if (is_int)
       hipLaunchKernelGGL((expand_kernel<int, int>), grid, dim3(256), 0, s->stream, (int*)dst, (const int*)d_src,
                          nlev, s->klon, s->nproma, s->col_offset, (long long)s->nblocks);
-    else if (s->precision == CLOUDSC_FP64)
+    else if (s->es == sizeof(double))
       hipLaunchKernelGGL((expand_kernel<double, double>), grid, dim3(256), 0, s->stream, (double*)dst,
                          (const double*)d_src, nlev, s->klon, s->nproma, s->col_offset, (long long)s->nblocks);
     else
@@ -454,7 +454,7 @@ int cloudsc_state_create(cloudsc_gpu_state_t** out, int device, int precision, i
   s->device = device; s->precision = precision; s->ngptot = ngptot; s->nproma = nproma;
   s->klev = t->klev; s->klon = t->klon; s->col_offset = col_offset;
   s->nblocks = ngptot / nproma + (ngptot % nproma ? 1 : 0);
-  s->es = precision == CLOUDSC_FP64 ? sizeof(double) : sizeof(float);
+  s->es = precision_storage_bytes(precision);
   std::memset(&s->f, 0, sizeof(s->f));
   auto fail = [&](int r) { cloudsc_state_destroy(s); return r; };
   if (hipSetDevice(device) != hipSuccess) return fail(CLOUDSC_ENODEV);
@@ -815,7 +815,7 @@ int cloudsc_state_download(cloudsc_gpu_state_t* s, int id, double* host) {
   void* const* slot = valid_slot(s, id, &kind);
   const size_t n = field_elems(s, kind);
   HIPCHK(hipStreamSynchronize(s->stream));
-  if (s->precision == CLOUDSC_FP64) {
+  if (s->es == sizeof(double)) {
     HIPCHK(hipMemcpy(host, *slot, n * sizeof(double), hipMemcpyDeviceToHost));
   } else {
     std::vector<float> tmp(n);
@@ -845,7 +845,7 @@ int cloudsc_state_validate(cloudsc_gpu_state_t* s, const cloudsc_reference_t* re
     e = hipMemcpyAsync(dref, ref->field[id], (size_t)nlev * ref->klon * sizeof(double), hipMemcpyHostToDevice,
                        s->stream);
     if (e != hipSuccess) break;
-    if (s->precision == CLOUDSC_FP64)
+    if (s->es == sizeof(double))
       hipLaunchKernelGGL(stats_kernel<double>, dim3(s->nblocks), dim3(256), 0, s->stream, (const double*)*slot,
                          dref, nlev, ref->klon, s->nproma, (long long)s->ngptot, s->col_offset, part);
     else

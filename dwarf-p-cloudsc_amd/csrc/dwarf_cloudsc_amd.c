@@ -105,7 +105,8 @@ static void usage(const char *prog) {
   fprintf(stderr,
           "usage: %s [<nthreads> <ngptot> <nproma>] [options]\n"
           "  --gpus N              shard the columns over N devices (default 1)\n"
-          "  --precision fp64|fp32 (default fp64)\n"
+          "  --precision fp64|fp32|mixed (default fp64; mixed: float fields, double arithmetic,\n"
+          "                        variants kseg, kcache and cpu; validated like fp32)\n"
           "  --variant kseg|kcache|scc|scc-private|cpu (default kseg; cpu = the library's CPU variant on\n"
           "                        <nthreads> host threads, host-memory fields: BASELINE config 1)\n"
           "  --fp32-exact-libm     fp32: exp/pow with the glibc algorithms (bit-identical to the fp32\n"
@@ -148,6 +149,7 @@ static int parse(int argc, char **argv, options_t *o) {
       NEEDV();
       if (!strcmp(v, "fp64") || !strcmp(v, "dp")) o->precision = CLOUDSC_FP64;
       else if (!strcmp(v, "fp32") || !strcmp(v, "sp")) o->precision = CLOUDSC_FP32;
+      else if (!strcmp(v, "mixed") || !strcmp(v, "mp")) o->precision = CLOUDSC_MIXED;
       else { fprintf(stderr, "bad precision %s\n", v); return -1; }
     } else if (!strcmp(a, "--variant")) {
       NEEDV();
@@ -352,6 +354,12 @@ static double print_error(const char *name, int ndim, const cloudsc_stats_t *s, 
   return rel;
 }
 
+/* a precision code's name and the bytes of its real field elements in memory */
+static const char *precision_name(int precision) {
+  return precision == CLOUDSC_FP64 ? "fp64" : precision == CLOUDSC_MIXED ? "mixed" : "fp32";
+}
+static int precision_bytes(int precision) { return precision == CLOUDSC_FP64 ? 8 : 4; }
+
 /* ---- host-memory paths: --transfer (GPU, H2D/D2H per chunk) and --variant cpu ---- */
 /* from the inventory (cloudsc_fields.def): cloudsc_io input index and validated field id ->
  * cloudsc_fields_t member index; the kind of every output member (-1 for the others) */
@@ -364,7 +372,8 @@ static const int k_out_kind[CLOUDSC_NFIELDS] = {CLOUDSC_FIELDS(OUT_KIND)};
 
 static int run_host(const options_t *o, const cloudsc_dataset_t *ds) {
   const int cpu = o->variant == VARIANT_CPU;
-  const int es = o->precision == CLOUDSC_FP64 ? 8 : 4;
+  const int es = precision_bytes(o->precision);
+  const int per_thread = cpu && o->precision == CLOUDSC_FP64;   /* the zinfo record: cloudsc_cpu_run_threads, fp64 */
   const int nb = o->ngptot / o->nproma + (o->ngptot % o->nproma ? 1 : 0);
   const int aer = ds->params.laericesed || ds->params.laericeauto;
   cloudsc_fields_t f;
@@ -421,8 +430,11 @@ static int run_host(const options_t *o, const cloudsc_dataset_t *ds) {
     double ms = 0.0;
     if (cpu) {
       double secs = 0.0;
-      rc = cloudsc_cpu_run_threads(nth, o->ngptot, o->nproma, ds->klev, &ds->params, &f, &secs, th_step,
-                                   th_blk_step, th_col_step);
+      if (per_thread)
+        rc = cloudsc_cpu_run_threads(nth, o->ngptot, o->nproma, ds->klev, &ds->params, &f, &secs, th_step,
+                                     th_blk_step, th_col_step);
+      else
+        rc = cloudsc_cpu_run_precision(nth, o->precision, o->ngptot, o->nproma, ds->klev, &ds->params, &f, &secs);
       ms = 1e3 * secs;
       if (r >= o->warmup)
         for (int t = 0; t < nth; t++) { th_s[t] += th_step[t]; th_blk[t] += th_blk_step[t]; th_col[t] += th_col_step[t]; }
@@ -442,7 +454,7 @@ static int run_host(const options_t *o, const cloudsc_dataset_t *ds) {
            "tid#", "Time(msec)", "MFlops/s", "col/s");
     /* per-thread rows (cloudsc_driver.c:238-253): columns and blocks of the last
      * step; time, MFlops/s and col/s over all timed steps like the TOTAL row */
-    for (int t = 0; cpu && t < nth; t++) {
+    for (int t = 0; per_thread && t < nth; t++) {
       const double tl = th_s[t], zfrac = (double)th_col[t] / cols;
       printf(" %10d%10d%10d%10d%10d %4d : %10d%10d%10d @ core#\n", o->numomp, o->ngptot, th_col_step[t],
              th_blk_step[t], o->nproma, t, (int)(tl * 1000.),
@@ -477,7 +489,8 @@ static int run_host(const options_t *o, const cloudsc_dataset_t *ds) {
         printf(" VALIDATION: %s (worst relative L1 error %.3e, gate %.1e, %d field(s) over)\n",
                bad ? "FAILED" : "PASSED", worst, o->tol, bad);
       else
-        printf(" VALIDATION: reported only (fp32 vs the fp64 reference; worst relative L1 error %.3e)\n", worst);
+        printf(" VALIDATION: reported only (%s vs the fp64 reference; worst relative L1 error %.3e)\n",
+               precision_name(o->precision), worst);
     }
   } else {
     fprintf(stderr, "dwarf-cloudsc-amd %s: %s (%s)\n", cpu ? "--variant cpu" : "--transfer", cloudsc_strerror(rc),
@@ -530,13 +543,13 @@ int main(int argc, char **argv) {
   }
 
   if (o.variant == VARIANT_CPU) {
-    if (o.precision != CLOUDSC_FP64 || o.ngpus != 1 || o.transfer) {
-      fprintf(stderr, "dwarf-cloudsc-amd: --variant cpu runs fp64 on the host (no --gpus/--transfer/fp32)\n");
+    if (o.precision == CLOUDSC_FP32 || o.ngpus != 1 || o.transfer) {
+      fprintf(stderr, "dwarf-cloudsc-amd: --variant cpu runs fp64 or mixed on the host (no --gpus/--transfer/fp32)\n");
       cloudsc_io_free(&ds);
       return EXIT_FAILURE;
     }
-    printf(" CLOUDSC-AMD: fp64, variant cpu (cloudsc_cpu_run, %d host thread(s)); state: %s\n", o.numomp,
-           ds.source);
+    printf(" CLOUDSC-AMD: %s, variant cpu (cloudsc_cpu_run, %d host thread(s)); state: %s\n",
+           precision_name(o.precision), o.numomp, ds.source);
     if (o.energy_s > 0.0) printf(" ENERGY: n/a (host variant: no GPU board power)\n");
     rc = run_host(&o, &ds);
     cloudsc_io_free(&ds);
@@ -552,9 +565,15 @@ int main(int argc, char **argv) {
   if (o.ngpus > ndev)
     printf(" CLOUDSC-AMD: %d shards on %d visible device(s): shard d runs on device d %% %d\n", o.ngpus, ndev, ndev);
 
+  if (o.precision == CLOUDSC_MIXED &&
+      (o.transfer || (o.variant != CLOUDSC_VARIANT_KSEG && o.variant != CLOUDSC_VARIANT_KCACHE))) {
+    fprintf(stderr, "dwarf-cloudsc-amd: --precision mixed runs --variant kseg|kcache|cpu (no --transfer)\n");
+    cloudsc_io_free(&ds);
+    return EXIT_FAILURE;
+  }
   if (o.transfer) {
     printf(" CLOUDSC-AMD: %s, variant %s, host-buffer path (--transfer), 1 device; state: %s\n",
-           o.precision == CLOUDSC_FP64 ? "fp64" : "fp32",
+           precision_name(o.precision),
            variant_name(o.variant),
            ds.source);
     if (o.energy_s > 0.0) printf(" ENERGY: n/a (the host-buffer path is bound by PCIe; run without --transfer)\n");
@@ -569,7 +588,7 @@ int main(int argc, char **argv) {
   cloudsc_io_reference(&ds, &ref);
   const int nblocks = o.ngptot / o.nproma + (o.ngptot % o.nproma ? 1 : 0);
   printf(" CLOUDSC-AMD: %s, variant %s, %d device(s); state: %s (KLON=%d, KLEV=%d)\n",
-         o.precision == CLOUDSC_FP64 ? "fp64" : (o.exact_libm ? "fp32 (glibc expf/powf)" : "fp32"),
+         o.precision == CLOUDSC_FP32 && o.exact_libm ? "fp32 (glibc expf/powf)" : precision_name(o.precision),
          variant_name(o.variant),
          o.ngpus, ds.source, ds.klon, ds.klev);
 
@@ -708,7 +727,8 @@ int main(int argc, char **argv) {
       printf(" VALIDATION: %s (worst relative L1 error %.3e, gate %.1e, %d field(s) over)\n",
              bad ? "FAILED" : "PASSED", worst, o.tol, bad);
     else
-      printf(" VALIDATION: reported only (fp32 vs the fp64 reference; worst relative L1 error %.3e)\n", worst);
+      printf(" VALIDATION: reported only (%s vs the fp64 reference; worst relative L1 error %.3e)\n",
+             precision_name(o.precision), worst);
   } else {
     printf(" VALIDATION: skipped (no reference outputs loaded)\n");
   }

@@ -41,8 +41,8 @@
  *   half-level field     [nblocks][klev+1][nproma]      (paph, the 14 flux fields)
  *   species field        [nblocks][NCLV][klev][nproma]  (pclv, tendency_*_cld)
  *   surface field        [nblocks][nproma]              (plsm, ktype, prainfrac_toprfz)
- * Element type is double for CLOUDSC_FP64 and float for CLOUDSC_FP32 (ktype is
- * always int32).  Lanes jl >= bsize of the last block are never read or written.
+ * Element type is double for CLOUDSC_FP64 and float for CLOUDSC_FP32 and
+ * CLOUDSC_MIXED (ktype is always int32).  Lanes jl >= bsize of the last block are never read or written.
  *
  * Output contract (stronger than the reference C kernel, matches the CUDA one):
  * the callee writes EVERY output element of every active column -- including
@@ -62,6 +62,28 @@ extern "C" {
 /* precision selector */
 #define CLOUDSC_FP64 8
 #define CLOUDSC_FP32 4
+/* Mixed precision: every real field is float in memory (ktype int32, as
+ * always), the arithmetic is double with the fp64 kernels' own exp/pow and
+ * IEEE divisions.  A load widens (exact); a store narrows with one conversion,
+ * round to nearest even with gradual underflow (no flush to zero).  The kernels
+ * never read back an output they stored, and the state carried between levels
+ * and KSEG segments stays double, so the contract is an identity, bit for bit
+ * over every output field and plude:
+ *
+ *   out = (float) fp64_kernel( (double) in )
+ *
+ * with `in` the float fields as stored (a caller holding doubles rounds them
+ * to float first) and fp64_kernel the CLOUDSC_FP64 computation -- the
+ * reference kernel's.  Half the bytes of fp64 per column and per resident
+ * state, the accuracy of fp64 arithmetic on float-rounded data (DESIGN.md
+ * §3.17).  Parameters, the KSEG workspace and cloudsc_gpu_scratch_bytes are
+ * fp64's; CLOUDSC_FP32_EXACT_LIBM is ignored, as for fp64.
+ * Where it runs: cloudsc_gpu_run / cloudsc_gpu_check with KCACHE and KSEG,
+ * cloudsc_fields_alloc, the state API, cloudsc_cpu_run_precision and the
+ * memory probes.  Where it does not (CLOUDSC_EINVAL): CLOUDSC_VARIANT_SCC and
+ * CLOUDSC_VARIANT_SCC_PRIVATE, cloudsc_host_pipeline_create and
+ * cloudsc_host_run; the drop-in cloudsc_c() is double by its signature. */
+#define CLOUDSC_MIXED 12
 
 /* kernel variant selector */
 #define CLOUDSC_VARIANT_SCC    1   /* SCC baseline: level phases as separate sweeps, temporaries in HBM scratch */
@@ -323,6 +345,16 @@ long long cloudsc_abi_sizeof(int which);
 int cloudsc_cpu_run(int nthreads, int ngptot, int nproma, int klev, const cloudsc_params_t *params,
                     const cloudsc_fields_t *host_fields, double *seconds);
 
+/* cloudsc_cpu_run for a precision code: CLOUDSC_FP64 (cloudsc_cpu_run itself)
+ * or CLOUDSC_MIXED -- host_fields then holds float arrays, the same phase
+ * functions run in double between a widening load and a narrowing store, and
+ * the output is the CLOUDSC_MIXED contract above, bit for bit, on a machine
+ * without a GPU.  Any other code: CLOUDSC_EINVAL (the fp32 arithmetic has no
+ * host form). */
+int cloudsc_cpu_run_precision(int nthreads, int precision, int ngptot, int nproma, int klev,
+                              const cloudsc_params_t *params, const cloudsc_fields_t *host_fields,
+                              double *seconds);
+
 /* cloudsc_cpu_run with the C dwarf's per-thread record (zinfo,
  * cloudsc_driver.c:185-228, printed as the "@ core#" rows at :238-253): for
  * thread t < nthreads, thread_seconds[t] = its wall time, thread_blocks[t] =
@@ -527,7 +559,8 @@ int cloudsc_state_validate(cloudsc_gpu_state_t *state, const cloudsc_reference_t
                            cloudsc_stats_t stats[CLOUDSC_NVALID]);
 
 /* Copy one validated output field to host memory in BLOCK layout as doubles
- * (fp32 states are widened).  `host` must hold the field's blocked size. */
+ * (fp32 and mixed states are widened, exactly).  `host` must hold the field's
+ * blocked size. */
 int cloudsc_state_download(cloudsc_gpu_state_t *state, int field_id, double *host);
 
 /* Element count of a validated field in block layout for this state. */
@@ -545,7 +578,8 @@ typedef struct cloudsc_host_pipeline cloudsc_host_pipeline_t;
  * precision's element type, ktype int).  The arrays are pinned in place
  * (hipHostRegister) until destroy; device buffers for `nstreams` chunk slots of
  * `chunk_blocks` blocks each are allocated here (1..16; chunk c uses slot
- * c % nstreams).  cloudsc_gpu_init must have been called for the device; the
+ * c % nstreams).  CLOUDSC_FP64 and CLOUDSC_FP32 only: CLOUDSC_MIXED returns
+ * CLOUDSC_EINVAL.  cloudsc_gpu_init must have been called for the device; the
  * pipeline keeps a copy of the device's default parameter set as it is at
  * creation. */
 int cloudsc_host_pipeline_create(cloudsc_host_pipeline_t **pipe, int device, int precision, int ngptot,
@@ -625,6 +659,7 @@ int cloudsc_debug_host_pipeline_engine_check(const cloudsc_host_pipeline_t *pipe
  * per device, its own stream, device buffers (grown to the largest call), KSEG
  * workspace and parameter set (uploaded again only when *params changes), so
  * concurrent callers share nothing.  Same output contract as cloudsc_gpu_run.
+ * CLOUDSC_FP64 and CLOUDSC_FP32 only: CLOUDSC_MIXED returns CLOUDSC_EINVAL.
  * The drop-in cloudsc_c() of libcloudsc_c_amd_gpu.so (csrc/cloudsc_c_dropin.c)
  * is built on it. */
 int cloudsc_host_run(int device, int precision, int variant, int ngptot, int nproma, int klev,
