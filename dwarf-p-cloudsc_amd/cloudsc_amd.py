@@ -148,6 +148,15 @@ PLACE_NONE = 1
 ALLOC_AEROSOLS = 2
 
 
+class LaunchGeometry(C.Structure):
+    """cloudsc_launch_geometry_t: what a physics launch would look like."""
+    _fields_ = [("pack", C.c_int), ("lanes", C.c_int), ("units", C.c_int), ("workgroups", C.c_int),
+                ("wg_threads", C.c_int)]
+
+    def to_dict(self) -> dict:
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 TEMPLATE_ORDER = list(INPUT_FIELDS)
 TEMPLATE_ORDER.insert(TEMPLATE_ORDER.index("plu") + 1, "plude")   # where the reference's files have it
 TEMPLATE_ORDER += AEROSOL_FIELDS
@@ -453,6 +462,8 @@ def gpu_lib(path: Optional[str] = None):
                                               C.POINTER(Fields), C.POINTER(C.c_double)]
     lib.cloudsc_debug_set_kseg_spin_limit.argtypes = [C.c_longlong]
     lib.cloudsc_debug_set_kseg_schedule.argtypes = [C.c_int, C.c_int]
+    lib.cloudsc_gpu_launch_geometry.argtypes = [C.c_int] * 6 + [C.POINTER(LaunchGeometry)]
+    lib.cloudsc_debug_set_narrow_pack.argtypes = [C.c_int]
     lib.cloudsc_debug_host_pipeline_mapping.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.cloudsc_debug_host_pinned.argtypes = [C.c_void_p, C.c_longlong]
     lib.cloudsc_debug_fp32_libm.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong]
@@ -469,6 +480,20 @@ FP32_EXACT_LIBM = 0x100
 def kseg_schedule(nseg: int = 0, grid: int = 0) -> None:
     """Diagnostic override of the KSEG schedule (0 = default); results do not change."""
     check(gpu_lib().cloudsc_debug_set_kseg_schedule(nseg, grid))
+
+
+def narrow_pack(mode: int = -1) -> None:
+    """Process-wide: 1 = run blocks of NPROMA <= 32 packed, 64 // nproma blocks per wave (KCACHE, KSEG),
+    0 = never, negative = the measured default per width.  The result bits do not depend on it."""
+    check(gpu_lib().cloudsc_debug_set_narrow_pack(mode))
+
+
+def launch_geometry(precision: int, variant: int, ngptot: int, nproma: int, klev: int, laer: bool = False) -> dict:
+    """What cloudsc_gpu_run would launch for these arguments (pack, lanes, units, workgroups, wg_threads);
+    host arithmetic, no GPU needed.  Raises CloudscError (code EINVAL) as the run would."""
+    g = LaunchGeometry()
+    check(gpu_lib().cloudsc_gpu_launch_geometry(precision, variant, ngptot, nproma, klev, int(bool(laer)), C.byref(g)))
+    return g.to_dict()
 
 
 def kseg_spin_limit(limit: int = -1) -> None:

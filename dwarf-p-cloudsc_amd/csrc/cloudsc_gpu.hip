@@ -190,6 +190,25 @@ __global__ void __launch_bounds__(256, WAVES) kseg_mixed_entry(const KArgs<doubl
   const cptr<KArgs<double, float>> ka = (cptr<KArgs<double, float>>)__builtin_amdgcn_kernarg_segment_ptr();
   cloudsc_kcache_persistent_body<double, PF, AER, LDSC>(ka, params_of<double, false>(ka), pa);
 }
+// Narrow blocks (NPROMA <= 32) packed into full waves: a workgroup is one wave
+// that walks PackArgs::pack consecutive blocks (cloudsc_kcache.h).  Entry points
+// of their own for every (compute, storage) pair, so the kernels above keep
+// their names and their code.
+template <typename real, typename S, int WAVES, int PF, bool AER, bool LDSC, bool FAST = false>
+__global__ void __launch_bounds__(256, WAVES) kcache_packed_entry(const KArgs<real, S> a, const PackArgs g) {
+  (void)a;
+  libm_tables_to_lds<real>();
+  const cptr<KArgs<real, S>> ka = (cptr<KArgs<real, S>>)__builtin_amdgcn_kernarg_segment_ptr();
+  cloudsc_kcache_packed_body<real, PF, AER, LDSC>(ka, params_of<real, FAST>(ka), g);
+}
+template <typename real, typename S, int WAVES, int PF, bool AER, bool LDSC, bool FAST = false>
+__global__ void __launch_bounds__(256, WAVES) kseg_packed_entry(const KArgs<real, S> a, const PersistArgs<real> pa,
+                                                                const PackArgs g) {
+  (void)a;
+  libm_tables_to_lds<real>();
+  const cptr<KArgs<real, S>> ka = (cptr<KArgs<real, S>>)__builtin_amdgcn_kernarg_segment_ptr();
+  cloudsc_kcache_persistent_body<real, PF, AER, LDSC, true>(ka, params_of<real, FAST>(ka), pa, g);
+}
 template <typename real, bool AER, bool FAST = false>
 __global__ void __launch_bounds__(256) scc_entry(const KArgs<real> a, const SccScratch<real> s) {
   (void)a;
@@ -289,6 +308,48 @@ int launch_kcache(hipStream_t st, const KArgs<real, S>& a, int nblocks, int npro
 #endif
 }
 
+// ---- narrow blocks packed into full waves ----
+// pack = 64 / nproma blocks per wave for nproma <= 32, on request
+// (cloudsc_debug_set_narrow_pack) or by the measured default; 1 = unpacked.
+// The packed kernels keep their lane offsets in 32 bits: the farthest one is
+// below pack * 5 * (klev + 1) * nproma elements of 8 bytes.
+std::atomic<int> g_narrow_pack{-1};
+// The default of a width class (negative mode), by the rule of DESIGN.md 3.18:
+// packed only where it measured faster than unpacked, by more than the spread
+// of the repeats, in all three precisions (profiles/narrow_pack/kseg_pack_ab.jsonl).
+// NPROMA 8 and 16 (pack 8 and 4) are 1.4-3.9 times faster packed; NPROMA 32
+// (pack 2) gains 2.5 % in fp64 and 4.6 % in mixed but loses 41 % in fp32, so
+// the widths above 16 (32 measured, 17-31 not measured) stay unpacked.
+bool narrow_pack_default(int nproma) { return nproma <= 16; }
+// Configurations whose packed kernel would not fit the register file without
+// spilling stay unpacked (profiles/narrow_pack/kernel_resources.txt): none does.
+bool narrow_pack_fits(int precision, int variant, bool aer) {
+  (void)precision; (void)variant; (void)aer;
+  return true;
+}
+int narrow_pack_factor(int precision, int variant, int nproma, int klev, bool aer) {
+  if (variant != CLOUDSC_VARIANT_KCACHE && variant != CLOUDSC_VARIANT_KSEG) return 1;
+  if (nproma > 32) return 1;
+  const int mode = g_narrow_pack.load(std::memory_order_relaxed);
+  if (mode == 0 || (mode < 0 && !narrow_pack_default(nproma))) return 1;
+  if (!narrow_pack_fits(precision, variant, aer)) return 1;
+  const int p = 64 / nproma;
+  if ((unsigned long long)p * 5ull * (unsigned long long)(klev + 1) * (unsigned long long)nproma * 8ull >= (1ull << 32))
+    return 1;
+  return p;
+}
+int precision_code(double, double) { return CLOUDSC_FP64; }
+int precision_code(float, float) { return CLOUDSC_FP32; }
+int precision_code(double, float) { return CLOUDSC_MIXED; }
+
+template <typename real, bool AER, bool FAST, typename S>
+int launch_kcache_packed(hipStream_t st, const KArgs<real, S>& a, int nblocks, int pack, const LaunchEvents* ev) {
+  const PackArgs g{pack, nblocks, (nblocks + pack - 1) / pack};
+  launch_physics(kcache_packed_entry<real, S, DefaultCfg<real>::waves, DefaultCfg<real>::pf, AER, false, FAST>,
+                 dim3(g.ngroups), dim3(64), 0, st, ev, a, g);
+  return CLOUDSC_OK;
+}
+
 // ---- persistent segmented variant ----
 // Every item is one wave: a block of NPROMA > 64 columns is run as
 // ceil(NPROMA/64) 64-column sub-blocks (the block layout is unchanged: sub-block
@@ -372,36 +433,11 @@ __global__ void __launch_bounds__(256) kseg_prepare_kernel(unsigned* ws, int nfl
 
 namespace {
 
-template <typename real, int WAVES, int PF, bool AER, bool LDSC, bool FAST, typename S>
-int launch_kseg_cfg(hipStream_t st, const KArgs<real, S>& a, const PersistArgs<real>& pa, int nproma, int nitems,
-                    int* grid_out, const LaunchEvents* ev) {
-  const int nseg = pa.nseg;
-  auto kern = kseg_kernel<real, S, WAVES, PF, AER, LDSC, FAST>();
-  const int wg = kseg_wg(nproma);
-  const size_t lds = LDSC ? carry_lds_bytes<real>(wg) : 0;
-  // Waves per SIMD: as many as fit, but no more than whole rounds of the work
-  // units (one column's 64-column sub-block) per SIMD: 2560 units on 1024 SIMDs
-  // take 2 waves each; a third resident wave (fp32 fits 3) would only find a
-  // next-segment item and spin until its predecessor finishes (fp32 KSEG 1.12 ms
-  // at 2 waves/SIMD against 1.23 ms at 3, profiles/r02/kseg_grid_sweep.jsonl).
-  // An over-estimate of residency only delays the extra workgroups: progress
-  // never depends on it, items are dequeued in order.
-  // Cached per workgroup size; threads driving different devices may race here, hence atomics.
-  static std::atomic<int> cache[65];
-  int per_cu = cache[wg].load(std::memory_order_relaxed);
-  if (!per_cu) {
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, wg, lds) != hipSuccess || n <= 0) n = 1;
-    per_cu = n;
-    cache[wg].store(n, std::memory_order_relaxed);
-  }
-  int dev = 0, ncu = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
-    ncu = 256;
-  constexpr int kSimdsPerCu = 4;                       // CDNA4 compute unit
+constexpr int kSimdsPerCu = 4;                       // CDNA4 compute unit
+// the KSEG grid for per_cu resident workgroups on each of ncu compute units
+int kseg_grid_size(int per_cu, int ncu, int nitems, int nseg) {
   const int simds = kSimdsPerCu * ncu;
-  const int units = nitems / (nseg > 0 ? nseg : 1);   // 64-column sub-blocks
+  const int units = nitems / (nseg > 0 ? nseg : 1);   // one-wave work units
   const int per_simd = per_cu / kSimdsPerCu > 0 ? per_cu / kSimdsPerCu : 1;
   int w = units / simds;
   if (w < 1) w = 1;
@@ -412,27 +448,64 @@ int launch_kseg_cfg(hipStream_t st, const KArgs<real, S>& a, const PersistArgs<r
   grid = env_int("CLOUDSC_KSEG_GRID", 0) > 0 ? env_int("CLOUDSC_KSEG_GRID", 0) : grid;
 #endif
   if (grid > nitems) grid = nitems;
+  return grid;
+}
+
+// pk: the packed kernel (one 64-lane workgroup per group of blocks); NULL: the unpacked one
+template <typename real, int WAVES, int PF, bool AER, bool LDSC, bool FAST, typename S>
+int launch_kseg_cfg(hipStream_t st, const KArgs<real, S>& a, const PersistArgs<real>& pa, int nproma, int nitems,
+                    int* grid_out, const LaunchEvents* ev, const PackArgs* pk = nullptr) {
+  const int nseg = pa.nseg;
+  auto kern = kseg_kernel<real, S, WAVES, PF, AER, LDSC, FAST>();
+  auto kern_packed = kseg_packed_entry<real, S, WAVES, PF, AER, LDSC, FAST>;
+  const int wg = pk ? 64 : kseg_wg(nproma);
+  const size_t lds = LDSC ? carry_lds_bytes<real>(wg) : 0;
+  // Waves per SIMD: as many as fit, but no more than whole rounds of the work
+  // units (one column's 64-column sub-block) per SIMD: 2560 units on 1024 SIMDs
+  // take 2 waves each; a third resident wave (fp32 fits 3) would only find a
+  // next-segment item and spin until its predecessor finishes (fp32 KSEG 1.12 ms
+  // at 2 waves/SIMD against 1.23 ms at 3, profiles/r02/kseg_grid_sweep.jsonl).
+  // An over-estimate of residency only delays the extra workgroups: progress
+  // never depends on it, items are dequeued in order.
+  // Cached per workgroup size; threads driving different devices may race here, hence atomics.
+  static std::atomic<int> cache[66];   // [65]: the packed kernel
+  const int slot = pk ? 65 : wg;
+  int per_cu = cache[slot].load(std::memory_order_relaxed);
+  if (!per_cu) {
+    int n = 0;
+    const hipError_t e = pk ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern_packed, wg, lds)
+                            : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, wg, lds);
+    if (e != hipSuccess || n <= 0) n = 1;
+    per_cu = n;
+    cache[slot].store(n, std::memory_order_relaxed);
+  }
+  int dev = 0, ncu = 0;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
+    ncu = 256;
+  const int grid = kseg_grid_size(per_cu, ncu, nitems, nseg);
   PersistArgs<real> pg = pa;
   pg.nstripes = kseg_nstripes(grid);
-  launch_physics(kern, dim3(grid), dim3(wg), lds, st, ev, a, pg);
+  if (pk) launch_physics(kern_packed, dim3(grid), dim3(wg), lds, st, ev, a, pg, *pk);
+  else launch_physics(kern, dim3(grid), dim3(wg), lds, st, ev, a, pg);
   *grid_out = grid;
   return CLOUDSC_OK;
 }
 
 template <typename real, bool AER, bool FAST, typename S>
 int launch_kseg(hipStream_t st, const KArgs<real, S>& a, const PersistArgs<real>& pa, int nproma, int nitems,
-                int* grid_out, const LaunchEvents* ev) {
+                int* grid_out, const LaunchEvents* ev, const PackArgs* pk) {
 #ifdef CLOUDSC_DEBUG_KNOBS
   switch (env_int("CLOUDSC_KCACHE_CFG", DefaultCfg<real>::code)) {
 #define X(code, w, pf, ldsc) \
-  case code: return launch_kseg_cfg<real, w, pf, AER, ldsc, FAST>(st, a, pa, nproma, nitems, grid_out, ev);
+  case code: return launch_kseg_cfg<real, w, pf, AER, ldsc, FAST>(st, a, pa, nproma, nitems, grid_out, ev, pk);
     CLOUDSC_FOR_EACH_CFG(X)
 #undef X
     default: return CLOUDSC_EINVAL;
   }
 #else
   return launch_kseg_cfg<real, DefaultCfg<real>::waves, DefaultCfg<real>::pf, AER, false, FAST>(st, a, pa, nproma, nitems,
-                                                                                        grid_out, ev);
+                                                                                        grid_out, ev, pk);
 #endif
 }
 
@@ -465,10 +538,18 @@ int launch_v(hipStream_t st, int variant, const cloudsc_fields_t* f, int ngptot,
   const bool aer = ps.aer;
   if (aer && (!f->pre_ice || !f->picrit_aer || !f->pnice)) return CLOUDSC_EINVAL;
   int rc = CLOUDSC_OK;
+  // blocks per wave (1 = unpacked) and the packed launches' extra kernel argument
+  const int pack = narrow_pack_factor(precision_code(real(), ST()), variant, nproma, klev, aer);
+  const PackArgs pk{pack, nblocks, (nblocks + pack - 1) / pack};
   if (variant == CLOUDSC_VARIANT_KCACHE) {
-    if constexpr (CLOUDSC_KEEP_KERNEL(real, false, false))
-      rc = aer ? launch_kcache<real, true, FAST>(st, a, nblocks, nproma, ev)
-               : launch_kcache<real, false, FAST>(st, a, nblocks, nproma, ev);
+    if constexpr (CLOUDSC_KEEP_KERNEL(real, false, false)) {
+      if (pack > 1)
+        rc = aer ? launch_kcache_packed<real, true, FAST>(st, a, nblocks, pack, ev)
+                 : launch_kcache_packed<real, false, FAST>(st, a, nblocks, pack, ev);
+      else
+        rc = aer ? launch_kcache<real, true, FAST>(st, a, nblocks, nproma, ev)
+                 : launch_kcache<real, false, FAST>(st, a, nblocks, nproma, ev);
+    }
   } else if (variant == CLOUDSC_VARIANT_KSEG) {
     if (!scratch) return CLOUDSC_EINVAL;
     PersistArgs<real> pa;
@@ -477,7 +558,11 @@ int launch_v(hipStream_t st, int variant, const cloudsc_fields_t* f, int ngptot,
     pa.clk = (unsigned long long*)((char*)scratch + kKsegClkOffset);
     pa.flags = (unsigned*)((char*)scratch + kKsegFlagOffset);
     pa.state = (real*)((char*)scratch + kseg_ctl_bytes(nblocks, nproma));
-    pa.nsub = kseg_nsub(nproma);
+    pa.nsub = pack > 1 ? 1 : kseg_nsub(nproma);
+    // the schedule's units: blocks, or groups of `pack` blocks (one flag each:
+    // the first pk.ngroups words of the flag area)
+    const int nunits = pack > 1 ? pk.ngroups : nblocks;
+    const PackArgs* const pkp = pack > 1 ? &pk : nullptr;
     pa.spin_limit = g_kseg_spin_limit.load(std::memory_order_relaxed);
     // item order (segment, block, sub-block); (segment, sub-block, block) measured
     // the same within noise at NPROMA 128, 2 % slower at 256 (profiles/r01/kseg_subblock_order.jsonl)
@@ -507,10 +592,10 @@ int launch_v(hipStream_t st, int variant, const cloudsc_fields_t* f, int ngptot,
       pa.lev[n] = klev;
     }
 #endif
-    pa.nitems = pa.nseg * nblocks * pa.nsub;
+    pa.nitems = pa.nseg * nunits * pa.nsub;
     const bool zero_ws = !(ep && ep->ready);
     if (zero_ws) {
-      const int nflags = nblocks * pa.nsub;
+      const int nflags = nblocks * kseg_nsub(nproma);
       const int g = (nflags + 255) / 256 < 64 ? (nflags + 255) / 256 : 64;
       hipLaunchKernelGGL(kseg_prepare_kernel, dim3(g > 0 ? g : 1), dim3(256), 0, st, (unsigned*)scratch, nflags);
       if (ep) ep->ready = false;
@@ -519,17 +604,17 @@ int launch_v(hipStream_t st, int variant, const cloudsc_fields_t* f, int ngptot,
     pa.stamp = zero_ws ? 0u : ep->stamp;
     int grid = 0;
     if constexpr (CLOUDSC_KEEP_KERNEL(real, true, true))
-      rc = aer ? launch_kseg<real, true, FAST>(st, a, pa, nproma, pa.nitems, &grid, ev)
-               : launch_kseg<real, false, FAST>(st, a, pa, nproma, pa.nitems, &grid, ev);
+      rc = aer ? launch_kseg<real, true, FAST>(st, a, pa, nproma, pa.nitems, &grid, ev, pkp)
+               : launch_kseg<real, false, FAST>(st, a, pa, nproma, pa.nitems, &grid, ev, pkp);
     else if constexpr (CLOUDSC_KEEP_KERNEL(real, true, false))
-      rc = launch_kseg<real, false, FAST>(st, a, pa, nproma, pa.nitems, &grid, ev);
+      rc = launch_kseg<real, false, FAST>(st, a, pa, nproma, pa.nitems, &grid, ev, pkp);
     if (rc) return rc;
     HIPCHK(hipGetLastError());
     if (ep) {   // the next launch on this workspace continues where this one ends
       // stripe q took its items plus one past-the-end ticket per workgroup of it
       const int S = kseg_nstripes(grid);
       for (int q = 0; q < kKsegStripes; q++) {
-        const unsigned nbs = q < S ? (unsigned)((nblocks - q + S - 1) / S) : 0u;
+        const unsigned nbs = q < S ? (unsigned)((nunits - q + S - 1) / S) : 0u;
         const unsigned wgs = q < S ? (unsigned)((grid - q + S - 1) / S) : 0u;
         ep->base[q] = pa.base[q] + (unsigned)pa.nseg * nbs * (unsigned)pa.nsub + wgs;
       }
@@ -630,12 +715,8 @@ long long cloudsc_gpu_scratch_bytes(int precision, int variant, int ngptot, int 
 }  // extern "C"
 
 namespace cloudsc_impl {
-int validate_run_args(int device, int precision, int variant, int ngptot, int nproma, int klev) {
-  if (variant & ~(0xff | CLOUDSC_FP32_EXACT_LIBM)) return CLOUDSC_EINVAL;
-  variant = variant_kind(variant);
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return CLOUDSC_ENODEV;
-  if (device < 0 || device >= n || device >= kMaxDevices) return CLOUDSC_ENODEV;
+// the checks of validate_run_args that need no device
+static int validate_shape_args(int precision, int variant, int ngptot, int nproma, int klev) {
   if (!precision_storage_bytes(precision)) return CLOUDSC_EINVAL;
   if (variant != CLOUDSC_VARIANT_KCACHE && variant != CLOUDSC_VARIANT_SCC && variant != CLOUDSC_VARIANT_KSEG &&
       variant != CLOUDSC_VARIANT_SCC_PRIVATE)
@@ -648,6 +729,14 @@ int validate_run_args(int device, int precision, int variant, int ngptot, int np
   const int max_nproma = variant == CLOUDSC_VARIANT_KSEG ? (1 << 24) : 256;
   if (ngptot <= 0 || nproma <= 0 || nproma > max_nproma || klev < 2) return CLOUDSC_EINVAL;
   return CLOUDSC_OK;
+}
+int validate_run_args(int device, int precision, int variant, int ngptot, int nproma, int klev) {
+  if (variant & ~(0xff | CLOUDSC_FP32_EXACT_LIBM)) return CLOUDSC_EINVAL;
+  variant = variant_kind(variant);
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return CLOUDSC_ENODEV;
+  if (device < 0 || device >= n || device >= kMaxDevices) return CLOUDSC_ENODEV;
+  return validate_shape_args(precision, variant, ngptot, nproma, klev);
 }
 
 // plude_in: NULL = in place (the reference INOUT semantics); otherwise the
@@ -727,6 +816,38 @@ int cloudsc_debug_set_kseg_schedule(int nseg, int grid) {
   if (nseg < 0 || grid < 0) return CLOUDSC_EINVAL;
   g_kseg_nseg.store(nseg, std::memory_order_relaxed);
   g_kseg_grid.store(grid, std::memory_order_relaxed);
+  return CLOUDSC_OK;
+}
+
+int cloudsc_debug_set_narrow_pack(int mode) {
+  g_narrow_pack.store(mode < 0 ? -1 : (mode ? 1 : 0), std::memory_order_relaxed);
+  return CLOUDSC_OK;
+}
+
+int cloudsc_gpu_launch_geometry(int precision, int variant, int ngptot, int nproma, int klev, int laer,
+                                cloudsc_launch_geometry_t* out) {
+  if (!out) return CLOUDSC_EINVAL;
+  if (variant & ~(0xff | CLOUDSC_FP32_EXACT_LIBM)) return CLOUDSC_EINVAL;
+  variant = variant_kind(variant);
+  const int rc = validate_shape_args(precision, variant, ngptot, nproma, klev);
+  if (rc) return rc;
+  const int nblocks = ngptot / nproma + (ngptot % nproma ? 1 : 0);
+  const int pack = narrow_pack_factor(precision, variant, nproma, klev, laer != 0);
+  const int nsub = kseg_nsub(nproma);
+  out->pack = pack;
+  out->lanes = pack * (nproma < 64 ? nproma : 64);
+  out->units = (nblocks + pack - 1) / pack * nsub;
+  if (variant == CLOUDSC_VARIANT_KSEG) {
+    int nseg = kKsegNseg;
+    if (const int n = g_kseg_nseg.load(std::memory_order_relaxed)) nseg = n > kMaxSeg ? kMaxSeg : n;
+    if (nseg > klev) nseg = klev;
+    // an MI355X: 256 compute units, 2 resident waves per SIMD (one-wave workgroups)
+    out->workgroups = kseg_grid_size(2 * kSimdsPerCu, 256, nseg * out->units, nseg);
+    out->wg_threads = pack > 1 ? 64 : kseg_wg(nproma);
+  } else {
+    out->workgroups = pack > 1 ? out->units : nblocks;
+    out->wg_threads = pack > 1 ? 64 : nproma;
+  }
   return CLOUDSC_OK;
 }
 

@@ -143,6 +143,39 @@ CLOUDSC_HD void stg_sp(T* ubase, size_t uidx, unsigned lane_bytes, typename std:
   else stg(ubase, uidx, lane_bytes, v);
 }
 
+// The lane's byte offset, by field kind.  Unpacked (one NPROMA block, or one
+// 64-column sub-block of it, per wave) every kind has the same offset, jl *
+// sizeof(S): the type is a plain `unsigned`.  Packed (a wave walks p = 64 /
+// nproma consecutive blocks, lane l = s * nproma + jl serving column jl of block
+// b0 + s) the uniform base is block b0's and sub-slot s is a whole block further
+// on, whose size depends on the kind: PackLo keeps jl and s * nproma in bytes
+// (two VGPRs) and forms each kind's offset where it is used, one multiply-add by
+// a uniform factor, instead of keeping four offsets alive across the level.
+struct PackLo {
+  unsigned jb;   // jl * sizeof(S)
+  unsigned sb;   // s * nproma * sizeof(S)
+  int klev;      // uniform
+};
+CLOUDSC_HD unsigned lo_full(unsigned lo) { return lo; }      // [nblocks][klev][nproma]
+CLOUDSC_HD unsigned lo_half(unsigned lo) { return lo; }      // [nblocks][klev+1][nproma]
+CLOUDSC_HD unsigned lo_spec(unsigned lo) { return lo; }      // [nblocks][5][klev][nproma]
+CLOUDSC_HD unsigned lo_surf(unsigned lo) { return lo; }      // [nblocks][nproma]
+CLOUDSC_HD unsigned lo_full(const PackLo& p) { return p.sb * (unsigned)p.klev + p.jb; }
+CLOUDSC_HD unsigned lo_half(const PackLo& p) { return p.sb * (unsigned)(p.klev + 1) + p.jb; }
+CLOUDSC_HD unsigned lo_spec(const PackLo& p) { return p.sb * (unsigned)(5 * p.klev) + p.jb; }
+CLOUDSC_HD unsigned lo_surf(const PackLo& p) { return p.sb + p.jb; }
+CLOUDSC_HD PackLo launder_vgpr(PackLo p) {
+  p.jb = launder_vgpr(p.jb);
+  p.sb = launder_vgpr(p.sb);
+  return p;
+}
+// A copy of the lane's values from which offsets are formed where they are used:
+// offsets formed from one shared copy are loop-invariant and would be hoisted,
+// one more register each live across the level loop.  The unpacked offset is
+// its own only form and stays as it is.
+CLOUDSC_HD unsigned lane_here(unsigned lo) { return lo; }
+CLOUDSC_HD PackLo lane_here(const PackLo& p) { return launder_vgpr(p); }
+
 // Per-level inputs of one column (the prefetch unit).
 template <typename real>
 struct LevelIn {
@@ -159,22 +192,24 @@ struct EarlyIn {
   real pt, pq, ttt, ttq, tta, pa, pap;
   real pclv[4], ttcld[4];
 };
-template <typename real, typename S>
+template <typename real, typename S, typename LO>
 CLOUDSC_HD void load_early(EarlyIn<real>& E, const KArgs<real, S>& A, size_t u2, size_t u3, int k, int klev,
-                           int nproma, unsigned lo) {
+                           int nproma, LO lane) {
   const size_t i = u2 + (size_t)k * nproma;
+  const unsigned lo = lo_full(lane), ls = lo_spec(lane);
   E.pt = ldg1(A.pt, i, lo); E.pq = ldg1(A.pq, i, lo); E.ttt = ldg1(A.ttt, i, lo); E.ttq = ldg1(A.ttq, i, lo);
   E.tta = ldg1(A.tta, i, lo); E.pa = ldg1(A.pa, i, lo); E.pap = ldg1(A.pap, i, lo);
 #pragma unroll
   for (int m = 0; m < 4; m++) {
     const size_t j = u3 + ((size_t)m * klev + k) * nproma;
-    E.pclv[m] = ldg1_sp<kSpOpaque<real, S>>(A.pclv, j, lo);
-    E.ttcld[m] = ldg1_sp<kSpOpaque<real, S>>(A.ttcld, j, lo);
+    E.pclv[m] = ldg1_sp<kSpOpaque<real, S>>(A.pclv, j, ls);
+    E.ttcld[m] = ldg1_sp<kSpOpaque<real, S>>(A.ttcld, j, ls);
   }
 }
-template <typename real, bool AER, typename S>
-CLOUDSC_HD void load_late(LevelIn<real>& L, const KArgs<real, S>& A, size_t u2, int k, int nproma, unsigned lo) {
+template <typename real, bool AER, typename S, typename LO>
+CLOUDSC_HD void load_late(LevelIn<real>& L, const KArgs<real, S>& A, size_t u2, int k, int nproma, LO lane) {
   const size_t i = u2 + (size_t)k * nproma;
+  const unsigned lo = lo_full(lane);
   L.plude = ldg1(A.plude_in, i, lo); L.pvfl = ldg1(A.pvfl, i, lo); L.pvfi = ldg1(A.pvfi, i, lo);
   L.phrsw = ldg1(A.phrsw, i, lo); L.phrlw = ldg1(A.phrlw, i, lo); L.pvervel = ldg1(A.pvervel, i, lo);
   L.psnde = ldg1(A.psnde, i, lo); L.psupsat = ldg1(A.psupsat, i, lo);
@@ -275,18 +310,19 @@ struct PhysOut {
 // All loads of a level are unconditional (the physics-only fields are read at
 // every level): branches around memory operations make hipcc's vmcnt
 // bookkeeping fall back to vmcnt(0), which drains the software pipeline.
-template <typename real, bool AER, typename S>
+template <typename real, bool AER, typename S, typename LO>
 CLOUDSC_HD void load_level(LevelIn<real>& L, const KArgs<real, S>& A, size_t u2, size_t u3, int k,
-                                           int klev, int nproma, unsigned lo) {
+                                           int klev, int nproma, LO lane) {
   const size_t i = u2 + (size_t)k * nproma;
+  const unsigned lo = lo_full(lane), ls = lo_spec(lane);
   L.pt = ldg1(A.pt, i, lo); L.pq = ldg1(A.pq, i, lo); L.ttt = ldg1(A.ttt, i, lo); L.ttq = ldg1(A.ttq, i, lo);
   L.tta = ldg1(A.tta, i, lo); L.pa = ldg1(A.pa, i, lo); L.pap = ldg1(A.pap, i, lo);
   L.plude = ldg1(A.plude_in, i, lo); L.pvfl = ldg1(A.pvfl, i, lo); L.pvfi = ldg1(A.pvfi, i, lo);
 #pragma unroll
   for (int m = 0; m < 4; m++) {
     const size_t j = u3 + ((size_t)m * klev + k) * nproma;
-    L.pclv[m] = ldg1_sp<kSpOpaque<real, S>>(A.pclv, j, lo);
-    L.ttcld[m] = ldg1_sp<kSpOpaque<real, S>>(A.ttcld, j, lo);
+    L.pclv[m] = ldg1_sp<kSpOpaque<real, S>>(A.pclv, j, ls);
+    L.ttcld[m] = ldg1_sp<kSpOpaque<real, S>>(A.ttcld, j, ls);
   }
   L.phrsw = ldg1(A.phrsw, i, lo); L.phrlw = ldg1(A.phrlw, i, lo); L.pvervel = ldg1(A.pvervel, i, lo);
   L.psnde = ldg1(A.psnde, i, lo); L.psupsat = ldg1(A.psupsat, i, lo);
@@ -1053,8 +1089,8 @@ CLOUDSC_HD void physics_level(const P& c, const int k, const int klev,
 }
 
 // ===== 8. flux diagnostics of one level (cloudsc_c.c:2521-2582), written at half level k+1 =====
-template <typename real, typename P, typename CS, typename S>
-CLOUDSC_HD void flux_level(const P& c, const KArgs<real, S>& A, size_t h, unsigned lo,
+template <typename real, typename P, typename CS, typename S, typename LO>
+CLOUDSC_HD void flux_level(const P& c, const KArgs<real, S>& A, size_t h, LO lane,
                                            const LevelIn<real>& in, const LevelState<real>& ls,
                                            const PhysOut<real>& po, real paph_k, real paph_n,
                                            CS& cs) {
@@ -1074,6 +1110,7 @@ CLOUDSC_HD void flux_level(const P& c, const KArgs<real, S>& A, size_t h, unsign
   cs.fl_itur = cs.fl_itur + (in.pvfi * c.ptsphy) * zgdph_r;
   const real sf = fi + (zqxn[QS] - zqx0[QS]) * zgdph_r;
   const real sng = nng + zlneg[QS] * zgdph_r;
+  const unsigned lo = lo_half(lane);
   stg(A.pfsqlf, h, lo, cs.fl_lf); stg(A.pfsqif, h, lo, cs.fl_if);
   stg(A.pfcqlng, h, lo, cs.fl_lng); stg(A.pfcqnng, h, lo, cs.fl_nng);
   stg(A.pfsqltur, h, lo, cs.fl_ltur); stg(A.pfsqitur, h, lo, cs.fl_itur);
@@ -1085,8 +1122,9 @@ CLOUDSC_HD void flux_level(const P& c, const KArgs<real, S>& A, size_t h, unsign
 }
 
 // level-0 half-level outputs (cloudsc_c.c:2523-2543, 2578-2579)
-template <typename real, typename P, typename S>
-CLOUDSC_HD void flux_top(const P& c, const KArgs<real, S>& A, size_t h0, unsigned lo) {
+template <typename real, typename P, typename S, typename LO>
+CLOUDSC_HD void flux_top(const P& c, const KArgs<real, S>& A, size_t h0, LO lane) {
+  const unsigned lo = lo_half(lane);
   stg(A.pfsqlf, h0, lo, R(0.0)); stg(A.pfsqif, h0, lo, R(0.0)); stg(A.pfsqrf, h0, lo, R(0.0));
   stg(A.pfsqsf, h0, lo, R(0.0)); stg(A.pfcqlng, h0, lo, R(0.0)); stg(A.pfcqnng, h0, lo, R(0.0));
   stg(A.pfcqrng, h0, lo, R(0.0)); stg(A.pfcqsng, h0, lo, R(0.0));
@@ -1096,13 +1134,14 @@ CLOUDSC_HD void flux_top(const P& c, const KArgs<real, S>& A, size_t h0, unsigne
   stg(A.pfhpsl, h0, lo, -c.rlvtt * plsl); stg(A.pfhpsn, h0, lo, -c.rlstt * plsn);
 }
 
-template <typename real, typename P, typename S>
+template <typename real, typename P, typename S, typename LO>
 CLOUDSC_HD ColConst<real> column_constants(const P& c, const KArgs<real, S>& A,
-                                                           size_t u1, size_t uh, unsigned lo) {
+                                                           size_t u1, size_t uh, LO lane) {
   ColConst<real> cc;
+  const unsigned lo = lo_surf(lane);
   const real plsm = ldg(A.plsm, u1, lo);
   cc.ktype = ldg(A.ktype, u1, lo * (unsigned)(sizeof(int)) / (unsigned)sizeof(S));
-  cc.paph_sfc = ldg(A.paph, uh + (size_t)A.klev * A.nproma, lo);
+  cc.paph_sfc = ldg(A.paph, uh + (size_t)A.klev * A.nproma, lo_half(lane));
   const bool land = plsm > R(0.5);
   cc.kk_const = land ? pval(c, c.rcl_kk_cloud_num_land) : pval(c, c.rcl_kk_cloud_num_sea);
   cc.kk_lcrit = land ? pval(c, c.rclcrit_land) : pval(c, c.rclcrit_sea);
@@ -1110,11 +1149,12 @@ CLOUDSC_HD ColConst<real> column_constants(const P& c, const KArgs<real, S>& A,
   return cc;
 }
 
-template <typename real, typename S>
+template <typename real, typename S, typename LO>
 CLOUDSC_HD void store_level(const KArgs<real, S>& A, size_t u2, size_t u3, int k, int klev,
-                                            int nproma, unsigned lo, bool physics, const LevelState<real>& ls,
+                                            int nproma, LO lane, bool physics, const LevelState<real>& ls,
                                             const PhysOut<real>& po) {
   const size_t i = u2 + (size_t)k * nproma;
+  const unsigned lo = lo_full(lane), lsp = lo_spec(lane);
   stg(A.tlt, i, lo, ls.ttend);
   stg(A.tlq, i, lo, ls.qtend);
   stg(A.tla, i, lo, po.atend);
@@ -1122,8 +1162,8 @@ CLOUDSC_HD void store_level(const KArgs<real, S>& A, size_t u2, size_t u3, int k
   stg(A.plude, i, lo, po.plude_k);   // INOUT: rewritten unchanged where not rescaled (no branch on a store)
 #pragma unroll
   for (int m = 0; m < 4; m++)
-    stg_sp<kSpOpaque<real, S>>(A.tlcld, u3 + ((size_t)m * klev + k) * nproma, lo, po.ctend[m]);
-  stg_sp<kSpOpaque<real, S>>(A.tlcld, u3 + ((size_t)4 * klev + k) * nproma, lo, R(0.0));
+    stg_sp<kSpOpaque<real, S>>(A.tlcld, u3 + ((size_t)m * klev + k) * nproma, lsp, po.ctend[m]);
+  stg_sp<kSpOpaque<real, S>>(A.tlcld, u3 + ((size_t)4 * klev + k) * nproma, lsp, R(0.0));
 }
 
 template <typename real, typename CS>
@@ -1153,11 +1193,11 @@ __device__ __forceinline__ const auto& params_here(const PV& pv, cptr<PT> cpar) 
 // kcache_levels runs levels [lev0, lev1) of block b for one (active) lane with
 // the carried state `cs`; the plain kernel runs [0, klev) in one go, the
 // persistent kernel (below) runs a column in level segments.
-template <typename real, int PF, bool AER, typename S, typename PT, typename CS>
+template <typename real, int PF, bool AER, typename S, typename PT, typename CS, typename LO>
 __device__ __forceinline__ void kcache_levels(cptr<KArgs<real, S>> ka, cptr<PT> cpar, int b,
-                                              unsigned lo0, int lev0, int lev1, CS& cs) {
+                                              LO lo0, int lev0, int lev1, CS& cs) {
   if (lev0 >= lev1) return;
-  const unsigned lo = lo0;                         // empty segment: no loads at lev0 (may be == klev)
+  const LO lo = lane_here(lo0);                        // empty segment: no loads at lev0 (may be == klev)
   // PF: 0 = loads at the top of their level, 1 = level k+1 prefetched into
   // registers, 2 = like 0, and the neighbour-level values (paph/pmfu/pmfd/plu of
   // k, k+1) re-read every level instead of carried (fewer live registers,
@@ -1184,13 +1224,13 @@ __device__ __forceinline__ void kcache_levels(cptr<KArgs<real, S>> ka, cptr<PT> 
     ncldtop0 = c.ncldtop - 1;
     cc = column_constants(c, A, u1, uh, lo);
     const int l1 = lev0 + 1 < klev ? lev0 + 1 : klev - 1;
-    nb.paph_k = ldg(A.paph, uh + (size_t)lev0 * nproma, lo);
-    nb.paph_n = ldg(A.paph, uh + (size_t)(lev0 + 1) * nproma, lo);
-    nb.pmfu_k = ldg(A.pmfu, u2 + (size_t)lev0 * nproma, lo);
-    nb.pmfd_k = ldg(A.pmfd, u2 + (size_t)lev0 * nproma, lo);
-    nb.pmfu_n = ldg(A.pmfu, u2 + (size_t)l1 * nproma, lo);
-    nb.pmfd_n = ldg(A.pmfd, u2 + (size_t)l1 * nproma, lo);
-    nb.plu_n = ldg(A.plu, u2 + (size_t)l1 * nproma, lo);
+    nb.paph_k = ldg(A.paph, uh + (size_t)lev0 * nproma, lo_half(lo));
+    nb.paph_n = ldg(A.paph, uh + (size_t)(lev0 + 1) * nproma, lo_half(lo));
+    nb.pmfu_k = ldg(A.pmfu, u2 + (size_t)lev0 * nproma, lo_full(lo));
+    nb.pmfd_k = ldg(A.pmfd, u2 + (size_t)lev0 * nproma, lo_full(lo));
+    nb.pmfu_n = ldg(A.pmfu, u2 + (size_t)l1 * nproma, lo_full(lo));
+    nb.pmfd_n = ldg(A.pmfd, u2 + (size_t)l1 * nproma, lo_full(lo));
+    nb.plu_n = ldg(A.plu, u2 + (size_t)l1 * nproma, lo_full(lo));
     if (PFX) load_level<real, AER>(cur, A, u2, u3, lev0, klev, nproma, lo);
     if (PFM) load_early<real>(nxt_e, A, u2, u3, lev0, klev, nproma, lo);
     if (PFA) load_level<real, AER>(nxt, A, u2, u3, lev0, klev, nproma, lo);
@@ -1229,7 +1269,7 @@ __device__ __forceinline__ void kcache_levels(cptr<KArgs<real, S>> ka, cptr<PT> 
     // and so is the lane's 32-bit byte offset: its zero-extension is then formed
     // in this block, where the level loads fold it into the saddr + voffset form
     // instead of a 64-bit VGPR address add per load
-    const unsigned lo = launder_vgpr(lo0);
+    const LO lo = launder_vgpr(lo0);
     const bool physics = k >= ncldtop0;
     // ---- issue the loads of the next levels (software pipelining) ----
     real paph_nn, pmfu_nn, pmfd_nn, plu_nn;
@@ -1247,18 +1287,18 @@ __device__ __forceinline__ void kcache_levels(cptr<KArgs<real, S>> ka, cptr<PT> 
       }
       if (PFX) load_level<real, AER>(nxt, A, u2, u3, k1, klev, nproma, lo);
       if (NBR) {
-        nb.paph_k = ldg(A.paph, uh + (size_t)k * nproma, lo);
-        nb.paph_n = ldg(A.paph, uh + (size_t)(k + 1) * nproma, lo);
+        nb.paph_k = ldg(A.paph, uh + (size_t)k * nproma, lo_half(lo));
+        nb.paph_n = ldg(A.paph, uh + (size_t)(k + 1) * nproma, lo_half(lo));
         const size_t i0 = u2 + (size_t)k * nproma, i1 = u2 + (size_t)k1 * nproma;
-        nb.pmfu_k = ldg(A.pmfu, i0, lo); nb.pmfd_k = ldg(A.pmfd, i0, lo);
-        nb.pmfu_n = ldg(A.pmfu, i1, lo); nb.pmfd_n = ldg(A.pmfd, i1, lo); nb.plu_n = ldg(A.plu, i1, lo);
+        nb.pmfu_k = ldg(A.pmfu, i0, lo_full(lo)); nb.pmfd_k = ldg(A.pmfd, i0, lo_full(lo));
+        nb.pmfu_n = ldg(A.pmfu, i1, lo_full(lo)); nb.pmfd_n = ldg(A.pmfd, i1, lo_full(lo)); nb.plu_n = ldg(A.plu, i1, lo_full(lo));
         paph_nn = pmfu_nn = pmfd_nn = plu_nn = R(0.0);
       } else {
         // read once each (levels k+2 rotate through registers): streaming loads,
         // -0.4 % fp64 / -0.7 % fp32 against cached ones (profiles/r05/experiments_kernel_ab.txt)
-        paph_nn = ldg1(A.paph, uh + (size_t)kh2 * nproma, lo);
+        paph_nn = ldg1(A.paph, uh + (size_t)kh2 * nproma, lo_half(lo));
         const size_t i2 = u2 + (size_t)k2 * nproma;
-        pmfu_nn = ldg1(A.pmfu, i2, lo); pmfd_nn = ldg1(A.pmfd, i2, lo); plu_nn = ldg1(A.plu, i2, lo);
+        pmfu_nn = ldg1(A.pmfu, i2, lo_full(lo)); pmfd_nn = ldg1(A.pmfd, i2, lo_full(lo)); plu_nn = ldg1(A.plu, i2, lo_full(lo));
       }
     }
 
@@ -1299,7 +1339,9 @@ __device__ __forceinline__ void kcache_levels(cptr<KArgs<real, S>> ka, cptr<PT> 
     {
       const KArgs<real, S>& A = *(const KArgs<real, S>*)launder_uniform(ka);
       const auto& c = params_here<PVR>(pv, cpar);
-      const unsigned los = PVR ? launder_vgpr(lo0) : lo;
+      // (packed: a fresh copy as well, so that neither the top-of-level copy nor the
+      // offsets formed from it stay live across the physics)
+      const LO los = PVR || std::is_same<LO, PackLo>::value ? launder_vgpr(lo0) : lo;
       store_level(A, u2, u3, k, klev, nproma, los, physics, ls, po);
       flux_level(c, A, uh + (size_t)(k + 1) * nproma, los, cur, ls, po, nb.paph_k, nb.paph_n, cs);
     }
@@ -1337,6 +1379,55 @@ __device__ __forceinline__ void cloudsc_kcache_body(cptr<KArgs<real, S>> ka, cpt
   }
   kcache_levels<real, PF, AER>(ka, cpar, b, lo, 0, A.klev, cs);
   stg(((const KArgs<real, S>*)launder_uniform(ka))->prainfrac, (size_t)b * A.nproma, lo, cs.rainfrac);
+}
+
+// ===================== narrow blocks packed into full waves =====================
+// NPROMA <= 32: one wave walks pack = 64 / nproma consecutive blocks b0 .. b0 +
+// pack - 1 (a "group").  The memory layout is the reference's; each lane does
+// exactly what the lane of the unpacked kernel serving its column does, so the
+// output bits are the same.  The host passes this as an extra kernel argument
+// (the unpacked kernels' arguments are untouched).
+struct PackArgs {
+  int pack;      // blocks per wave
+  int nblocks;
+  int ngroups;   // ceil(nblocks / pack)
+};
+// Lane l of the wave of group b0 / pack: sub-slot s = l / nproma, column jl = l %
+// nproma of block b0 + s.  Returns whether the lane has a column: an inactive
+// lane (l >= pack * nproma, a block or a column past the end) must issue no load
+// and no store, its addresses may lie beyond the allocations.
+template <typename S>
+__device__ __forceinline__ bool pack_lane(int ngptot, int nproma, int klev, const PackArgs& G, int b0, PackLo& lo,
+                                          unsigned& sub) {
+  const unsigned l = threadIdx.x, np = (unsigned)nproma;
+  const unsigned s = l / np, jl = l - s * np;
+  lo.jb = jl * (unsigned)sizeof(S);
+  lo.sb = s * np * (unsigned)sizeof(S);
+  lo.klev = klev;
+  sub = s;
+  const unsigned b = (unsigned)b0 + s;                 // < nblocks + 64: no wrap
+  // (b * np + jl is evaluated for every lane; where b < nblocks it is below
+  // ngptot + nproma, where not its value is not used)
+  return s < (unsigned)G.pack && b < (unsigned)G.nblocks && b * np + jl < (unsigned)ngptot;
+}
+
+template <typename real, int PF, bool AER, bool LDSC, typename S, typename PT>
+__device__ __forceinline__ void cloudsc_kcache_packed_body(cptr<KArgs<real, S>> ka, cptr<PT> cpar,
+                                                           const PackArgs& G) {
+  const KArgs<real, S>& A = *(const KArgs<real, S>*)ka;
+  const int b0 = (int)blockIdx.x * G.pack;
+  PackLo lo;
+  unsigned sub;
+  if (!pack_lane<S>(A.ngptot, A.nproma, A.klev, G, b0, lo, sub)) return;
+  CarryOf<real, LDSC> cs(carry_lds_base<real>());
+  init_carry<real>(cs);
+  {
+    CLOUDSC_PARAMS_HERE;
+    flux_top(c, A, (size_t)b0 * (A.klev + 1) * A.nproma, lo);
+  }
+  kcache_levels<real, PF, AER>(ka, cpar, b0, lo, 0, A.klev, cs);
+  stg(((const KArgs<real, S>*)launder_uniform(ka))->prainfrac, (size_t)b0 * A.nproma, lo_surf(lane_here(lo)),
+      cs.rainfrac);
 }
 
 // ===================== persistent (work-queue) SCC-k-caching =====================
@@ -1422,12 +1513,16 @@ __device__ __forceinline__ void carry_io(real* st, size_t u, size_t plane, unsig
 #undef CLOUDSC_CARRY_IO
 }
 
-template <typename real, int PF, bool AER, bool LDSC, typename ST, typename PT>
+// PACK: the schedule runs over groups of G.pack blocks instead of blocks (items
+// are (segment, group), stripes are taken over groups, one flag per group: the
+// first G.ngroups words of the flag area); the carried state keeps its layout.
+template <typename real, int PF, bool AER, bool LDSC, bool PACK = false, typename ST, typename PT>
 __device__ __forceinline__ void cloudsc_kcache_persistent_body(cptr<KArgs<real, ST>> ka, cptr<PT> cpar,
-                                                               const PersistArgs<real>& P) {
+                                                               const PersistArgs<real>& P,
+                                                               const PackArgs& G = PackArgs{1, 0, 0}) {
   __shared__ int s_item;
   const KArgs<real, ST>& A = *(const KArgs<real, ST>*)ka;
-  const int nproma = A.nproma, nsub = P.nsub;
+  const int nproma = A.nproma, nsub = PACK ? 1 : P.nsub;
   // Every branch around a barrier is wave-uniform, and visibly so to the
   // compiler (SGPR conditions): the first wave of the workgroup does the
   // dequeue, the polling and the flag store with all of its lanes (same address,
@@ -1440,7 +1535,7 @@ __device__ __forceinline__ void cloudsc_kcache_persistent_body(cptr<KArgs<real, 
   // this workgroup's stripe: blocks b = lb * S + st, lb < nbs (all wave-uniform)
   const int S = P.nstripes;
   const int st = (int)(blockIdx.x % (unsigned)S);
-  const int nbs = (P.nblocks - st + S - 1) / S;
+  const int nbs = ((PACK ? G.ngroups : P.nblocks) - st + S - 1) / S;
   const int nsbs = nbs * nsub;                        // items per segment in the stripe
   const int items = P.nseg * nsbs;
   unsigned* const ctr = P.ctr + st * kKsegCtrStride;
@@ -1461,18 +1556,30 @@ __device__ __forceinline__ void cloudsc_kcache_persistent_body(cptr<KArgs<real, 
     const int seg = item / nsbs, r = item - seg * nsbs;
     const int lb = P.sb_major ? r % nbs : r / nsub;
     const int hh = P.sb_major ? r / nbs : r - lb * nsub;
-    const int b = lb * S + st;
-    const int sb = b * nsub + hh;
+    const int ug = lb * S + st;                        // the block, or the group of blocks
+    const int sb = ug * nsub + hh;
+    const int b = PACK ? ug * G.pack : ug;             // packed: the group's first block
     const int jl = hh * 64 + (int)threadIdx.x;
     // the lane's byte offset in a field plane (storage type) and in a plane of
     // the carried state in the workspace (compute type): one value unless mixed
-    const unsigned lo = (unsigned)jl * (unsigned)sizeof(ST);
-    const unsigned lo_c = (unsigned)jl * (unsigned)sizeof(real);
+    typename std::conditional<PACK, PackLo, unsigned>::type lo;
+    unsigned lo_c;
+    bool active;
+    if constexpr (PACK) {
+      unsigned sub;
+      active = pack_lane<ST>(A.ngptot, nproma, A.klev, G, b, lo, sub);
+      lo = lane_here(lo);
+      // sub-slot `sub` is a whole block of carried state ([kCarryN][nproma]) further on
+      lo_c = (lo.sb * (unsigned)kCarryN + lo.jb) / (unsigned)sizeof(ST) * (unsigned)sizeof(real);
+    } else {
+      lo = (unsigned)jl * (unsigned)sizeof(ST);
+      lo_c = (unsigned)jl * (unsigned)sizeof(real);
+      active = jl < nproma && b * nproma + jl < A.ngptot;
+    }
 #ifdef CLOUDSC_KSEG_TRACE
     const unsigned long long t_start = __builtin_amdgcn_s_memrealtime();
     unsigned long long t_ready = t_start;
 #endif
-    const bool active = jl < nproma && b * nproma + jl < A.ngptot;
     const size_t ust = (size_t)b * kCarryN * nproma;
     CarryOf<real, LDSC> cs(carry_lds_base<real>());
     if (seg == 0) {
@@ -1505,6 +1612,8 @@ __device__ __forceinline__ void cloudsc_kcache_persistent_body(cptr<KArgs<real, 
       if (active) carry_io(P.state, ust, (size_t)nproma, lo_c, cs, false);
     }
     if (active) kcache_levels<real, PF, AER>(ka, cpar, b, lo, P.lev[seg], P.lev[seg + 1], cs);
+    const auto lo_e = lane_here(lo);   // packed: the offsets below formed here, not live across the levels
+    if constexpr (PACK) lo_c = (lo_e.sb * (unsigned)kCarryN + lo_e.jb) / (unsigned)sizeof(ST) * (unsigned)sizeof(real);
     if (seg + 1 < P.nseg) {
       // producer (G16 R1): sc1 payload stores, every wave drains, barrier, the
       // flag stored with an agent atomic
@@ -1513,7 +1622,7 @@ __device__ __forceinline__ void cloudsc_kcache_persistent_body(cptr<KArgs<real, 
       __syncthreads();
       if (wave0) __hip_atomic_store(P.flags + sb, P.stamp + (unsigned)(seg + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     } else if (active) {
-      stg(((const KArgs<real, ST>*)launder_uniform(ka))->prainfrac, (size_t)b * nproma, lo, cs.rainfrac);
+      stg(((const KArgs<real, ST>*)launder_uniform(ka))->prainfrac, (size_t)b * nproma, lo_surf(lo_e), cs.rainfrac);
     }
 #ifdef CLOUDSC_KSEG_TRACE
     const int gitem = seg * P.nblocks * nsub + sb;   // the item's index in the unstriped order

@@ -58,6 +58,7 @@ typedef struct {
   int numomp, ngptot, nproma, ngpus, precision, variant, reps, warmup;
   int transfer, chunk_blocks, nstreams, exact_libm;
   int place;                      /* placement search: 1 on, 0 off, -1 auto (on when reps > 1) */
+  int narrow_pack;                /* NPROMA <= 32 packed into full waves: 1 on, 0 off, -1 the library's default */
   double energy_s;                /* --energy: seconds of back-to-back launches sampled for board power */
   double tol;
   int tol_given;
@@ -114,6 +115,8 @@ static void usage(const char *prog) {
           "  --reps R              timed steps (default 1)\n"
           "  --place on|off|auto   output placement search at state creation (~0.5 s, ~250 kernel\n"
           "                        launches; default auto: on when --reps > 1, off for one step)\n"
+          "  --narrow-pack on|off|auto  kseg, kcache: run blocks of NPROMA <= 32 packed, 64 / NPROMA blocks\n"
+          "                        per wave (same layout, same bits); auto = the measured default per width\n"
           "  --warmup W            untimed steps before the timed ones (default 1)\n"
           "  --energy S            after the timed steps, S seconds of back-to-back launches with the\n"
           "                        device's board power sampled every 10 ms (hwmon power1_input):\n"
@@ -136,7 +139,7 @@ static int parse(int argc, char **argv, options_t *o) {
   memset(o, 0, sizeof(*o));
   o->numomp = 1; o->ngptot = 100; o->nproma = 4;     /* dwarf_cloudsc.c:25-27 defaults */
   o->ngpus = 1; o->precision = CLOUDSC_FP64; o->variant = CLOUDSC_VARIANT_KSEG;
-  o->reps = 1; o->warmup = 1; o->tol = 10.0 * DBL_EPSILON; o->place = -1;
+  o->reps = 1; o->warmup = 1; o->tol = 10.0 * DBL_EPSILON; o->place = -1; o->narrow_pack = -1;
   o->chunk_blocks = 128; o->nstreams = 3;  /* chunk slots; profiles/r04/transfer_sweep_kseg_fp64.txt */
   int npos = 0;
   long pos[3] = {0, 0, 0};
@@ -173,6 +176,13 @@ static int parse(int argc, char **argv, options_t *o) {
       else if (!strcmp(v, "off")) o->place = 0;
       else if (!strcmp(v, "auto")) o->place = -1;
       else { fprintf(stderr, "bad --place %s\n", v); return -1; }
+    }
+    else if (!strcmp(a, "--narrow-pack")) {
+      NEEDV();
+      if (!strcmp(v, "on")) o->narrow_pack = 1;
+      else if (!strcmp(v, "off")) o->narrow_pack = 0;
+      else if (!strcmp(v, "auto")) o->narrow_pack = -1;
+      else { fprintf(stderr, "bad --narrow-pack %s\n", v); return -1; }
     }
     else if (!strcmp(a, "--input")) { NEEDV(); o->input_h5 = v; }
     else if (!strcmp(a, "--reference")) { NEEDV(); o->reference_h5 = v; }
@@ -565,6 +575,7 @@ int main(int argc, char **argv) {
   if (o.ngpus > ndev)
     printf(" CLOUDSC-AMD: %d shards on %d visible device(s): shard d runs on device d %% %d\n", o.ngpus, ndev, ndev);
 
+  cloudsc_debug_set_narrow_pack(o.narrow_pack);
   if (o.precision == CLOUDSC_MIXED &&
       (o.transfer || (o.variant != CLOUDSC_VARIANT_KSEG && o.variant != CLOUDSC_VARIANT_KCACHE))) {
     fprintf(stderr, "dwarf-cloudsc-amd: --precision mixed runs --variant kseg|kcache|cpu (no --transfer)\n");
@@ -587,10 +598,15 @@ int main(int argc, char **argv) {
   cloudsc_io_template(&ds, &tmpl);
   cloudsc_io_reference(&ds, &ref);
   const int nblocks = o.ngptot / o.nproma + (o.ngptot % o.nproma ? 1 : 0);
-  printf(" CLOUDSC-AMD: %s, variant %s, %d device(s); state: %s (KLON=%d, KLEV=%d)\n",
+  /* NPROMA blocks per wave of the launches (1 = unpacked; narrow blocks: --narrow-pack) */
+  cloudsc_launch_geometry_t geo;
+  if (cloudsc_gpu_launch_geometry(o.precision, o.variant, o.ngptot, o.nproma, ds.klev,
+                                  ds.params.laericesed || ds.params.laericeauto, &geo) != CLOUDSC_OK)
+    geo.pack = 1;
+  printf(" CLOUDSC-AMD: %s, variant %s, %d device(s); state: %s (KLON=%d, KLEV=%d); pack=%d\n",
          o.precision == CLOUDSC_FP32 && o.exact_libm ? "fp32 (glibc expf/powf)" : precision_name(o.precision),
          variant_name(o.variant),
-         o.ngpus, ds.source, ds.klon, ds.klev);
+         o.ngpus, ds.source, ds.klon, ds.klev, geo.pack);
 
   /* the placement search costs ~0.5 s of kernel launches per state and saves
    * up to ~15 % per step: worth it for repeated steps, not for one (the

@@ -196,6 +196,12 @@ int cloudsc_gpu_init(int device, const cloudsc_params_t *params);
  * nproma: 1..256 for KCACHE and SCC (one workgroup of nproma threads per
  * block), 1..2^24 for KSEG (64-column sub-blocks; all index arithmetic is
  * 64-bit); otherwise CLOUDSC_EINVAL.
+ * Narrow blocks: KCACHE and KSEG can run blocks of nproma <= 32 packed,
+ * 64 / nproma consecutive blocks per wave, instead of one block per partly
+ * idle wave.  The memory layout, the workspace and the output bits are the
+ * same either way; cloudsc_gpu_launch_geometry reports what a launch would
+ * do, cloudsc_debug_set_narrow_pack overrides the measured default (DESIGN.md
+ * §3.18).
  * A caller-owned KSEG workspace carries a sticky error word (below): zero it,
  * or pass it through cloudsc_gpu_check, before reusing the memory for a new
  * series of launches, or a stale count may surface as CLOUDSC_EHANDOFF. */
@@ -277,6 +283,31 @@ int cloudsc_debug_set_kseg_spin_limit(long long limit);
  * The result bits do not depend on either; the tests use it to exercise the
  * hand-offs with few workgroups and many segments. */
 int cloudsc_debug_set_kseg_schedule(int nseg, int grid);
+
+/* The launch geometry of the physics kernels.  A one-wave work unit is what one
+ * wave computes for one level segment: a 64-column sub-block of a block, or,
+ * packed, `pack` whole blocks of nproma <= 32 columns. */
+typedef struct cloudsc_launch_geometry {
+  int pack;           /* NPROMA blocks per wave (1 = unpacked)              */
+  int lanes;          /* active lanes of a full wave: pack * min(nproma,64) */
+  int units;          /* one-wave work units per level segment              */
+  int workgroups;     /* grid the launch would use                          */
+  int wg_threads;     /* threads per workgroup                              */
+} cloudsc_launch_geometry_t;
+
+/* What cloudsc_gpu_run would launch for these arguments; host arithmetic only, needs no GPU.
+ * laer != 0: the aerosol kernels.  CLOUDSC_EINVAL as cloudsc_gpu_run would return it.
+ * KSEG sizes its grid by the device it runs on: `workgroups` is the grid on an
+ * MI355X (256 compute units, two resident waves per SIMD), or the grid of
+ * cloudsc_debug_set_kseg_schedule, never more than segments x units. */
+int cloudsc_gpu_launch_geometry(int precision, int variant, int ngptot, int nproma, int klev,
+                                int laer, cloudsc_launch_geometry_t *out);
+
+/* Process-wide: 1 pack blocks of nproma <= 32, 0 never, negative = the default
+ * (per width, as measured: DESIGN.md §3.18).  Packing needs every lane offset
+ * to fit 32 bits: a launch with 64 / nproma * 5 * (klev + 1) * nproma * 8 >=
+ * 2^32 runs unpacked whatever the mode.  SCC and SCC_PRIVATE never pack. */
+int cloudsc_debug_set_narrow_pack(int mode);
 
 /* Diagnostic: field placement of the states created after this call.  < 0 (the
  * default): one device allocation per field.  >= 0: all fields of a state in
