@@ -460,6 +460,11 @@ def gpu_lib(path: Optional[str] = None):
                                     C.POINTER(C.c_double)]
     lib.cloudsc_cpu_run_precision.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Params),
                                               C.POINTER(Fields), C.POINTER(C.c_double)]
+    # (device, stream | nthreads), ngptot, klev, then precision, nproma, fields of src and of dst
+    lib.cloudsc_fields_convert.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Fields),
+                                           C.c_int, C.c_int, C.POINTER(Fields)]
+    lib.cloudsc_cpu_fields_convert.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Fields),
+                                               C.c_int, C.c_int, C.POINTER(Fields)]
     lib.cloudsc_debug_set_kseg_spin_limit.argtypes = [C.c_longlong]
     lib.cloudsc_debug_set_kseg_schedule.argtypes = [C.c_int, C.c_int]
     lib.cloudsc_gpu_launch_geometry.argtypes = [C.c_int] * 6 + [C.POINTER(LaunchGeometry)]
@@ -521,6 +526,53 @@ def cpu_run_state(ds: "Dataset", st: "HostState", nthreads: int = 0) -> float:
     check(gpu_lib().cloudsc_cpu_run_precision(nthreads, st.precision, st.ngptot, st.nproma, st.klev, C.byref(p),
                                               C.byref(f), C.byref(secs)))
     return secs.value
+
+
+def fields_subset(f: "Fields", names=None, other: Optional["Fields"] = None) -> "Fields":
+    """A Fields with only `names` copied from f (None: every member f holds -- and `other` holds, if given)."""
+    out = Fields()
+    for n in (ALL_FIELDS if names is None else names):
+        if n not in ALL_FIELDS:
+            raise KeyError("no such field: %s" % n)
+        p = getattr(f, n)
+        if names is None and (not p or (other is not None and not getattr(other, n))):
+            continue
+        setattr(out, n, p)
+    return out
+
+
+def convert_fields(src: "Fields", dst: "Fields", ngptot: int, klev: int, src_precision: int, src_nproma: int,
+                   dst_precision: int, dst_nproma: int, device: int = 0, stream=None) -> None:
+    """cloudsc_fields_convert: copy the members set in both DEVICE field sets into another NPROMA blocking
+    and / or storage type, one kernel launch on `stream` (a hipStream_t value, None = the default stream).
+    Asynchronous: synchronise the stream before reading dst from the host."""
+    check(gpu_lib().cloudsc_fields_convert(device, stream, ngptot, klev, src_precision, src_nproma, C.byref(src),
+                                           dst_precision, dst_nproma, C.byref(dst)))
+
+
+def cpu_convert_fields(src, dst, ngptot: Optional[int] = None, klev: Optional[int] = None,
+                       src_precision: Optional[int] = None, src_nproma: Optional[int] = None,
+                       dst_precision: Optional[int] = None, dst_nproma: Optional[int] = None, names=None,
+                       nthreads: int = 0) -> None:
+    """cloudsc_cpu_fields_convert on host arrays.  src / dst: a HostState (its shape and precision are
+    taken from it, and `names` -- default: the arrays both states hold -- selects the members) or a plain
+    Fields of host pointers (every shape argument is then needed; names must be None)."""
+    def unpack(x, precision, nproma):
+        if isinstance(x, HostState):
+            return x.fields(), x.ngptot, x.klev, x.precision, x.nproma
+        if precision is None or nproma is None:
+            raise ValueError("a plain Fields needs its precision and nproma")
+        return x, ngptot, klev, precision, nproma
+    sf, sn, sk, sp, snp = unpack(src, src_precision, src_nproma)
+    df, dn, dk, dp, dnp = unpack(dst, dst_precision, dst_nproma)
+    n, k = (sn if ngptot is None else ngptot), (sk if klev is None else klev)
+    if n is None or k is None or dn not in (None, n) or dk not in (None, k):
+        raise ValueError("ngptot / klev missing or not the same for src and dst")
+    if isinstance(src, HostState) and isinstance(dst, HostState):
+        sf, df = fields_subset(sf, names, df), fields_subset(df, names, sf)
+    elif names is not None:
+        raise ValueError("names needs two HostStates")
+    check(gpu_lib().cloudsc_cpu_fields_convert(nthreads, n, k, sp, snp, C.byref(sf), dp, dnp, C.byref(df)))
 
 
 def validate_host_state(ds: "Dataset", st: "HostState") -> float:
@@ -851,8 +903,17 @@ class DeviceFields:
             if rc != 0:
                 raise CloudscError("hipMemcpy %s failed (%d)" % (n, rc))
 
-    def download(self, name: str) -> np.ndarray:
-        """One field in block layout as float64."""
+    def convert_to(self, other: "DeviceFields", names=None, stream=None) -> None:
+        """cloudsc_fields_convert of this set into `other` (another blocking and / or precision of the
+        same ngptot and klev, same device): the members in `names`, or every member both sets hold.
+        Asynchronous on `stream` (None = the default stream)."""
+        if (other.ngptot, other.klev, other.device) != (self.ngptot, self.klev, self.device):
+            raise ValueError("convert_to: ngptot, klev and device must be the same")
+        convert_fields(fields_subset(self.f, names, other.f), fields_subset(other.f, names, self.f), self.ngptot,
+                       self.klev, self.precision, self.nproma, other.precision, other.nproma, self.device, stream)
+
+    def download_raw(self, name: str) -> np.ndarray:
+        """One field in block layout in its storage type (after a device synchronise)."""
         self.hip.hipSetDevice(self.device)
         self.hip.hipDeviceSynchronize()
         dt = np.int32 if name == "ktype" else storage_dtype(self.precision)
@@ -861,7 +922,11 @@ class DeviceFields:
         rc = self.hip.hipMemcpy(out.ctypes.data, getattr(self.f, name), out.nbytes, 2)
         if rc != 0:
             raise CloudscError("hipMemcpy %s failed (%d)" % (name, rc))
-        return out.astype(np.float64)
+        return out
+
+    def download(self, name: str) -> np.ndarray:
+        """One field in block layout as float64."""
+        return self.download_raw(name).astype(np.float64)
 
     def close(self) -> None:
         if getattr(self, "f", None) is not None:

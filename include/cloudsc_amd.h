@@ -73,7 +73,8 @@ extern "C" {
  *   out = (float) fp64_kernel( (double) in )
  *
  * with `in` the float fields as stored (a caller holding doubles rounds them
- * to float first) and fp64_kernel the CLOUDSC_FP64 computation -- the
+ * to float first: cloudsc_fields_convert does it on the device, with this same
+ * conversion) and fp64_kernel the CLOUDSC_FP64 computation -- the
  * reference kernel's.  Half the bytes of fp64 per column and per resident
  * state, the accuracy of fp64 arithmetic on float-rounded data (DESIGN.md
  * §3.17).  Parameters, the KSEG workspace and cloudsc_gpu_scratch_bytes are
@@ -259,6 +260,44 @@ int cloudsc_fields_alloc(int device, int precision, int ngptot, int nproma, int 
  * Non-NULL pointers it did not make (on this device) are left alone and make
  * the call return CLOUDSC_EINVAL. */
 int cloudsc_fields_free(int device, cloudsc_fields_t *fields);
+
+/* Copy a field set on `device` into another NPROMA blocking and / or storage
+ * type, asynchronously on `stream` (a hipStream_t, NULL = the default stream),
+ * in one kernel launch.  For every member that is non-NULL in both src and dst,
+ * every row of its kind -- klev (full-level), klev + 1 (half-level),
+ * CLOUDSC_NCLV * klev (species) or 1 (surface) -- and every global column
+ * g < ngptot:
+ *
+ *   dst[g / dst_nproma][row][g % dst_nproma] = (dst type) src[g / src_nproma][row][g % src_nproma]
+ *
+ * The element type follows the precision code as everywhere else: double for
+ * CLOUDSC_FP64, float for CLOUDSC_FP32 and CLOUDSC_MIXED; ktype is always an
+ * int32 copy.  Widening is exact.  Narrowing is one conversion, round to
+ * nearest even with gradual underflow, overflow to infinity, NaN stays NaN: the
+ * conversion of the mixed kernels' stores and of the state's expansion.  Equal
+ * types copy bits.  Lanes jl past the last column of dst's last block are never
+ * written.  dst's input members are `const void *` in the struct and ARE
+ * written here.  A member that is NULL in both sets is skipped, so any subset
+ * converts: the inputs only, the outputs only, one field.
+ * CLOUDSC_EINVAL: a member that is NULL in exactly one of the two sets, no
+ * member to convert, the same pointer for a member in src and dst, an unknown
+ * precision code, ngptot, klev or an NPROMA < 1, an NPROMA > 2^24, a NULL
+ * struct.  Every argument is checked before the first HIP call: a bad argument
+ * is CLOUDSC_EINVAL on a machine without a GPU too.  The buffers of src and dst
+ * must not overlap: only pointer equality is checked.
+ * Never synchronises; returns launch-configuration errors only, asynchronous
+ * faults surface at the caller's sync.  Needs no cloudsc_gpu_init.  Moves about
+ * as many bytes as a physics step (DESIGN.md §3.19 has the measured rates). */
+int cloudsc_fields_convert(int device, void *stream, int ngptot, int klev,
+                           int src_precision, int src_nproma, const cloudsc_fields_t *src,
+                           int dst_precision, int dst_nproma, const cloudsc_fields_t *dst);
+
+/* The same on HOST arrays, on `nthreads` host threads (<= 0: all hardware
+ * threads) taking destination blocks from a shared counter: the same
+ * semantics, conversion and errors.  Needs no GPU. */
+int cloudsc_cpu_fields_convert(int nthreads, int ngptot, int klev,
+                               int src_precision, int src_nproma, const cloudsc_fields_t *src,
+                               int dst_precision, int dst_nproma, const cloudsc_fields_t *dst);
 
 /* Bytes of device scratch a variant needs for (ngptot, nproma, klev, precision); 0 for KCACHE. */
 long long cloudsc_gpu_scratch_bytes(int precision, int variant, int ngptot, int nproma, int klev);
