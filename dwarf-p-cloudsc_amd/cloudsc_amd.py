@@ -176,6 +176,18 @@ class Stats(C.Structure):
                 ("errsum_lo", C.c_double), ("refsum_lo", C.c_double)]
 
 
+class FieldDiff(C.Structure):
+    """cloudsc_field_diff_t: one member of a field set against the same member of another."""
+    _fields_ = [("stats", Stats), ("compared", C.c_longlong), ("mismatches", C.c_longlong),
+                ("first_column", C.c_longlong), ("first_row", C.c_longlong)]
+
+    def to_dict(self) -> dict:
+        s = self.stats
+        return {"stats": (s.minval, s.maxval, s.maxerr, s.errsum, s.refsum, s.errsum_lo, s.refsum_lo),
+                "compared": self.compared, "mismatches": self.mismatches,
+                "first": (self.first_column, self.first_row) if self.mismatches else None}
+
+
 # ---------------------------------------------------------------------------
 # dataset (template) I/O
 # ---------------------------------------------------------------------------
@@ -465,6 +477,19 @@ def gpu_lib(path: Optional[str] = None):
                                            C.c_int, C.c_int, C.POINTER(Fields)]
     lib.cloudsc_cpu_fields_convert.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Fields),
                                                C.c_int, C.c_int, C.POINTER(Fields)]
+    # the same argument order, then one FieldDiff per Fields member
+    lib.cloudsc_fields_compare.argtypes = lib.cloudsc_fields_convert.argtypes + [C.POINTER(FieldDiff)]
+    lib.cloudsc_cpu_fields_compare.argtypes = lib.cloudsc_cpu_fields_convert.argtypes + [C.POINTER(FieldDiff)]
+    lib.cloudsc_fields_validate.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong,
+                                            C.POINTER(Fields), C.POINTER(Reference), C.POINTER(Stats)]
+    lib.cloudsc_fields_expand.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_longlong,
+                                          C.POINTER(Template), C.POINTER(Fields)]
+    lib.cloudsc_fields_diff_sizeof.restype = C.c_longlong
+    lib.cloudsc_fields_compare_release.argtypes = [C.c_int]
+    lib.cloudsc_debug_set_compare_grid.argtypes = [C.c_int]
+    if (lib.cloudsc_fields_diff_sizeof() != C.sizeof(FieldDiff)
+            or lib.cloudsc_fields_members() != len(Fields._fields_)):
+        raise CloudscError("FieldDiff / Fields do not match libcloudsc_amd.so (cloudsc_field_diff_t)")
     lib.cloudsc_debug_set_kseg_spin_limit.argtypes = [C.c_longlong]
     lib.cloudsc_debug_set_kseg_schedule.argtypes = [C.c_int, C.c_int]
     lib.cloudsc_gpu_launch_geometry.argtypes = [C.c_int] * 6 + [C.POINTER(LaunchGeometry)]
@@ -573,6 +598,40 @@ def cpu_convert_fields(src, dst, ngptot: Optional[int] = None, klev: Optional[in
     elif names is not None:
         raise ValueError("names needs two HostStates")
     check(gpu_lib().cloudsc_cpu_fields_convert(nthreads, n, k, sp, snp, C.byref(sf), dp, dnp, C.byref(df)))
+
+
+def _diffs_to_dict(diffs) -> Dict[str, dict]:
+    return {n: d.to_dict() for n, d in zip(ALL_FIELDS, diffs) if d.compared}
+
+
+def compare_fields(a: "Fields", b: "Fields", ngptot: int, klev: int, a_precision: int, a_nproma: int,
+                   b_precision: int, b_nproma: int, device: int = 0, stream=None) -> Dict[str, dict]:
+    """cloudsc_fields_compare: the members set in both DEVICE field sets, a against b as the reference, in
+    one streaming pass on `stream` (waits for that stream).  {member: {"stats": the 7-tuple of
+    GpuState.validate, "compared", "mismatches" (elements that differ as bits), "first": (global column,
+    row) of the first mismatch or None}} for the members compared."""
+    diffs = (FieldDiff * len(ALL_FIELDS))()
+    check(gpu_lib().cloudsc_fields_compare(device, stream, ngptot, klev, a_precision, a_nproma, C.byref(a),
+                                           b_precision, b_nproma, C.byref(b), diffs))
+    return _diffs_to_dict(diffs)
+
+
+def cpu_compare_fields(a: "HostState", b: "HostState", names=None, nthreads: int = 0) -> Dict[str, dict]:
+    """cloudsc_cpu_fields_compare on two HostStates of the same ngptot and klev (any two blockings and
+    precisions): the members in `names`, or every array both hold.  Same result shape as compare_fields."""
+    if (a.ngptot, a.klev) != (b.ngptot, b.klev):
+        raise ValueError("cpu_compare_fields: ngptot and klev must be the same")
+    fa, fb = a.fields(), b.fields()
+    fa, fb = fields_subset(fa, names, fb), fields_subset(fb, names, fa)
+    diffs = (FieldDiff * len(ALL_FIELDS))()
+    check(gpu_lib().cloudsc_cpu_fields_compare(nthreads, a.ngptot, a.klev, a.precision, a.nproma, C.byref(fa),
+                                               b.precision, b.nproma, C.byref(fb), diffs))
+    return _diffs_to_dict(diffs)
+
+
+def compare_grid(workgroups: int = 0) -> None:
+    """Diagnostic: workgroups of the comparison kernel (0 = default); only the sums' low parts may change."""
+    check(gpu_lib().cloudsc_debug_set_compare_grid(workgroups))
 
 
 def validate_host_state(ds: "Dataset", st: "HostState") -> float:
@@ -911,6 +970,36 @@ class DeviceFields:
             raise ValueError("convert_to: ngptot, klev and device must be the same")
         convert_fields(fields_subset(self.f, names, other.f), fields_subset(other.f, names, self.f), self.ngptot,
                        self.klev, self.precision, self.nproma, other.precision, other.nproma, self.device, stream)
+
+    def compare(self, other: "DeviceFields", names=None, stream=None) -> Dict[str, dict]:
+        """cloudsc_fields_compare of this set against `other` as the reference (another blocking and / or
+        precision of the same ngptot and klev, same device): the members in `names`, or every member both
+        sets hold.  See compare_fields for the result."""
+        if (other.ngptot, other.klev, other.device) != (self.ngptot, self.klev, self.device):
+            raise ValueError("compare: ngptot, klev and device must be the same")
+        return compare_fields(fields_subset(self.f, names, other.f), fields_subset(other.f, names, self.f),
+                              self.ngptot, self.klev, self.precision, self.nproma, other.precision, other.nproma,
+                              self.device, stream)
+
+    def validate(self, ds: "Dataset", col_offset: int = 0, stream=None) -> list:
+        """cloudsc_fields_validate: the 21 validated fields against ds.reference on the device; the list
+        of 7-tuples GpuState.validate returns."""
+        keep: list = []
+        ref = make_reference(ds, keep)
+        st = (Stats * 21)()
+        check(self.lib.cloudsc_fields_validate(self.device, stream, self.precision, self.ngptot, self.nproma,
+                                               self.klev, col_offset, C.byref(self.f), C.byref(ref), st))
+        return [(s.minval, s.maxval, s.maxerr, s.errsum, s.refsum, s.errsum_lo, s.refsum_lo) for s in st]
+
+    def expand(self, ds: "Dataset", col_offset: int = 0, stream=None) -> None:
+        """cloudsc_fields_expand: fill every input member this set holds (plude included) from the
+        dataset's template on the device.  Asynchronous on `stream` (None = the default stream)."""
+        if ds.klev != self.klev:
+            raise ValueError("expand: the dataset's klev is not this set's")
+        keep: list = []
+        tmpl = make_template(ds, keep)
+        check(self.lib.cloudsc_fields_expand(self.device, stream, self.precision, self.ngptot, self.nproma,
+                                             col_offset, C.byref(tmpl), C.byref(self.f)))
 
     def download_raw(self, name: str) -> np.ndarray:
         """One field in block layout in its storage type (after a device synchronise)."""

@@ -151,6 +151,27 @@ size_t search_transient_bytes(size_t set_bytes, int n, int sets);
 // copy ceiling on the pipelines' engine pair (cloudsc_pipeline.hip)
 int pcie_engine_gbps(int device, size_t nb, int reps, double* h2d, double* d2h, double* both);
 
+// ---------------------------------------------------------------------------
+// plumbing shared by cloudsc_state.hip and cloudsc_compare.hip
+// ---------------------------------------------------------------------------
+// Double-double accumulation of non-negative terms (Knuth's TwoSum, then a
+// renormalisation): hi + lo carries the sum to ~100 bits, so partial sums
+// combined in any grouping -- NPROMA blocks here, shards or ranks on the host --
+// round to the same double unless the exact sum lies within ~2^-100 of a
+// rounding midpoint.  No FMA contraction applies (-ffp-contract=off),
+// and nothing here is reassociated (no fast-math).
+struct DD {
+  double hi, lo;
+};
+__host__ __device__ __forceinline__ DD dd_add(DD a, DD b) {
+  const double s = a.hi + b.hi;
+  const double bb = s - a.hi;
+  const double e = (a.hi - (s - bb)) + (b.hi - bb);   // TwoSum error of a.hi + b.hi
+  const double t = e + (a.lo + b.lo);
+  const double hi = s + t;
+  return {hi, t - (hi - s)};                          // FastTwoSum renormalisation
+}
+
 }  // namespace cloudsc_impl
 
 #define HIPCHK(call)                                                \

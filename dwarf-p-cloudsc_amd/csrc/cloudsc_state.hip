@@ -39,23 +39,7 @@ __global__ void expand_kernel(T* __restrict__ dst, const S* __restrict__ src, in
   }
 }
 
-// Double-double accumulation of non-negative terms (Knuth's TwoSum, then a
-// renormalisation): hi + lo carries the sum to ~100 bits, so partial sums
-// combined in any grouping -- NPROMA blocks here, shards or ranks on the host --
-// round to the same double unless the exact sum lies within ~2^-100 of a
-// rounding midpoint.  No FMA contraction applies (-ffp-contract=off),
-// and nothing here is reassociated (no fast-math).
-struct DD {
-  double hi, lo;
-};
-__host__ __device__ __forceinline__ DD dd_add(DD a, DD b) {
-  const double s = a.hi + b.hi;
-  const double bb = s - a.hi;
-  const double e = (a.hi - (s - bb)) + (b.hi - bb);   // TwoSum error of a.hi + b.hi
-  const double t = e + (a.lo + b.lo);
-  const double hi = s + t;
-  return {hi, t - (hi - s)};                          // FastTwoSum renormalisation
-}
+// DD and dd_add are in cloudsc_internal.h (shared with cloudsc_compare.hip)
 
 // One workgroup per NPROMA block: min/max of the field, max|d|, sum|d|, sum|ref|
 // over the active lanes of that block (validate_mod.F90:136-146, with fabs);

@@ -57,6 +57,7 @@
 typedef struct {
   int numomp, ngptot, nproma, ngpus, precision, variant, reps, warmup;
   int transfer, chunk_blocks, nstreams, exact_libm;
+  int fields_caller;              /* --fields caller: caller-owned field sets instead of a state */
   int place;                      /* placement search: 1 on, 0 off, -1 auto (on when reps > 1) */
   int narrow_pack;                /* NPROMA <= 32 packed into full waves: 1 on, 0 off, -1 the library's default */
   double energy_s;                /* --energy: seconds of back-to-back launches sampled for board power */
@@ -68,6 +69,7 @@ typedef struct {
 typedef struct {
   int device, ngptot, nproma, precision, variant, reps, warmup;
   int libm_bit;                   /* CLOUDSC_FP32_EXACT_LIBM or 0 */
+  int caller, place_on, aerosols; /* --fields caller; its placement search; aerosol inputs allocated */
   double energy_s;
   long long col_offset;
   const cloudsc_template_t *tmpl;
@@ -126,6 +128,10 @@ static void usage(const char *prog) {
           "  --data DIR            raw dataset directory (default $CLOUDSC_DATA or the\n"
           "                        repository's data/cloudsc100)\n"
           "  --tol X               relative L1 gate per field (default 10*eps = 2.2e-15 for fp64)\n"
+          "  --fields state|caller state (default): the device-resident state API; caller: the reference\n"
+          "                        CUDA driver's shape on caller-owned device fields, per shard\n"
+          "                        cloudsc_fields_alloc, _expand, cloudsc_gpu_run, cloudsc_gpu_check,\n"
+          "                        cloudsc_fields_validate (not with --transfer or --variant cpu)\n"
           "  --transfer            host-buffer path: block-layout arrays in host memory,\n"
           "                        H2D -> kernel -> D2H per chunk, overlapped on streams\n"
           "                        (TOTAL includes the transfers, like cloudsc_driver.cu)\n"
@@ -190,6 +196,12 @@ static int parse(int argc, char **argv, options_t *o) {
     else if (!strcmp(a, "--tol")) { NEEDV(); o->tol = atof(v); o->tol_given = 1; }
     else if (!strcmp(a, "--write-h5")) { NEEDV(); o->write_h5_dir = v; }
     else if (!strcmp(a, "--transfer")) o->transfer = 1;
+    else if (!strcmp(a, "--fields")) {
+      NEEDV();
+      if (!strcmp(v, "state")) o->fields_caller = 0;
+      else if (!strcmp(v, "caller")) o->fields_caller = 1;
+      else { fprintf(stderr, "bad --fields %s\n", v); return -1; }
+    }
     else if (!strcmp(a, "--fp32-exact-libm")) o->exact_libm = 1;
     else if (!strcmp(a, "--chunk")) { NEEDV(); o->chunk_blocks = atoi(v); }
     else if (!strcmp(a, "--streams")) { NEEDV(); o->nstreams = atoi(v); }
@@ -323,8 +335,67 @@ static int energy_window(shard_t *s, cloudsc_gpu_state_t *st) {
   return rc;
 }
 
+/* ---- --fields caller: the reference CUDA driver's shape (cloudsc_driver.cu:276-447) on caller-owned
+ * device fields: allocate, expand the template on the device, launch, check, validate on the device.
+ * The KSEG / SCC workspace is the caller's too: hipMalloc from the HIP runtime the library has loaded. ---- */
+static void *hip_sym(const char *name) {
+  void *hip = dlopen("libamdhip64.so", RTLD_NOW | RTLD_NOLOAD);
+  if (!hip) hip = dlopen("libamdhip64.so", RTLD_NOW);
+  return hip ? dlsym(hip, name) : NULL;
+}
+
+static void shard_caller(shard_t *s) {
+  int (*set_device)(int) = (int (*)(int))hip_sym("hipSetDevice");
+  int (*dmalloc)(void **, size_t) = (int (*)(void **, size_t))hip_sym("hipMalloc");
+  int (*dmemset)(void *, int, size_t) = (int (*)(void *, int, size_t))hip_sym("hipMemset");
+  int (*dfree)(void *) = (int (*)(void *))hip_sym("hipFree");
+  const int klev = s->tmpl->klev, variant = s->variant | s->libm_bit;
+  cloudsc_fields_t f, plude;
+  memset(&f, 0, sizeof(f));
+  memset(&plude, 0, sizeof(plude));
+  void *ws = NULL;
+  s->rc = set_device && dmalloc && dmemset && dfree ? CLOUDSC_OK : CLOUDSC_EHIP;
+  if (!s->rc)
+    s->rc = cloudsc_fields_alloc(s->device, s->precision, s->ngptot, s->nproma, klev,
+                                 (s->place_on ? 0 : CLOUDSC_PLACE_NONE) | (s->aerosols ? CLOUDSC_ALLOC_AEROSOLS : 0), &f,
+                                 &s->place);
+  if (!s->rc) s->rc = cloudsc_fields_expand(s->device, NULL, s->precision, s->ngptot, s->nproma, s->col_offset, s->tmpl, &f);
+  const long long wsb = cloudsc_gpu_scratch_bytes(s->precision, s->variant, s->ngptot, s->nproma, klev);
+  if (!s->rc && wsb < 0) s->rc = CLOUDSC_EINVAL;
+  if (!s->rc && wsb > 0 && (set_device(s->device) || dmalloc(&ws, (size_t)wsb) || dmemset(ws, 0, 256))) s->rc = CLOUDSC_ENOMEM;
+  plude.plude = f.plude;
+  /* plude is INOUT: expanded again before every step, outside the timing */
+  for (int r = 0; r < s->warmup && !s->rc; r++) {
+    if (r) s->rc = cloudsc_fields_expand(s->device, NULL, s->precision, s->ngptot, s->nproma, s->col_offset, s->tmpl, &plude);
+    if (!s->rc) s->rc = cloudsc_gpu_run(s->device, NULL, s->precision, variant, s->ngptot, s->nproma, klev, &f, ws);
+    if (!s->rc) s->rc = cloudsc_gpu_check(s->device, NULL, s->variant, ws);
+  }
+  pthread_barrier_wait(s->barrier);
+  s->t_start = now();
+  double timed = 0.0;
+  for (int r = 0; r < s->reps && !s->rc; r++) {
+    if (r || s->warmup)
+      s->rc = cloudsc_fields_expand(s->device, NULL, s->precision, s->ngptot, s->nproma, s->col_offset, s->tmpl, &plude);
+    if (!s->rc) s->rc = cloudsc_gpu_check(s->device, NULL, CLOUDSC_VARIANT_KCACHE, NULL);   /* the expansion is done */
+    const double k0 = now();
+    if (!s->rc) s->rc = cloudsc_gpu_run(s->device, NULL, s->precision, variant, s->ngptot, s->nproma, klev, &f, ws);
+    if (!s->rc) s->rc = cloudsc_gpu_check(s->device, NULL, s->variant, ws);
+    s->kernel_ms[r] = (float)(1e3 * (now() - k0));   /* launch to the check's return, on the host clock */
+    timed += now() - k0;
+  }
+  s->t_end = s->t_start + timed;
+  pthread_barrier_wait(s->barrier);
+  if (!s->rc && s->ref)
+    s->rc = cloudsc_fields_validate(s->device, NULL, s->precision, s->ngptot, s->nproma, klev, s->col_offset, &f, s->ref,
+                                    s->stats);
+  if (s->rc) snprintf(s->err, sizeof(s->err), "%s", cloudsc_last_hip_error());
+  if (ws) dfree(ws);
+  cloudsc_fields_free(s->device, &f);
+}
+
 static void *shard_main(void *arg) {
   shard_t *s = (shard_t *)arg;
+  if (s->caller) { shard_caller(s); return NULL; }
   cloudsc_gpu_state_t *st = NULL;
   s->rc = cloudsc_state_create(&st, s->device, s->precision, s->ngptot, s->nproma, s->col_offset, s->tmpl,
                                s->params);
@@ -552,6 +623,12 @@ int main(int argc, char **argv) {
     return rc ? EXIT_FAILURE : EXIT_SUCCESS;
   }
 
+  if (o.fields_caller && (o.transfer || o.variant == VARIANT_CPU)) {
+    fprintf(stderr, "dwarf-cloudsc-amd: --fields caller runs the GPU variants on device fields (no --transfer, no "
+                    "--variant cpu)\n");
+    cloudsc_io_free(&ds);
+    return EXIT_FAILURE;
+  }
   if (o.variant == VARIANT_CPU) {
     if (o.precision == CLOUDSC_FP32 || o.ngpus != 1 || o.transfer) {
       fprintf(stderr, "dwarf-cloudsc-amd: --variant cpu runs fp64 or mixed on the host (no --gpus/--transfer/fp32)\n");
@@ -632,6 +709,8 @@ int main(int argc, char **argv) {
     s->precision = o.precision; s->variant = o.variant; s->reps = o.reps; s->warmup = o.warmup;
     s->libm_bit = o.exact_libm ? CLOUDSC_FP32_EXACT_LIBM : 0;
     s->energy_s = o.energy_s;
+    s->caller = o.fields_caller; s->place_on = place;
+    s->aerosols = ds.params.laericesed || ds.params.laericeauto;
     s->tmpl = &tmpl; s->params = &ds.params; s->ref = ds.has_reference ? &ref : NULL; s->barrier = &bar;
     s->kernel_ms = (float *)calloc((size_t)o.reps, sizeof(float));
     col += cols;
@@ -640,6 +719,13 @@ int main(int argc, char **argv) {
     pthread_barrier_destroy(&bar);
     pthread_barrier_init(&bar, NULL, (unsigned)nused);
   }
+  /* --fields caller launches with the devices' default parameter sets (cloudsc_gpu_run) */
+  for (int d = 0; d < nused && d < ndev && o.fields_caller; d++)
+    if ((rc = cloudsc_gpu_init(sh[d].device, &ds.params))) {
+      fprintf(stderr, "dwarf-cloudsc-amd: cloudsc_gpu_init: %s (%s)\n", cloudsc_strerror(rc), cloudsc_last_hip_error());
+      cloudsc_io_free(&ds);
+      return EXIT_FAILURE;
+    }
   for (int d = 0; d < nused; d++) pthread_create(&th[d], NULL, shard_main, &sh[d]);
   for (int d = 0; d < nused; d++) pthread_join(th[d], NULL);
   pthread_barrier_destroy(&bar);
@@ -697,12 +783,14 @@ int main(int argc, char **argv) {
       printf(" PLACEMENT: shard=%d search=off\n", d);
       continue;
     }
-    printf(" PLACEMENT: shard=%d search=kernel first_ms=%.4f kept_ms=%.4f tries=%d moves=%d launches=%d "
-           "search_ms=%.1f peak_transient_MB=%.1f\n", d, pl->probe_first_ms, pl->probe_final_ms, pl->tries,
+    printf(" PLACEMENT: shard=%d search=%s first_ms=%.4f kept_ms=%.4f tries=%d moves=%d launches=%d "
+           "search_ms=%.1f peak_transient_MB=%.1f\n", d,
+           pl->method == CLOUDSC_PLACE_METHOD_KERNEL ? "kernel" : "rw-probe", pl->probe_first_ms, pl->probe_final_ms, pl->tries,
            pl->moves, pl->launches, pl->search_ms, pl->peak_transient_bytes / 1048576.0);
   }
   /* board power over the energy window (--energy): uJ per column = W x ms per launch / columns */
-  for (int d = 0; d < nused && o.energy_s > 0.0; d++) {
+  if (o.energy_s > 0.0 && o.fields_caller) printf(" ENERGY: n/a (--fields caller has no energy window)\n");
+  for (int d = 0; d < nused && o.energy_s > 0.0 && !o.fields_caller; d++) {
     if (!sh[d].power_path[0] || !sh[d].power_samples) {
       printf(" ENERGY: shard=%d device=%d n/a (no hwmon power file for this device)\n", d, sh[d].device);
       continue;

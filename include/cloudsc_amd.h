@@ -396,7 +396,8 @@ int cloudsc_pcie_gbps(int device, long long bytes, int reps, double *h2d, double
 int cloudsc_debug_stream_probe(int device, int mode, int width, long long bytes, int reps, double *ms);
 
 /* ABI introspection for bindings: sizeof of the public structs
- * (0 params, 1 fields, 2 template, 3 reference, 4 stats), -1 otherwise. */
+ * (0 params, 1 fields, 2 template, 3 reference, 4 stats), -1 otherwise.
+ * Later structs report their own size: cloudsc_fields_diff_sizeof. */
 long long cloudsc_abi_sizeof(int which);
 
 /* ------------------------------------------------------------------------ */
@@ -637,6 +638,116 @@ int cloudsc_state_download(cloudsc_gpu_state_t *state, int field_id, double *hos
 long long cloudsc_state_field_elems(const cloudsc_gpu_state_t *state, int field_id);
 
 int cloudsc_state_destroy(cloudsc_gpu_state_t *state);
+
+/* ------------------------------------------------------------------------ */
+/* Caller-owned field sets on the device: fill, validate, compare            */
+/* ------------------------------------------------------------------------ */
+/* The reference CUDA driver's shape (cloudsc_driver.cu:276-447) without a host
+ * copy of any field: cloudsc_fields_alloc, cloudsc_fields_expand,
+ * cloudsc_gpu_run, cloudsc_gpu_check, cloudsc_fields_validate -- and
+ * cloudsc_fields_compare to hold two such sets against each other.
+ * compare, validate and expand share one workspace per device (the partial
+ * results, the uploaded reference or template), allocated on first use, grown
+ * on demand, guarded by a mutex: calls on one device serialise.  Only the
+ * first call on a device and a call that grows the workspace synchronise the
+ * whole device; cloudsc_fields_compare_release frees it.  None of them needs
+ * cloudsc_gpu_init. */
+
+/* What cloudsc_fields_compare reports for one cloudsc_fields_t member. */
+typedef struct cloudsc_field_diff {
+  cloudsc_stats_t stats;              /* a against b as the reference                         */
+  long long compared;                 /* elements compared: rows x ngptot; 0 = member skipped */
+  long long mismatches;               /* elements that differ as bits                         */
+  long long first_column, first_row;  /* the first mismatch, -1 / -1 if none                  */
+} cloudsc_field_diff_t;
+
+/* Number of cloudsc_fields_t members (the length of diff[] below) and
+ * sizeof(cloudsc_field_diff_t), for bindings. */
+int cloudsc_fields_members(void);
+long long cloudsc_fields_diff_sizeof(void);
+
+/* Compare two field sets on `device`, in any two NPROMA blockings and storage
+ * types, in one streaming pass that reads every element once and writes none.
+ * For every member that is non-NULL in both sets, every row of its kind and
+ * every global column g < ngptot, with v the element of a and r the element of
+ * b, both widened to double (exact; ktype is compared as int32):
+ *   stats    min v, max v (fmin / fmax), max |v - r|, sum |v - r|, sum |r| --
+ *            the ERROR_PRINT inputs with b as the reference, the sums as
+ *            double-doubles (cloudsc_stats_t)
+ *   mismatches  elements that differ AS BITS: the raw words when both sets have
+ *            the same storage type, otherwise the 64-bit words after widening
+ *            the float.  +0 against -0 counts (with |v - r| = 0); NaN against
+ *            the same NaN word does not.  A NaN in an active lane makes the
+ *            sums NaN; min, max and max |v - r| skip it.
+ *   first_column / first_row  the mismatch with the smallest global column
+ *            and, in that column, the smallest row.
+ * diff[] has one record per cloudsc_fields_t member, in member order
+ * (cloudsc_fields_members()).  A member that is NULL in both sets is skipped:
+ * compared = 0, -1 / -1, stats = {DBL_MAX, -DBL_MAX, 0, ...}.  min, max,
+ * max |v - r|, the counts and the first mismatch do not depend on the launch
+ * grid or on either NPROMA; the sums depend on the grouping only within the
+ * double-double bound stated at cloudsc_stats_t.  Padding lanes of a last
+ * partial block are never read.
+ * CLOUDSC_EINVAL: a member that is NULL in exactly one set, no member in both,
+ * an unknown precision code, ngptot, klev or an NPROMA < 1, an NPROMA > 2^24,
+ * a NULL struct or diff.  The same pointer on both sides is allowed (nothing
+ * is written).  Every argument is checked before the first HIP call: a bad
+ * argument is CLOUDSC_EINVAL on a machine without a GPU too.
+ * Enqueues on `stream` (a hipStream_t, NULL = the default stream), waits for
+ * THAT STREAM ONLY and then writes diff[]. */
+int cloudsc_fields_compare(int device, void *stream, int ngptot, int klev,
+                           int a_precision, int a_nproma, const cloudsc_fields_t *a,
+                           int b_precision, int b_nproma, const cloudsc_fields_t *b,
+                           cloudsc_field_diff_t *diff);
+
+/* The same on HOST arrays, on `nthreads` host threads (<= 0: all hardware
+ * threads) taking blocks of a from a shared counter, the threads' records
+ * combined in thread order: the same semantics and errors.  Needs no GPU. */
+int cloudsc_cpu_fields_compare(int nthreads, int ngptot, int klev,
+                               int a_precision, int a_nproma, const cloudsc_fields_t *a,
+                               int b_precision, int b_nproma, const cloudsc_fields_t *b,
+                               cloudsc_field_diff_t *diff);
+
+/* cloudsc_state_validate for a caller-owned set: the 21 validated members of
+ * `fields` (all must be set) against the KLON-column reference, read as
+ * ref[row][(col_offset + g) % klon] -- the comparison kernel with the
+ * reference as its second operand.  The reference arrays are uploaded on
+ * `stream`, ordered before the one launch; the call waits for that stream only
+ * and writes stats[CLOUDSC_NVALID] in cloudsc_field_id order.  CLOUDSC_EINVAL:
+ * a NULL argument, validated member or reference array, an unknown precision,
+ * a size < 1, nproma > 2^24, col_offset < 0, ref->klev != klev, ref->klon < 1
+ * (checked before the first HIP call). */
+int cloudsc_fields_validate(int device, void *stream, int precision, int ngptot, int nproma, int klev,
+                            long long col_offset, const cloudsc_fields_t *fields,
+                            const cloudsc_reference_t *ref, cloudsc_stats_t *stats);
+
+/* cloudsc_state_create's expansion for a caller-owned set: fills every
+ * non-NULL INPUT member of `fields` (aerosol inputs and plude included; the
+ * outputs are left alone) from the host template,
+ *   dst[b][row][i] = (storage type) tmpl[row][(col_offset + b * nproma + i) % klon]
+ * for the columns b * nproma + i < ngptot: padding lanes of a last partial
+ * block are never written.  klev is the template's.  A member to fill whose
+ * template array is NULL, no member to fill, col_offset < 0, an unknown
+ * precision or a bad size: CLOUDSC_EINVAL before the first HIP call.
+ * Asynchronous on `stream`: the template arrays are copied into the library's
+ * pinned staging buffer before the call returns, so the caller may change or
+ * free them at once; the fields are filled in stream order (synchronise
+ * `stream`, or enqueue the consumer on it).  The call itself never waits for
+ * `stream`; the next compare / validate / expand call on this device first
+ * waits for this expansion's kernel, which still reads the staged template. */
+int cloudsc_fields_expand(int device, void *stream, int precision, int ngptot, int nproma,
+                          long long col_offset, const cloudsc_template_t *tmpl, const cloudsc_fields_t *fields);
+
+/* Free the device's compare / validate / expand workspace (after waiting for a
+ * pending expansion); the next such call allocates it again. */
+int cloudsc_fields_compare_release(int device);
+
+/* Diagnostic: the grid of the comparison kernel (cloudsc_fields_compare and
+ * cloudsc_fields_validate), process-wide: `workgroups` 256-thread workgroups,
+ * 0 = the default, eight per compute unit (never more than there are work
+ * items).  Negative or > 65536: CLOUDSC_EINVAL.  Only the low parts of the sums
+ * may depend on it; the tests run the same comparison on 1 and 3 workgroups. */
+int cloudsc_debug_set_compare_grid(int workgroups);
 
 /* ------------------------------------------------------------------------ */
 /* Host-buffer pipeline: the reference GPU drivers' H2D -> kernel -> D2H      */
