@@ -478,6 +478,13 @@ def gpu_lib(path: Optional[str] = None):
     lib.cloudsc_cpu_fields_convert.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Fields),
                                                C.c_int, C.c_int, C.POINTER(Fields)]
     # the same argument order, then one FieldDiff per Fields member
+    lib.cloudsc_tendbuf_bind.argtypes = [C.POINTER(Fields), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    lib.cloudsc_gpu_run_tendbuf.argtypes = [C.c_int, C.c_void_p] + [C.c_int] * 6 + [C.POINTER(Fields), C.c_void_p]
+    lib.cloudsc_cpu_run_tendbuf.argtypes = [C.c_int] * 6 + [C.POINTER(Params), C.POINTER(Fields)]
+    lib.cloudsc_fields_convert_tendbuf.argtypes = [C.c_int, C.c_void_p] + [C.c_int] * 5 + [C.POINTER(Fields)] + \
+        [C.c_int] * 3 + [C.POINTER(Fields)]
+    lib.cloudsc_cpu_fields_convert_tendbuf.argtypes = [C.c_int] * 6 + [C.POINTER(Fields)] + [C.c_int] * 3 + \
+        [C.POINTER(Fields)]
     lib.cloudsc_fields_compare.argtypes = lib.cloudsc_fields_convert.argtypes + [C.POINTER(FieldDiff)]
     lib.cloudsc_cpu_fields_compare.argtypes = lib.cloudsc_cpu_fields_convert.argtypes + [C.POINTER(FieldDiff)]
     lib.cloudsc_fields_validate.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong,
@@ -598,6 +605,55 @@ def cpu_convert_fields(src, dst, ngptot: Optional[int] = None, klev: Optional[in
     elif names is not None:
         raise ValueError("names needs two HostStates")
     check(gpu_lib().cloudsc_cpu_fields_convert(nthreads, n, k, sp, snp, C.byref(sf), dp, dnp, C.byref(df)))
+
+
+# Packed tendency buffers (the reference's Fortran drivers' BUFFER_TMP / BUFFER_LOC, include/cloudsc_amd.h):
+# [nblocks][tend_planes][klev][nproma], the reference's plane order T, A, Q, CLD(1..5)
+TENDBUF_PLANES_MIN, TENDBUF_PLANES_MAX = 8, 64
+TENDBUF_T, TENDBUF_A, TENDBUF_Q, TENDBUF_CLD = 0, 1, 2, 3
+TENDENCY_FIELDS = tuple(n for n in ALL_FIELDS if n.startswith("tendency_"))
+
+
+def bind_tendbuf(f: "Fields", precision: int, nproma: int, klev: int, buffer_tmp: int, buffer_loc: int) -> None:
+    """cloudsc_tendbuf_bind: the eight tendency members of f = the plane starts of the two buffers (host or
+    device addresses) in the reference's plane order."""
+    check(gpu_lib().cloudsc_tendbuf_bind(C.byref(f), precision, nproma, klev, buffer_tmp, buffer_loc))
+
+
+def gpu_run_tendbuf(f: "Fields", precision: int, variant: int, ngptot: int, nproma: int, klev: int,
+                    tend_planes: int, scratch=None, device: int = 0, stream=None) -> None:
+    """cloudsc_gpu_run_tendbuf: one step on DEVICE fields whose tendency members are planes of packed
+    buffers of tend_planes planes per block.  Asynchronous on `stream`; KSEG callers follow it with
+    cloudsc_gpu_check."""
+    check(gpu_lib().cloudsc_gpu_run_tendbuf(device, stream, precision, variant, ngptot, nproma, klev, tend_planes,
+                                            C.byref(f), scratch))
+
+
+def cpu_run_tendbuf(params: "Params", f: "Fields", precision: int, ngptot: int, nproma: int, klev: int,
+                    tend_planes: int, nthreads: int = 0) -> None:
+    """cloudsc_cpu_run_tendbuf: the CPU variant on HOST fields whose tendency members are planes of packed
+    buffers (precision FP64 or MIXED)."""
+    check(gpu_lib().cloudsc_cpu_run_tendbuf(nthreads, precision, ngptot, nproma, klev, tend_planes, C.byref(params),
+                                            C.byref(f)))
+
+
+def convert_fields_tendbuf(src: "Fields", dst: "Fields", ngptot: int, klev: int, src_precision: int,
+                           src_nproma: int, src_tend_planes: int, dst_precision: int, dst_nproma: int,
+                           dst_tend_planes: int, device: int = 0, stream=None) -> None:
+    """cloudsc_fields_convert_tendbuf: convert_fields with the tendency members of src and / or dst in packed
+    buffers (*_tend_planes planes per block, 0 = separate arrays): pack, unpack or re-pack in one launch."""
+    check(gpu_lib().cloudsc_fields_convert_tendbuf(device, stream, ngptot, klev, src_precision, src_nproma,
+                                                   src_tend_planes, C.byref(src), dst_precision, dst_nproma,
+                                                   dst_tend_planes, C.byref(dst)))
+
+
+def cpu_convert_fields_tendbuf(src: "Fields", dst: "Fields", ngptot: int, klev: int, src_precision: int,
+                               src_nproma: int, src_tend_planes: int, dst_precision: int, dst_nproma: int,
+                               dst_tend_planes: int, nthreads: int = 0) -> None:
+    """cloudsc_cpu_fields_convert_tendbuf: the same on HOST arrays."""
+    check(gpu_lib().cloudsc_cpu_fields_convert_tendbuf(nthreads, ngptot, klev, src_precision, src_nproma,
+                                                       src_tend_planes, C.byref(src), dst_precision, dst_nproma,
+                                                       dst_tend_planes, C.byref(dst)))
 
 
 def _diffs_to_dict(diffs) -> Dict[str, dict]:
@@ -915,6 +971,8 @@ def _hip():
     h.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
     h.hipDeviceSynchronize.argtypes = []
     h.hipSetDevice.argtypes = [C.c_int]
+    h.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+    h.hipFree.argtypes = [C.c_void_p]
     return h
 
 
@@ -923,10 +981,14 @@ class DeviceFields:
     the reference CUDA driver's shape -- allocate (cloudsc_driver.cu:276-328),
     copy the inputs in, launch cloudsc_gpu_run (:391-416), copy the outputs
     back (:425-447) -- with the output buffers placed by the library's
-    memory-pattern search (reads + writes, no physics) unless place=False."""
+    memory-pattern search (reads + writes, no physics) unless place=False.
+    tend_planes (8..64): also allocate two packed tendency buffers of that many planes per block
+    (self.buffer_tmp, self.buffer_loc, plain hipMalloc) and bind the eight tendency members of self.f to
+    them in the reference's plane order -- the set then runs with gpu_run_tendbuf; self.separate keeps the
+    set with the tendency members as the separate arrays cloudsc_fields_alloc made."""
 
     def __init__(self, ngptot: int, nproma: int, klev: int, precision: int = FP64, device: int = 0,
-                 place: bool = True, aerosols: bool = False):
+                 place: bool = True, aerosols: bool = False, tend_planes: int = 0):
         self.lib = gpu_lib()
         self.ngptot, self.nproma, self.klev, self.precision, self.device = ngptot, nproma, klev, precision, device
         self.f = Fields()
@@ -935,6 +997,32 @@ class DeviceFields:
         check(self.lib.cloudsc_fields_alloc(device, precision, ngptot, nproma, klev, flags, C.byref(self.f),
                                             C.byref(self.report)))
         self.hip = _hip()
+        self.tend_planes, self.separate, self.buffer_tmp, self.buffer_loc = 0, None, None, None
+        if tend_planes:
+            if not TENDBUF_PLANES_MIN <= tend_planes <= TENDBUF_PLANES_MAX:
+                self.close()
+                raise ValueError("tend_planes must be in %d..%d" % (TENDBUF_PLANES_MIN, TENDBUF_PLANES_MAX))
+            self.separate = Fields()
+            C.memmove(C.byref(self.separate), C.byref(self.f), C.sizeof(Fields))
+            self.tend_planes = tend_planes
+            self.hip.hipSetDevice(device)
+            bufs = []
+            for _ in range(2):
+                p = C.c_void_p()
+                if self.hip.hipMalloc(C.byref(p), self.tendbuf_nbytes()) != 0 or not p.value:
+                    for q in bufs:
+                        self.hip.hipFree(q)
+                    self.tend_planes = 0
+                    self.close()
+                    raise CloudscError("hipMalloc of a tendency buffer failed")
+                bufs.append(p.value)
+            self.buffer_tmp, self.buffer_loc = bufs
+            bind_tendbuf(self.f, precision, nproma, klev, self.buffer_tmp, self.buffer_loc)
+
+    def tendbuf_nbytes(self) -> int:
+        """Bytes of one packed tendency buffer of this set."""
+        return (nblocks_of(self.ngptot, self.nproma) * self.tend_planes * self.klev * self.nproma *
+                np.dtype(storage_dtype(self.precision)).itemsize)
 
     def nbytes(self, name: str) -> int:
         es = 4 if name == "ktype" else np.dtype(storage_dtype(self.precision)).itemsize
@@ -983,23 +1071,27 @@ class DeviceFields:
 
     def validate(self, ds: "Dataset", col_offset: int = 0, stream=None) -> list:
         """cloudsc_fields_validate: the 21 validated fields against ds.reference on the device; the list
-        of 7-tuples GpuState.validate returns."""
+        of 7-tuples GpuState.validate returns.  (A tend_planes set: its separate arrays, self.separate --
+        the validation has no packed form; unpack BUFFER_LOC first.)"""
         keep: list = []
         ref = make_reference(ds, keep)
         st = (Stats * 21)()
         check(self.lib.cloudsc_fields_validate(self.device, stream, self.precision, self.ngptot, self.nproma,
-                                               self.klev, col_offset, C.byref(self.f), C.byref(ref), st))
+                                               self.klev, col_offset, C.byref(self.separate or self.f),
+                                               C.byref(ref), st))
         return [(s.minval, s.maxval, s.maxerr, s.errsum, s.refsum, s.errsum_lo, s.refsum_lo) for s in st]
 
     def expand(self, ds: "Dataset", col_offset: int = 0, stream=None) -> None:
         """cloudsc_fields_expand: fill every input member this set holds (plude included) from the
-        dataset's template on the device.  Asynchronous on `stream` (None = the default stream)."""
+        dataset's template on the device.  Asynchronous on `stream` (None = the default stream).
+        (A tend_planes set: its separate arrays, self.separate -- the expansion has no packed form; pack
+        tendency_tmp_* afterwards.)"""
         if ds.klev != self.klev:
             raise ValueError("expand: the dataset's klev is not this set's")
         keep: list = []
         tmpl = make_template(ds, keep)
         check(self.lib.cloudsc_fields_expand(self.device, stream, self.precision, self.ngptot, self.nproma,
-                                             col_offset, C.byref(tmpl), C.byref(self.f)))
+                                             col_offset, C.byref(tmpl), C.byref(self.separate or self.f)))
 
     def download_raw(self, name: str) -> np.ndarray:
         """One field in block layout in its storage type (after a device synchronise)."""
@@ -1019,6 +1111,11 @@ class DeviceFields:
 
     def close(self) -> None:
         if getattr(self, "f", None) is not None:
+            if getattr(self, "tend_planes", 0):   # the separate arrays back, the buffers freed
+                for b in (self.buffer_tmp, self.buffer_loc):
+                    self.hip.hipFree(b)
+                C.memmove(C.byref(self.f), C.byref(self.separate), C.sizeof(Fields))
+                self.tend_planes = 0
             self.lib.cloudsc_fields_free(self.device, C.byref(self.f))
             self.f = None
 

@@ -37,8 +37,9 @@ struct HostColumn {
   ColConst<real> cc;
 };
 
-// real: the compute type, S: the fields' element type (float under double = CLOUDSC_MIXED)
-template <typename real, bool AER, typename S>
+// real: the compute type, S: the fields' element type (float under double = CLOUDSC_MIXED);
+// TB: the tendency members are planes of packed buffers and A is a KArgsTB (cloudsc_kcache.h)
+template <typename real, bool AER, bool TB, typename S>
 void run_block(const DevParams<real>& c, const KArgs<real, S>& A, int b, std::vector<HostColumn<real>>& col) {
   const int nproma = A.nproma, klev = A.klev;
   const int bsize = std::min(nproma, A.ngptot - b * nproma);
@@ -70,7 +71,7 @@ void run_block(const DevParams<real>& c, const KArgs<real, S>& A, int b, std::ve
       const unsigned lo = (unsigned)jl * (unsigned)sizeof(S);
       HostColumn<real>& h = col[jl];
       LevelIn<real> cur;
-      load_level<real, AER>(cur, A, u2, u3, k, klev, nproma, lo);
+      load_level<real, AER, TB>(cur, A, u2, u3, k, klev, nproma, lo);
       LevelState<real> ls;
       PhysOut<real> po;
       init_level(c, cur, ls);
@@ -79,7 +80,7 @@ void run_block(const DevParams<real>& c, const KArgs<real, S>& A, int b, std::ve
       po.atend = R(0.0);
       po.zcovptot_out = R(0.0);
       if (physics) physics_level(c, k, klev, ncldtop0, cur, h.nb, h.cc, ls, h.cs, po);
-      store_level(A, u2, u3, k, klev, nproma, lo, physics, ls, po);
+      store_level<TB>(A, u2, u3, k, klev, nproma, lo, physics, ls, po);
       flux_level(c, A, uh + (size_t)(k + 1) * nproma, lo, cur, ls, po, h.nb.paph_k, h.nb.paph_n, h.cs);
       h.cs.t_prev = ls.ztp1;
       h.cs.a_prev = ls.za;
@@ -100,7 +101,7 @@ void run_block(const DevParams<real>& c, const KArgs<real, S>& A, int b, std::ve
 template <typename S>
 int cpu_run(int nthreads, int ngptot, int nproma, int klev, const cloudsc_params_t* params,
             const cloudsc_fields_t* f, double* seconds, double* thread_seconds, int* thread_blocks,
-            int* thread_columns) {
+            int* thread_columns, int tend_planes = 0) {
   int rc = cloudsc_impl::check_params(params);
   if (rc) return rc;
   if (!f || !cloudsc_impl::fields_complete(f) || ngptot <= 0 || nproma <= 0 || klev < 2) return CLOUDSC_EINVAL;
@@ -108,7 +109,9 @@ int cpu_run(int nthreads, int ngptot, int nproma, int klev, const cloudsc_params
   if (aer && (!f->pre_ice || !f->picrit_aer || !f->pnice)) return CLOUDSC_EINVAL;
   if (nthreads <= 0 && (thread_seconds || thread_blocks || thread_columns)) return CLOUDSC_EINVAL;
   const DevParams<double> c = fold_params<double>(*params);
-  const KArgs<double, S> A = make_kargs<double, S>(f, ngptot, nproma, klev, nullptr);
+  KArgsTB<double, S> A;
+  static_cast<KArgs<double, S>&>(A) = make_kargs<double, S>(f, ngptot, nproma, klev, nullptr);
+  A.tend_planes = tend_planes;   // 0: separate arrays
   const int nblocks = ngptot / nproma + (ngptot % nproma ? 1 : 0);
   if (nthreads <= 0) nthreads = (int)std::max(1u, std::thread::hardware_concurrency());
   const int nreq = nthreads;                 // the caller's per-thread arrays have nreq entries
@@ -126,8 +129,14 @@ int cpu_run(int nthreads, int ngptot, int nproma, int klev, const cloudsc_params
     std::vector<HostColumn<double>> col((size_t)nproma);
     int icalls = 0, igpc = 0;
     for (int b = next.fetch_add(1); b < nblocks; b = next.fetch_add(1)) {
-      if (aer) run_block<double, true>(c, A, b, col);
-      else run_block<double, false>(c, A, b, col);
+      if (tend_planes) {
+        if (aer) run_block<double, true, true>(c, A, b, col);
+        else run_block<double, false, true>(c, A, b, col);
+      } else if (aer) {
+        run_block<double, true, false>(c, A, b, col);
+      } else {
+        run_block<double, false, false>(c, A, b, col);
+      }
       icalls++;
       igpc += std::min(nproma, ngptot - b * nproma);
     }
@@ -179,4 +188,17 @@ extern "C" int cloudsc_cpu_run_precision(int nthreads, int precision, int ngptot
 extern "C" int cloudsc_cpu_run(int nthreads, int ngptot, int nproma, int klev, const cloudsc_params_t* params,
                                const cloudsc_fields_t* f, double* seconds) {
   return cloudsc_cpu_run_precision(nthreads, CLOUDSC_FP64, ngptot, nproma, klev, params, f, seconds);
+}
+
+extern "C" int cloudsc_cpu_run_tendbuf(int nthreads, int precision, int ngptot, int nproma, int klev, int tend_planes,
+                                       const cloudsc_params_t* params, const cloudsc_fields_t* f) {
+  if (tend_planes < CLOUDSC_TENDBUF_PLANES_MIN || tend_planes > CLOUDSC_TENDBUF_PLANES_MAX) return CLOUDSC_EINVAL;
+  if (!cloudsc_impl::precision_computes_double(precision)) return CLOUDSC_EINVAL;   // as cloudsc_cpu_run_precision
+  switch (cloudsc_impl::precision_storage_bytes(precision)) {
+    case sizeof(double):
+      return cpu_run<double>(nthreads, ngptot, nproma, klev, params, f, nullptr, nullptr, nullptr, nullptr, tend_planes);
+    case sizeof(float):
+      return cpu_run<float>(nthreads, ngptot, nproma, klev, params, f, nullptr, nullptr, nullptr, nullptr, tend_planes);
+    default: return CLOUDSC_EINVAL;
+  }
 }

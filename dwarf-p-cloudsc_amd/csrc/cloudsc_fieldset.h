@@ -111,6 +111,10 @@ __device__ __forceinline__ FsPos fs_pos(unsigned g, unsigned np) {
 __device__ __forceinline__ size_t fs_offset(FsPos p, unsigned np, FsRows r) {
   return ((size_t)p.block * r.rows + r.row0) * np + p.lane;
 }
+// the same in a member whose blocks are `brows` rows apart (a plane of a packed tendency buffer: brows > r.rows)
+__device__ __forceinline__ size_t fs_offset_strided(FsPos p, unsigned np, FsRows r, size_t brows) {
+  return ((size_t)p.block * brows + r.row0) * np + p.lane;
+}
 // the same in a [rows][klon] operand whose column 0 is global column col_offset: [row0][(col_offset + g) % klon]
 __device__ __forceinline__ size_t fs_wrapped(unsigned g, long long col_offset, int klon, FsRows r) {
   return r.row0 * (size_t)klon + (size_t)((col_offset + (long long)g) % klon);
@@ -153,6 +157,31 @@ inline int fs_build(int ngptot, int klev, int a_precision, int a_nproma, const c
   }
   if (!a->n) return CLOUDSC_EINVAL;
   fs_shape(a, ngptot, a_nproma, b_nproma);
+  return CLOUDSC_OK;
+}
+
+// Packed tendency buffers (cloudsc_fields_convert_tendbuf): a table with the rows between consecutive blocks
+// of every entry, on both sides.  A plain member's is its `rows`; the eight tendency members of a side whose
+// tend_planes is non-zero are planes of a buffer [nblocks][tend_planes][klev][np]: tend_planes * klev.
+struct FsTendTable : FsTable<void> {
+  long long abrows[kFsMaxEntries], bbrows[kFsMaxEntries];
+};
+inline bool fs_is_tendency(int m) { return std::strncmp(kFieldTable[m].name, "tendency_", 9) == 0; }
+inline bool fs_tend_planes_ok(int planes) {
+  return planes == 0 || (planes >= CLOUDSC_TENDBUF_PLANES_MIN && planes <= CLOUDSC_TENDBUF_PLANES_MAX);
+}
+// fs_build, then the block strides of the two sides; member: scratch of kFsMaxEntries ints
+inline int fs_build_tend(int ngptot, int klev, int a_precision, int a_nproma, int a_planes, const cloudsc_fields_t* fa,
+                         int b_precision, int b_nproma, int b_planes, const cloudsc_fields_t* fb, FsTendTable* a) {
+  if (!fs_tend_planes_ok(a_planes) || !fs_tend_planes_ok(b_planes)) return CLOUDSC_EINVAL;
+  int member[kFsMaxEntries];
+  const int rc = fs_build<void>(ngptot, klev, a_precision, a_nproma, fa, b_precision, b_nproma, fb, a, member);
+  if (rc) return rc;
+  for (int i = 0; i < a->n; i++) {
+    const bool tend = fs_is_tendency(member[i]);
+    a->abrows[i] = tend && a_planes ? (long long)a_planes * klev : a->e[i].rows;
+    a->bbrows[i] = tend && b_planes ? (long long)b_planes * klev : a->e[i].rows;
+  }
   return CLOUDSC_OK;
 }
 

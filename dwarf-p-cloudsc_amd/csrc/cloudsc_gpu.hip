@@ -209,6 +209,41 @@ __global__ void __launch_bounds__(256, WAVES) kseg_packed_entry(const KArgs<real
   const cptr<KArgs<real, S>> ka = (cptr<KArgs<real, S>>)__builtin_amdgcn_kernarg_segment_ptr();
   cloudsc_kcache_persistent_body<real, PF, AER, LDSC, true>(ka, params_of<real, FAST>(ka), pa, g);
 }
+// The tendency buffer form (cloudsc_gpu_run_tendbuf): the same bodies with TB
+// on, the kernel arguments a KArgsTB.  Entry points of their own for every
+// (compute, storage) pair, in the product configuration only.
+template <typename real, typename S, int WAVES, int PF, bool AER, bool FAST = false>
+__global__ void __launch_bounds__(256, WAVES) kcache_tendbuf_entry(const KArgsTB<real, S> a) {
+  (void)a;
+  libm_tables_to_lds<real>();
+  const cptr<KArgs<real, S>> ka = (cptr<KArgs<real, S>>)__builtin_amdgcn_kernarg_segment_ptr();
+  cloudsc_kcache_body<real, PF, AER, false, true>(ka, params_of<real, FAST>(ka));
+}
+template <typename real, typename S, int WAVES, int PF, bool AER, bool FAST = false>
+__global__ void __launch_bounds__(256, WAVES) kseg_tendbuf_entry(const KArgsTB<real, S> a,
+                                                                 const PersistArgs<real> pa) {
+  (void)a;
+  libm_tables_to_lds<real>();
+  const cptr<KArgs<real, S>> ka = (cptr<KArgs<real, S>>)__builtin_amdgcn_kernarg_segment_ptr();
+  cloudsc_kcache_persistent_body<real, PF, AER, false, false, true>(ka, params_of<real, FAST>(ka), pa);
+}
+template <typename real, typename S, int WAVES, int PF, bool AER, bool FAST = false>
+__global__ void __launch_bounds__(256, WAVES) kcache_tendbuf_packed_entry(const KArgsTB<real, S> a,
+                                                                          const PackArgs g) {
+  (void)a;
+  libm_tables_to_lds<real>();
+  const cptr<KArgs<real, S>> ka = (cptr<KArgs<real, S>>)__builtin_amdgcn_kernarg_segment_ptr();
+  cloudsc_kcache_packed_body<real, PF, AER, false, true>(ka, params_of<real, FAST>(ka), g);
+}
+template <typename real, typename S, int WAVES, int PF, bool AER, bool FAST = false>
+__global__ void __launch_bounds__(256, WAVES) kseg_tendbuf_packed_entry(const KArgsTB<real, S> a,
+                                                                        const PersistArgs<real> pa,
+                                                                        const PackArgs g) {
+  (void)a;
+  libm_tables_to_lds<real>();
+  const cptr<KArgs<real, S>> ka = (cptr<KArgs<real, S>>)__builtin_amdgcn_kernarg_segment_ptr();
+  cloudsc_kcache_persistent_body<real, PF, AER, false, true, true>(ka, params_of<real, FAST>(ka), pa, g);
+}
 template <typename real, bool AER, bool FAST = false>
 __global__ void __launch_bounds__(256) scc_entry(const KArgs<real> a, const SccScratch<real> s) {
   (void)a;
@@ -282,10 +317,29 @@ constexpr auto kcache_kernel() {
   if constexpr (std::is_same<real, S>::value) return kcache_entry<real, WAVES, PF, AER, LDSC, FAST>;
   else return kcache_mixed_entry<WAVES, PF, AER, LDSC>;
 }
-template <typename real, typename S, int WAVES, int PF, bool AER, bool LDSC, bool FAST>
+template <typename real, typename S, int WAVES, int PF, bool AER, bool LDSC, bool FAST, bool TB = false>
 constexpr auto kseg_kernel() {
-  if constexpr (std::is_same<real, S>::value) return kseg_entry<real, WAVES, PF, AER, LDSC, FAST>;
+  if constexpr (TB) return kseg_tendbuf_entry<real, S, WAVES, PF, AER, FAST>;
+  else if constexpr (std::is_same<real, S>::value) return kseg_entry<real, WAVES, PF, AER, LDSC, FAST>;
   else return kseg_mixed_entry<WAVES, PF, AER, LDSC>;
+}
+template <typename real, typename S, int WAVES, int PF, bool AER, bool LDSC, bool FAST, bool TB = false>
+constexpr auto kseg_packed_kernel() {
+  if constexpr (TB) return kseg_tendbuf_packed_entry<real, S, WAVES, PF, AER, FAST>;
+  else return kseg_packed_entry<real, S, WAVES, PF, AER, LDSC, FAST>;
+}
+// the kernel arguments of a launch: a's, with tend_planes behind them in the tendency buffer form
+template <bool TB, typename real, typename S>
+auto kernel_args(const KArgs<real, S>& a, int tend_planes) {
+  if constexpr (TB) {
+    KArgsTB<real, S> t;
+    static_cast<KArgs<real, S>&>(t) = a;
+    t.tend_planes = tend_planes;
+    return t;
+  } else {
+    (void)tend_planes;
+    return a;
+  }
 }
 
 template <typename real, bool AER, bool FAST, typename S>
@@ -347,6 +401,21 @@ int launch_kcache_packed(hipStream_t st, const KArgs<real, S>& a, int nblocks, i
   const PackArgs g{pack, nblocks, (nblocks + pack - 1) / pack};
   launch_physics(kcache_packed_entry<real, S, DefaultCfg<real>::waves, DefaultCfg<real>::pf, AER, false, FAST>,
                  dim3(g.ngroups), dim3(64), 0, st, ev, a, g);
+  return CLOUDSC_OK;
+}
+
+// the tendency buffer form of launch_kcache and launch_kcache_packed: the product configuration (in a
+// CLOUDSC_DEBUG_KNOBS build too: CLOUDSC_KCACHE_CFG selects among the plain kernels only)
+template <typename real, bool AER, bool FAST, typename S>
+int launch_kcache_tendbuf(hipStream_t st, const KArgsTB<real, S>& a, int nblocks, int nproma, int pack,
+                          const LaunchEvents* ev) {
+  constexpr int W = DefaultCfg<real>::waves, PF = DefaultCfg<real>::pf;
+  if (pack > 1) {
+    const PackArgs g{pack, nblocks, (nblocks + pack - 1) / pack};
+    launch_physics(kcache_tendbuf_packed_entry<real, S, W, PF, AER, FAST>, dim3(g.ngroups), dim3(64), 0, st, ev, a, g);
+  } else {
+    launch_physics(kcache_tendbuf_entry<real, S, W, PF, AER, FAST>, dim3(nblocks), dim3(nproma), 0, st, ev, a);
+  }
   return CLOUDSC_OK;
 }
 
@@ -451,13 +520,15 @@ int kseg_grid_size(int per_cu, int ncu, int nitems, int nseg) {
   return grid;
 }
 
-// pk: the packed kernel (one 64-lane workgroup per group of blocks); NULL: the unpacked one
-template <typename real, int WAVES, int PF, bool AER, bool LDSC, bool FAST, typename S>
-int launch_kseg_cfg(hipStream_t st, const KArgs<real, S>& a, const PersistArgs<real>& pa, int nproma, int nitems,
-                    int* grid_out, const LaunchEvents* ev, const PackArgs* pk = nullptr) {
+// pk: the packed kernel (one 64-lane workgroup per group of blocks); NULL: the unpacked one;
+// tend_planes (TB): the tendency buffer form of either
+template <typename real, int WAVES, int PF, bool AER, bool LDSC, bool FAST, bool TB = false, typename S>
+int launch_kseg_cfg(hipStream_t st, const KArgs<real, S>& a0, const PersistArgs<real>& pa, int nproma, int nitems,
+                    int* grid_out, const LaunchEvents* ev, const PackArgs* pk = nullptr, int tend_planes = 0) {
   const int nseg = pa.nseg;
-  auto kern = kseg_kernel<real, S, WAVES, PF, AER, LDSC, FAST>();
-  auto kern_packed = kseg_packed_entry<real, S, WAVES, PF, AER, LDSC, FAST>;
+  const auto a = kernel_args<TB>(a0, tend_planes);
+  auto kern = kseg_kernel<real, S, WAVES, PF, AER, LDSC, FAST, TB>();
+  auto kern_packed = kseg_packed_kernel<real, S, WAVES, PF, AER, LDSC, FAST, TB>();
   const int wg = pk ? 64 : kseg_wg(nproma);
   const size_t lds = LDSC ? carry_lds_bytes<real>(wg) : 0;
   // Waves per SIMD: as many as fit, but no more than whole rounds of the work
@@ -524,13 +595,19 @@ int launch_kseg(hipStream_t st, const KArgs<real, S>& a, const PersistArgs<real>
 // `real` is CLOUDSC_MIXED: the k-caching kernels only)
 template <typename real, bool FAST, typename ST = real>
 int launch_v(hipStream_t st, int variant, const cloudsc_fields_t* f, int ngptot, int nproma, int klev,
-             void* scratch, const void* plude_in, const ParamSet& ps, KsegEpoch* ep, const LaunchEvents* ev) {
+             void* scratch, const void* plude_in, const ParamSet& ps, KsegEpoch* ep, const LaunchEvents* ev,
+             int tend_planes) {
 #ifdef CLOUDSC_ONLY_KSEG
   if (variant != CLOUDSC_VARIANT_KSEG || ps.aer || sizeof(real) != CLOUDSC_ONLY_KSEG || sizeof(ST) != sizeof(real))
     return CLOUDSC_EINVAL;
 #endif
   constexpr bool kPlain = std::is_same<real, ST>::value;
   if (!kPlain && variant != CLOUDSC_VARIANT_KCACHE && variant != CLOUDSC_VARIANT_KSEG) return CLOUDSC_EINVAL;
+  // tend_planes != 0: the tendency buffer form: KCACHE and KSEG, fp64, fp32 (its default exp/pow) and mixed,
+  // in the product configuration only -- a CLOUDSC_DEBUG_KNOBS build's CLOUDSC_KCACHE_CFG does not apply to it
+  constexpr bool kTendbuf = !(std::is_same<real, float>::value && !FAST);
+  if (tend_planes && (!kTendbuf || (variant != CLOUDSC_VARIANT_KCACHE && variant != CLOUDSC_VARIANT_KSEG)))
+    return CLOUDSC_EINVAL;
   KArgs<real, ST> a = make_kargs<real, ST>(
       f, ngptot, nproma, klev, (const DevParams<real>*)((const char*)ps.dev + (sizeof(real) == 8 ? 0 : kSpOffset)));
   if (plude_in) a.plude_in = (const ST*)plude_in;
@@ -539,11 +616,18 @@ int launch_v(hipStream_t st, int variant, const cloudsc_fields_t* f, int ngptot,
   if (aer && (!f->pre_ice || !f->picrit_aer || !f->pnice)) return CLOUDSC_EINVAL;
   int rc = CLOUDSC_OK;
   // blocks per wave (1 = unpacked) and the packed launches' extra kernel argument
-  const int pack = narrow_pack_factor(precision_code(real(), ST()), variant, nproma, klev, aer);
+  int pack = narrow_pack_factor(precision_code(real(), ST()), variant, nproma, klev, aer);
+  // (a packed lane's offset in a tendency buffer: below pack * tend_planes * klev * nproma elements)
+  if ((unsigned long long)pack * (unsigned)tend_planes * (unsigned long long)klev * (unsigned)nproma * 8ull >= (1ull << 32))
+    pack = 1;
   const PackArgs pk{pack, nblocks, (nblocks + pack - 1) / pack};
   if (variant == CLOUDSC_VARIANT_KCACHE) {
     if constexpr (CLOUDSC_KEEP_KERNEL(real, false, false)) {
-      if (pack > 1)
+      if (tend_planes) {
+        if constexpr (kTendbuf)
+          rc = aer ? launch_kcache_tendbuf<real, true, FAST>(st, kernel_args<true>(a, tend_planes), nblocks, nproma, pack, ev)
+                   : launch_kcache_tendbuf<real, false, FAST>(st, kernel_args<true>(a, tend_planes), nblocks, nproma, pack, ev);
+      } else if (pack > 1)
         rc = aer ? launch_kcache_packed<real, true, FAST>(st, a, nblocks, pack, ev)
                  : launch_kcache_packed<real, false, FAST>(st, a, nblocks, pack, ev);
       else
@@ -603,7 +687,14 @@ int launch_v(hipStream_t st, int variant, const cloudsc_fields_t* f, int ngptot,
     for (int q = 0; q < kKsegStripes; q++) pa.base[q] = zero_ws ? 0u : ep->base[q];
     pa.stamp = zero_ws ? 0u : ep->stamp;
     int grid = 0;
-    if constexpr (CLOUDSC_KEEP_KERNEL(real, true, true))
+    constexpr int W = DefaultCfg<real>::waves, PF = DefaultCfg<real>::pf;
+    if (tend_planes) {
+      if constexpr (kTendbuf && CLOUDSC_KEEP_KERNEL(real, true, true))
+        rc = aer ? launch_kseg_cfg<real, W, PF, true, false, FAST, true>(st, a, pa, nproma, pa.nitems, &grid, ev, pkp,
+                                                                         tend_planes)
+                 : launch_kseg_cfg<real, W, PF, false, false, FAST, true>(st, a, pa, nproma, pa.nitems, &grid, ev, pkp,
+                                                                          tend_planes);
+    } else if constexpr (CLOUDSC_KEEP_KERNEL(real, true, true))
       rc = aer ? launch_kseg<real, true, FAST>(st, a, pa, nproma, pa.nitems, &grid, ev, pkp)
                : launch_kseg<real, false, FAST>(st, a, pa, nproma, pa.nitems, &grid, ev, pkp);
     else if constexpr (CLOUDSC_KEEP_KERNEL(real, true, false))
@@ -644,26 +735,29 @@ int launch_v(hipStream_t st, int variant, const cloudsc_fields_t* f, int ngptot,
 // reference CPU build's forms (CLOUDSC_FP32_EXACT_LIBM); fp64 has only those
 template <typename real>
 int launch(hipStream_t st, int variant, bool exact_libm, const cloudsc_fields_t* f, int ngptot, int nproma,
-           int klev, void* scratch, const void* plude_in, const ParamSet& ps, KsegEpoch* ep, const LaunchEvents* ev) {
+           int klev, void* scratch, const void* plude_in, const ParamSet& ps, KsegEpoch* ep, const LaunchEvents* ev,
+           int tend_planes) {
   if constexpr (std::is_same<real, float>::value) {
-    if (!exact_libm) return launch_v<real, true>(st, variant, f, ngptot, nproma, klev, scratch, plude_in, ps, ep, ev);
+    if (!exact_libm)
+      return launch_v<real, true>(st, variant, f, ngptot, nproma, klev, scratch, plude_in, ps, ep, ev, tend_planes);
   }
   (void)exact_libm;
-  return launch_v<real, false>(st, variant, f, ngptot, nproma, klev, scratch, plude_in, ps, ep, ev);
+  return launch_v<real, false>(st, variant, f, ngptot, nproma, klev, scratch, plude_in, ps, ep, ev, tend_planes);
 }
 
 // The launch of a precision code.  CLOUDSC_MIXED is the fp64 launch (exp/pow,
 // parameter mirror, configuration, workspace) over float fields.
 int launch_precision(int precision, hipStream_t st, int variant, bool exact_libm, const cloudsc_fields_t* f,
                      int ngptot, int nproma, int klev, void* scratch, const void* plude_in, const ParamSet& ps,
-                     KsegEpoch* ep, const LaunchEvents* ev) {
+                     KsegEpoch* ep, const LaunchEvents* ev, int tend_planes) {
   switch (precision) {
     case CLOUDSC_FP64:
-      return launch<double>(st, variant, exact_libm, f, ngptot, nproma, klev, scratch, plude_in, ps, ep, ev);
+      return launch<double>(st, variant, exact_libm, f, ngptot, nproma, klev, scratch, plude_in, ps, ep, ev, tend_planes);
     case CLOUDSC_FP32:
-      return launch<float>(st, variant, exact_libm, f, ngptot, nproma, klev, scratch, plude_in, ps, ep, ev);
+      return launch<float>(st, variant, exact_libm, f, ngptot, nproma, klev, scratch, plude_in, ps, ep, ev, tend_planes);
     case CLOUDSC_MIXED:
-      return launch_v<double, false, float>(st, variant, f, ngptot, nproma, klev, scratch, plude_in, ps, ep, ev);
+      return launch_v<double, false, float>(st, variant, f, ngptot, nproma, klev, scratch, plude_in, ps, ep, ev,
+                                            tend_planes);
     default: return CLOUDSC_EINVAL;
   }
 }
@@ -744,7 +838,7 @@ int validate_run_args(int device, int precision, int variant, int ngptot, int np
 // ps: the parameter set of the launch (NULL = the device's default set).
 int gpu_run_impl(int device, void* stream, int precision, int variant, int ngptot, int nproma, int klev,
                  const cloudsc_fields_t* f, void* scratch, const void* plude_in, const ParamSet* ps,
-                 KsegEpoch* ep, const LaunchEvents* lev) {
+                 KsegEpoch* ep, const LaunchEvents* lev, int tend_planes) {
   const bool exact_libm = (variant & CLOUDSC_FP32_EXACT_LIBM) != 0;
   variant = variant_kind(variant);
   int rc = validate_run_args(device, precision, variant, ngptot, nproma, klev);
@@ -755,7 +849,8 @@ int gpu_run_impl(int device, void* stream, int precision, int variant, int ngpto
   if (!f || !fields_complete(f)) return CLOUDSC_EINVAL;
   HIPCHK(hipSetDevice(device));
   hipStream_t st = (hipStream_t)stream;
-  return launch_precision(precision, st, variant, exact_libm, f, ngptot, nproma, klev, scratch, plude_in, *ps, ep, lev);
+  return launch_precision(precision, st, variant, exact_libm, f, ngptot, nproma, klev, scratch, plude_in, *ps, ep, lev,
+                          tend_planes);
 }
 
 int kseg_clock(int device, void* stream, void* scratch, bool reset, double* ghz, double* seconds) {
@@ -798,6 +893,38 @@ extern "C" {
 int cloudsc_gpu_run(int device, void* stream, int precision, int variant, int ngptot, int nproma,
                     int klev, const cloudsc_fields_t* f, void* scratch) {
   return gpu_run_impl(device, stream, precision, variant, ngptot, nproma, klev, f, scratch, nullptr, nullptr);
+}
+
+int cloudsc_tendbuf_bind(cloudsc_fields_t* f, int precision, int nproma, int klev, const void* buffer_tmp,
+                         void* buffer_loc) {
+  const size_t eb = precision_storage_bytes(precision);
+  if (!f || !eb || nproma < 1 || klev < 1 || !buffer_tmp || !buffer_loc) return CLOUDSC_EINVAL;
+  const size_t plane = (size_t)klev * (size_t)nproma * eb;
+  const char* tmp = (const char*)buffer_tmp;
+  char* loc = (char*)buffer_loc;
+  f->tendency_tmp_t = tmp + CLOUDSC_TENDBUF_T * plane;
+  f->tendency_tmp_a = tmp + CLOUDSC_TENDBUF_A * plane;
+  f->tendency_tmp_q = tmp + CLOUDSC_TENDBUF_Q * plane;
+  f->tendency_tmp_cld = tmp + CLOUDSC_TENDBUF_CLD * plane;
+  f->tendency_loc_t = loc + CLOUDSC_TENDBUF_T * plane;
+  f->tendency_loc_a = loc + CLOUDSC_TENDBUF_A * plane;
+  f->tendency_loc_q = loc + CLOUDSC_TENDBUF_Q * plane;
+  f->tendency_loc_cld = loc + CLOUDSC_TENDBUF_CLD * plane;
+  return CLOUDSC_OK;
+}
+
+int cloudsc_gpu_run_tendbuf(int device, void* stream, int precision, int variant, int ngptot, int nproma, int klev,
+                            int tend_planes, const cloudsc_fields_t* f, void* scratch) {
+  // every argument rule first, the device's among them last: no HIP call before an argument error
+  if (tend_planes < CLOUDSC_TENDBUF_PLANES_MIN || tend_planes > CLOUDSC_TENDBUF_PLANES_MAX) return CLOUDSC_EINVAL;
+  if (variant & ~0xff) return CLOUDSC_EINVAL;                                                  // no option bits
+  const int kind = variant_kind(variant);
+  if (kind != CLOUDSC_VARIANT_KCACHE && kind != CLOUDSC_VARIANT_KSEG) return CLOUDSC_EINVAL;   // no SCC form
+  const int rc = validate_shape_args(precision, kind, ngptot, nproma, klev);
+  if (rc) return rc;
+  if (!f || !fields_complete(f) || (kind == CLOUDSC_VARIANT_KSEG && !scratch)) return CLOUDSC_EINVAL;
+  return gpu_run_impl(device, stream, precision, variant, ngptot, nproma, klev, f, scratch, nullptr, nullptr, nullptr,
+                      nullptr, tend_planes);
 }
 
 int cloudsc_gpu_check(int device, void* stream, int variant, void* scratch) {

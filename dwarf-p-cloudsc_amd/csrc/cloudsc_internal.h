@@ -92,10 +92,11 @@ struct LaunchEvents {
 // cloudsc_gpu_run with an optional separate source of plude (NULL = in place),
 // an explicit parameter set (NULL = the device's default set), an optional
 // KSEG workspace record (NULL = zero the workspace before every KSEG launch)
-// and optional events timing the physics kernel (NULL = none)
+// and optional events timing the physics kernel (NULL = none); tend_planes != 0:
+// the tendency members of f are planes of packed buffers (cloudsc_gpu_run_tendbuf)
 int gpu_run_impl(int device, void* stream, int precision, int variant, int ngptot, int nproma, int klev,
                  const cloudsc_fields_t* f, void* scratch, const void* plude_in, const ParamSet* ps,
-                 KsegEpoch* ep = nullptr, const LaunchEvents* lev = nullptr);
+                 KsegEpoch* ep = nullptr, const LaunchEvents* lev = nullptr, int tend_planes = 0);
 // the kernel variant of a `variant` argument without its option bits (CLOUDSC_FP32_EXACT_LIBM)
 inline int variant_kind(int variant) { return variant & 0xff; }
 // waits for `stream` and returns CLOUDSC_EHANDOFF if the last KSEG launch on

@@ -50,6 +50,15 @@ struct KArgs {
   const DevParams<real>* par;   // the launch's parameter set (device memory, read with scalar loads)
   int ngptot, nproma, klev;
 };
+// The kernel arguments of the "tendency buffer" form (TB): the eight tendency
+// members tendency_tmp_* / tendency_loc_* are planes of two packed buffers
+// [nblocks][tend_planes][klev][nproma] (the reference's Fortran drivers'
+// BUFFER_TMP / BUFFER_LOC), each member pointer the start of its plane in block
+// 0; the block stride of these members is tend_planes * klev * nproma elements.
+template <typename real, typename store = real>
+struct KArgsTB : KArgs<real, store> {
+  int tend_planes;
+};
 
 enum { QL = 0, QI = 1, QR = 2, QS = 3, QV = 4 };
 
@@ -176,6 +185,23 @@ CLOUDSC_HD PackLo launder_vgpr(PackLo p) {
 CLOUDSC_HD unsigned lane_here(unsigned lo) { return lo; }
 CLOUDSC_HD PackLo lane_here(const PackLo& p) { return launder_vgpr(p); }
 
+// The tendency buffer form (TB) of the three functions that touch the eight
+// tendency members: load_early, load_level, store_level.  Their block base in a
+// buffer is ut = b * tend_planes * klev * nproma = u2 * tend_planes, formed
+// where it is used from the level fields' block base u2 and the (re-laundered)
+// kernel arguments, so TB adds no argument and nothing live across the level;
+// the species member indexes ut + (m * klev + k) * nproma, as u3 does.  A
+// packed lane's sub-slot s is s blocks of a buffer further on.  With TB off the
+// functions' expressions are the ones of the fields' kinds, untouched.
+template <typename real, typename S>
+CLOUDSC_HD int tend_planes_of(const KArgs<real, S>& A) {
+  return static_cast<const KArgsTB<real, S>&>(A).tend_planes;
+}
+CLOUDSC_HD unsigned lo_tend(unsigned lo, int) { return lo; }      // [nblocks][tend_planes][klev][nproma]
+CLOUDSC_HD unsigned lo_tend(const PackLo& p, int tend_planes) {
+  return p.sb * (unsigned)(tend_planes * p.klev) + p.jb;
+}
+
 // Per-level inputs of one column (the prefetch unit).
 template <typename real>
 struct LevelIn {
@@ -192,18 +218,28 @@ struct EarlyIn {
   real pt, pq, ttt, ttq, tta, pa, pap;
   real pclv[4], ttcld[4];
 };
-template <typename real, typename S, typename LO>
+template <typename real, bool TB = false, typename S, typename LO>
 CLOUDSC_HD void load_early(EarlyIn<real>& E, const KArgs<real, S>& A, size_t u2, size_t u3, int k, int klev,
                            int nproma, LO lane) {
   const size_t i = u2 + (size_t)k * nproma;
   const unsigned lo = lo_full(lane), ls = lo_spec(lane);
-  E.pt = ldg1(A.pt, i, lo); E.pq = ldg1(A.pq, i, lo); E.ttt = ldg1(A.ttt, i, lo); E.ttq = ldg1(A.ttq, i, lo);
-  E.tta = ldg1(A.tta, i, lo); E.pa = ldg1(A.pa, i, lo); E.pap = ldg1(A.pap, i, lo);
+  size_t it = i, t3 = u3;            // the tendency members' level index, species base and lane offsets
+  unsigned lot = lo, lst = ls;
+  if constexpr (TB) {
+    const int tp = tend_planes_of(A);
+    t3 = u2 * (size_t)tp;
+    it = t3 + (size_t)k * nproma;
+    lot = lst = lo_tend(lane, tp);
+  }
+  E.pt = ldg1(A.pt, i, lo); E.pq = ldg1(A.pq, i, lo); E.ttt = ldg1(A.ttt, it, lot); E.ttq = ldg1(A.ttq, it, lot);
+  E.tta = ldg1(A.tta, it, lot); E.pa = ldg1(A.pa, i, lo); E.pap = ldg1(A.pap, i, lo);
 #pragma unroll
   for (int m = 0; m < 4; m++) {
     const size_t j = u3 + ((size_t)m * klev + k) * nproma;
+    size_t jt = j;
+    if constexpr (TB) jt = t3 + ((size_t)m * klev + k) * nproma;
     E.pclv[m] = ldg1_sp<kSpOpaque<real, S>>(A.pclv, j, ls);
-    E.ttcld[m] = ldg1_sp<kSpOpaque<real, S>>(A.ttcld, j, ls);
+    E.ttcld[m] = ldg1_sp<kSpOpaque<real, S>>(A.ttcld, jt, lst);
   }
 }
 template <typename real, bool AER, typename S, typename LO>
@@ -310,19 +346,29 @@ struct PhysOut {
 // All loads of a level are unconditional (the physics-only fields are read at
 // every level): branches around memory operations make hipcc's vmcnt
 // bookkeeping fall back to vmcnt(0), which drains the software pipeline.
-template <typename real, bool AER, typename S, typename LO>
+template <typename real, bool AER, bool TB = false, typename S, typename LO>
 CLOUDSC_HD void load_level(LevelIn<real>& L, const KArgs<real, S>& A, size_t u2, size_t u3, int k,
                                            int klev, int nproma, LO lane) {
   const size_t i = u2 + (size_t)k * nproma;
   const unsigned lo = lo_full(lane), ls = lo_spec(lane);
-  L.pt = ldg1(A.pt, i, lo); L.pq = ldg1(A.pq, i, lo); L.ttt = ldg1(A.ttt, i, lo); L.ttq = ldg1(A.ttq, i, lo);
-  L.tta = ldg1(A.tta, i, lo); L.pa = ldg1(A.pa, i, lo); L.pap = ldg1(A.pap, i, lo);
+  size_t it = i, t3 = u3;            // the tendency members' level index, species base and lane offsets
+  unsigned lot = lo, lst = ls;
+  if constexpr (TB) {
+    const int tp = tend_planes_of(A);
+    t3 = u2 * (size_t)tp;
+    it = t3 + (size_t)k * nproma;
+    lot = lst = lo_tend(lane, tp);
+  }
+  L.pt = ldg1(A.pt, i, lo); L.pq = ldg1(A.pq, i, lo); L.ttt = ldg1(A.ttt, it, lot); L.ttq = ldg1(A.ttq, it, lot);
+  L.tta = ldg1(A.tta, it, lot); L.pa = ldg1(A.pa, i, lo); L.pap = ldg1(A.pap, i, lo);
   L.plude = ldg1(A.plude_in, i, lo); L.pvfl = ldg1(A.pvfl, i, lo); L.pvfi = ldg1(A.pvfi, i, lo);
 #pragma unroll
   for (int m = 0; m < 4; m++) {
     const size_t j = u3 + ((size_t)m * klev + k) * nproma;
+    size_t jt = j;
+    if constexpr (TB) jt = t3 + ((size_t)m * klev + k) * nproma;
     L.pclv[m] = ldg1_sp<kSpOpaque<real, S>>(A.pclv, j, ls);
-    L.ttcld[m] = ldg1_sp<kSpOpaque<real, S>>(A.ttcld, j, ls);
+    L.ttcld[m] = ldg1_sp<kSpOpaque<real, S>>(A.ttcld, jt, lst);
   }
   L.phrsw = ldg1(A.phrsw, i, lo); L.phrlw = ldg1(A.phrlw, i, lo); L.pvervel = ldg1(A.pvervel, i, lo);
   L.psnde = ldg1(A.psnde, i, lo); L.psupsat = ldg1(A.psupsat, i, lo);
@@ -1149,21 +1195,30 @@ CLOUDSC_HD ColConst<real> column_constants(const P& c, const KArgs<real, S>& A,
   return cc;
 }
 
-template <typename real, typename S, typename LO>
+template <bool TB = false, typename real, typename S, typename LO>
 CLOUDSC_HD void store_level(const KArgs<real, S>& A, size_t u2, size_t u3, int k, int klev,
                                             int nproma, LO lane, bool physics, const LevelState<real>& ls,
                                             const PhysOut<real>& po) {
   const size_t i = u2 + (size_t)k * nproma;
-  const unsigned lo = lo_full(lane), lsp = lo_spec(lane);
-  stg(A.tlt, i, lo, ls.ttend);
-  stg(A.tlq, i, lo, ls.qtend);
-  stg(A.tla, i, lo, po.atend);
+  const unsigned lo = lo_full(lane);
+  unsigned lsp = lo_spec(lane);
+  size_t it = i, t3 = u3;
+  unsigned lot = lo;
+  if constexpr (TB) {
+    const int tp = tend_planes_of(A);
+    t3 = u2 * (size_t)tp;
+    it = t3 + (size_t)k * nproma;
+    lot = lsp = lo_tend(lane, tp);
+  }
+  stg(A.tlt, it, lot, ls.ttend);
+  stg(A.tlq, it, lot, ls.qtend);
+  stg(A.tla, it, lot, po.atend);
   stg(A.pcovptot, i, lo, po.zcovptot_out);
   stg(A.plude, i, lo, po.plude_k);   // INOUT: rewritten unchanged where not rescaled (no branch on a store)
 #pragma unroll
   for (int m = 0; m < 4; m++)
-    stg_sp<kSpOpaque<real, S>>(A.tlcld, u3 + ((size_t)m * klev + k) * nproma, lsp, po.ctend[m]);
-  stg_sp<kSpOpaque<real, S>>(A.tlcld, u3 + ((size_t)4 * klev + k) * nproma, lsp, R(0.0));
+    stg_sp<kSpOpaque<real, S>>(A.tlcld, t3 + ((size_t)m * klev + k) * nproma, lsp, po.ctend[m]);
+  stg_sp<kSpOpaque<real, S>>(A.tlcld, t3 + ((size_t)4 * klev + k) * nproma, lsp, R(0.0));
 }
 
 template <typename real, typename CS>
@@ -1193,7 +1248,9 @@ __device__ __forceinline__ const auto& params_here(const PV& pv, cptr<PT> cpar) 
 // kcache_levels runs levels [lev0, lev1) of block b for one (active) lane with
 // the carried state `cs`; the plain kernel runs [0, klev) in one go, the
 // persistent kernel (below) runs a column in level segments.
-template <typename real, int PF, bool AER, typename S, typename PT, typename CS, typename LO>
+//
+// TB: the tendency buffer form (KArgsTB; `ka` then points at one).
+template <typename real, int PF, bool AER, bool TB = false, typename S, typename PT, typename CS, typename LO>
 __device__ __forceinline__ void kcache_levels(cptr<KArgs<real, S>> ka, cptr<PT> cpar, int b,
                                               LO lo0, int lev0, int lev1, CS& cs) {
   if (lev0 >= lev1) return;
@@ -1231,9 +1288,9 @@ __device__ __forceinline__ void kcache_levels(cptr<KArgs<real, S>> ka, cptr<PT> 
     nb.pmfu_n = ldg(A.pmfu, u2 + (size_t)l1 * nproma, lo_full(lo));
     nb.pmfd_n = ldg(A.pmfd, u2 + (size_t)l1 * nproma, lo_full(lo));
     nb.plu_n = ldg(A.plu, u2 + (size_t)l1 * nproma, lo_full(lo));
-    if (PFX) load_level<real, AER>(cur, A, u2, u3, lev0, klev, nproma, lo);
-    if (PFM) load_early<real>(nxt_e, A, u2, u3, lev0, klev, nproma, lo);
-    if (PFA) load_level<real, AER>(nxt, A, u2, u3, lev0, klev, nproma, lo);
+    if (PFX) load_level<real, AER, TB>(cur, A, u2, u3, lev0, klev, nproma, lo);
+    if (PFM) load_early<real, TB>(nxt_e, A, u2, u3, lev0, klev, nproma, lo);
+    if (PFA) load_level<real, AER, TB>(nxt, A, u2, u3, lev0, klev, nproma, lo);
   }
 #if defined(__HIP_DEVICE_COMPILE__)
   // PF 1: drain the prologue's loads once (per segment) before the level loop.
@@ -1279,13 +1336,13 @@ __device__ __forceinline__ void kcache_levels(cptr<KArgs<real, S>> ka, cptr<PT> 
       const int k1 = k + 1 < klev ? k + 1 : klev - 1;
       const int k2 = k + 2 < klev ? k + 2 : klev - 1;
       const int kh2 = k + 2 < klev + 1 ? k + 2 : klev;
-      if (!PFX && !PFM && !PFA) load_level<real, AER>(cur, A, u2, u3, k, klev, nproma, lo);
+      if (!PFX && !PFM && !PFA) load_level<real, AER, TB>(cur, A, u2, u3, k, klev, nproma, lo);
       if (PFA) cur = nxt;
       if (PFM) {
         load_late<real, AER>(cur, A, u2, k, nproma, lo);
         take_early(cur, nxt_e);
       }
-      if (PFX) load_level<real, AER>(nxt, A, u2, u3, k1, klev, nproma, lo);
+      if (PFX) load_level<real, AER, TB>(nxt, A, u2, u3, k1, klev, nproma, lo);
       if (NBR) {
         nb.paph_k = ldg(A.paph, uh + (size_t)k * nproma, lo_half(lo));
         nb.paph_n = ldg(A.paph, uh + (size_t)(k + 1) * nproma, lo_half(lo));
@@ -1318,10 +1375,10 @@ __device__ __forceinline__ void kcache_levels(cptr<KArgs<real, S>> ka, cptr<PT> 
         if (PFM || PFA) {
           const int k1 = k + 1 < klev ? k + 1 : klev - 1;
           if (PFM)
-            load_early<real>(nxt_e, *(const KArgs<real, S>*)launder_uniform(ka), u2, u3, k1, klev, nproma,
+            load_early<real, TB>(nxt_e, *(const KArgs<real, S>*)launder_uniform(ka), u2, u3, k1, klev, nproma,
                              launder_vgpr(lo0));
           else
-            load_level<real, AER>(nxt, *(const KArgs<real, S>*)launder_uniform(ka), u2, u3, k1, klev, nproma,
+            load_level<real, AER, TB>(nxt, *(const KArgs<real, S>*)launder_uniform(ka), u2, u3, k1, klev, nproma,
                                   launder_vgpr(lo0));
         }
       };
@@ -1342,7 +1399,7 @@ __device__ __forceinline__ void kcache_levels(cptr<KArgs<real, S>> ka, cptr<PT> 
       // (packed: a fresh copy as well, so that neither the top-of-level copy nor the
       // offsets formed from it stay live across the physics)
       const LO los = PVR || std::is_same<LO, PackLo>::value ? launder_vgpr(lo0) : lo;
-      store_level(A, u2, u3, k, klev, nproma, los, physics, ls, po);
+      store_level<TB>(A, u2, u3, k, klev, nproma, los, physics, ls, po);
       flux_level(c, A, uh + (size_t)(k + 1) * nproma, los, cur, ls, po, nb.paph_k, nb.paph_n, cs);
     }
 
@@ -1365,7 +1422,7 @@ struct CarryRegs : CarryState<real> {
 template <typename real, bool LDSC>
 using CarryOf = typename std::conditional<LDSC, CarryLds<real>, CarryRegs<real>>::type;
 
-template <typename real, int PF, bool AER, bool LDSC, typename S, typename PT>
+template <typename real, int PF, bool AER, bool LDSC, bool TB = false, typename S, typename PT>
 __device__ __forceinline__ void cloudsc_kcache_body(cptr<KArgs<real, S>> ka, cptr<PT> cpar) {
   const KArgs<real, S>& A = *(const KArgs<real, S>*)ka;
   const int b = blockIdx.x, jl = threadIdx.x;
@@ -1377,7 +1434,7 @@ __device__ __forceinline__ void cloudsc_kcache_body(cptr<KArgs<real, S>> ka, cpt
     CLOUDSC_PARAMS_HERE;
     flux_top(c, A, (size_t)b * (A.klev + 1) * A.nproma, lo);
   }
-  kcache_levels<real, PF, AER>(ka, cpar, b, lo, 0, A.klev, cs);
+  kcache_levels<real, PF, AER, TB>(ka, cpar, b, lo, 0, A.klev, cs);
   stg(((const KArgs<real, S>*)launder_uniform(ka))->prainfrac, (size_t)b * A.nproma, lo, cs.rainfrac);
 }
 
@@ -1411,7 +1468,7 @@ __device__ __forceinline__ bool pack_lane(int ngptot, int nproma, int klev, cons
   return s < (unsigned)G.pack && b < (unsigned)G.nblocks && b * np + jl < (unsigned)ngptot;
 }
 
-template <typename real, int PF, bool AER, bool LDSC, typename S, typename PT>
+template <typename real, int PF, bool AER, bool LDSC, bool TB = false, typename S, typename PT>
 __device__ __forceinline__ void cloudsc_kcache_packed_body(cptr<KArgs<real, S>> ka, cptr<PT> cpar,
                                                            const PackArgs& G) {
   const KArgs<real, S>& A = *(const KArgs<real, S>*)ka;
@@ -1425,7 +1482,7 @@ __device__ __forceinline__ void cloudsc_kcache_packed_body(cptr<KArgs<real, S>> 
     CLOUDSC_PARAMS_HERE;
     flux_top(c, A, (size_t)b0 * (A.klev + 1) * A.nproma, lo);
   }
-  kcache_levels<real, PF, AER>(ka, cpar, b0, lo, 0, A.klev, cs);
+  kcache_levels<real, PF, AER, TB>(ka, cpar, b0, lo, 0, A.klev, cs);
   stg(((const KArgs<real, S>*)launder_uniform(ka))->prainfrac, (size_t)b0 * A.nproma, lo_surf(lane_here(lo)),
       cs.rainfrac);
 }
@@ -1516,7 +1573,7 @@ __device__ __forceinline__ void carry_io(real* st, size_t u, size_t plane, unsig
 // PACK: the schedule runs over groups of G.pack blocks instead of blocks (items
 // are (segment, group), stripes are taken over groups, one flag per group: the
 // first G.ngroups words of the flag area); the carried state keeps its layout.
-template <typename real, int PF, bool AER, bool LDSC, bool PACK = false, typename ST, typename PT>
+template <typename real, int PF, bool AER, bool LDSC, bool PACK = false, bool TB = false, typename ST, typename PT>
 __device__ __forceinline__ void cloudsc_kcache_persistent_body(cptr<KArgs<real, ST>> ka, cptr<PT> cpar,
                                                                const PersistArgs<real>& P,
                                                                const PackArgs& G = PackArgs{1, 0, 0}) {
@@ -1611,7 +1668,7 @@ __device__ __forceinline__ void cloudsc_kcache_persistent_body(cptr<KArgs<real, 
 #endif
       if (active) carry_io(P.state, ust, (size_t)nproma, lo_c, cs, false);
     }
-    if (active) kcache_levels<real, PF, AER>(ka, cpar, b, lo, P.lev[seg], P.lev[seg + 1], cs);
+    if (active) kcache_levels<real, PF, AER, TB>(ka, cpar, b, lo, P.lev[seg], P.lev[seg + 1], cs);
     const auto lo_e = lane_here(lo);   // packed: the offsets below formed here, not live across the levels
     if constexpr (PACK) lo_c = (lo_e.sb * (unsigned)kCarryN + lo_e.jb) / (unsigned)sizeof(ST) * (unsigned)sizeof(real);
     if (seg + 1 < P.nseg) {

@@ -57,7 +57,8 @@
 typedef struct {
   int numomp, ngptot, nproma, ngpus, precision, variant, reps, warmup;
   int transfer, chunk_blocks, nstreams, exact_libm;
-  int fields_caller;              /* --fields caller: caller-owned field sets instead of a state */
+  int fields_caller;              /* --fields caller | tendbuf: caller-owned field sets instead of a state */
+  int tend_planes;                /* --fields tendbuf: planes per block of the two tendency buffers (0: not tendbuf) */
   int place;                      /* placement search: 1 on, 0 off, -1 auto (on when reps > 1) */
   int narrow_pack;                /* NPROMA <= 32 packed into full waves: 1 on, 0 off, -1 the library's default */
   double energy_s;                /* --energy: seconds of back-to-back launches sampled for board power */
@@ -70,6 +71,7 @@ typedef struct {
   int device, ngptot, nproma, precision, variant, reps, warmup;
   int libm_bit;                   /* CLOUDSC_FP32_EXACT_LIBM or 0 */
   int caller, place_on, aerosols; /* --fields caller; its placement search; aerosol inputs allocated */
+  int tend_planes;                /* --fields tendbuf: the step runs on two packed tendency buffers of that many planes */
   double energy_s;
   long long col_offset;
   const cloudsc_template_t *tmpl;
@@ -132,6 +134,10 @@ static void usage(const char *prog) {
           "                        CUDA driver's shape on caller-owned device fields, per shard\n"
           "                        cloudsc_fields_alloc, _expand, cloudsc_gpu_run, cloudsc_gpu_check,\n"
           "                        cloudsc_fields_validate (not with --transfer or --variant cpu)\n"
+          "  --fields tendbuf      caller, with the tendencies in the reference Fortran drivers' two packed\n"
+          "                        buffers: tendency_tmp_* packed into a BUFFER_TMP, cloudsc_gpu_run_tendbuf,\n"
+          "                        BUFFER_LOC unpacked before the validation (kseg and kcache only)\n"
+          "  --tend-planes N       --fields tendbuf: planes per block of the two buffers, 8..64 (default 8)\n"
           "  --transfer            host-buffer path: block-layout arrays in host memory,\n"
           "                        H2D -> kernel -> D2H per chunk, overlapped on streams\n"
           "                        (TOTAL includes the transfers, like cloudsc_driver.cu)\n"
@@ -200,7 +206,16 @@ static int parse(int argc, char **argv, options_t *o) {
       NEEDV();
       if (!strcmp(v, "state")) o->fields_caller = 0;
       else if (!strcmp(v, "caller")) o->fields_caller = 1;
+      else if (!strcmp(v, "tendbuf")) o->fields_caller = 2;
       else { fprintf(stderr, "bad --fields %s\n", v); return -1; }
+    }
+    else if (!strcmp(a, "--tend-planes")) {
+      NEEDV();
+      o->tend_planes = atoi(v);
+      if (o->tend_planes < CLOUDSC_TENDBUF_PLANES_MIN || o->tend_planes > CLOUDSC_TENDBUF_PLANES_MAX) {
+        fprintf(stderr, "bad --tend-planes %s\n", v);
+        return -1;
+      }
     }
     else if (!strcmp(a, "--fp32-exact-libm")) o->exact_libm = 1;
     else if (!strcmp(a, "--chunk")) { NEEDV(); o->chunk_blocks = atoi(v); }
@@ -344,6 +359,14 @@ static void *hip_sym(const char *name) {
   return hip ? dlsym(hip, name) : NULL;
 }
 
+/* one step of a --fields caller | tendbuf shard on the field set f (tendbuf: its tendencies in the buffers) */
+static int caller_step(const shard_t *s, int variant, int klev, const cloudsc_fields_t *f, void *ws) {
+  if (s->tend_planes)
+    return cloudsc_gpu_run_tendbuf(s->device, NULL, s->precision, variant, s->ngptot, s->nproma, klev, s->tend_planes, f,
+                                   ws);
+  return cloudsc_gpu_run(s->device, NULL, s->precision, variant, s->ngptot, s->nproma, klev, f, ws);
+}
+
 static void shard_caller(shard_t *s) {
   int (*set_device)(int) = (int (*)(int))hip_sym("hipSetDevice");
   int (*dmalloc)(void **, size_t) = (int (*)(void **, size_t))hip_sym("hipMalloc");
@@ -354,6 +377,13 @@ static void shard_caller(shard_t *s) {
   memset(&f, 0, sizeof(f));
   memset(&plude, 0, sizeof(plude));
   void *ws = NULL;
+  /* --fields tendbuf: g is f with the eight tendency members bound to the two buffers; tmp_* / loc_* hold
+   * the tendency_tmp_* / tendency_loc_* members alone, of the separate arrays (sep) and of the buffers (buf) */
+  const int tp = s->tend_planes;
+  void *buf_tmp = NULL, *buf_loc = NULL;
+  cloudsc_fields_t g, tmp_sep, tmp_buf, loc_sep, loc_buf;
+  memset(&tmp_sep, 0, sizeof(tmp_sep)); memset(&tmp_buf, 0, sizeof(tmp_buf));
+  memset(&loc_sep, 0, sizeof(loc_sep)); memset(&loc_buf, 0, sizeof(loc_buf));
   s->rc = set_device && dmalloc && dmemset && dfree ? CLOUDSC_OK : CLOUDSC_EHIP;
   if (!s->rc)
     s->rc = cloudsc_fields_alloc(s->device, s->precision, s->ngptot, s->nproma, klev,
@@ -363,11 +393,31 @@ static void shard_caller(shard_t *s) {
   const long long wsb = cloudsc_gpu_scratch_bytes(s->precision, s->variant, s->ngptot, s->nproma, klev);
   if (!s->rc && wsb < 0) s->rc = CLOUDSC_EINVAL;
   if (!s->rc && wsb > 0 && (set_device(s->device) || dmalloc(&ws, (size_t)wsb) || dmemset(ws, 0, 256))) s->rc = CLOUDSC_ENOMEM;
+  g = f;
+  if (!s->rc && tp) {
+    const size_t es = s->precision == CLOUDSC_FP64 ? 8 : 4;
+    const size_t nb = (size_t)(s->ngptot / s->nproma + (s->ngptot % s->nproma ? 1 : 0));
+    const size_t bytes = nb * (size_t)tp * (size_t)klev * (size_t)s->nproma * es;
+    if (set_device(s->device) || dmalloc(&buf_tmp, bytes) || dmalloc(&buf_loc, bytes)) s->rc = CLOUDSC_ENOMEM;
+    if (!s->rc) s->rc = cloudsc_tendbuf_bind(&g, s->precision, s->nproma, klev, buf_tmp, buf_loc);
+    tmp_sep.tendency_tmp_t = f.tendency_tmp_t; tmp_sep.tendency_tmp_a = f.tendency_tmp_a;
+    tmp_sep.tendency_tmp_q = f.tendency_tmp_q; tmp_sep.tendency_tmp_cld = f.tendency_tmp_cld;
+    tmp_buf.tendency_tmp_t = g.tendency_tmp_t; tmp_buf.tendency_tmp_a = g.tendency_tmp_a;
+    tmp_buf.tendency_tmp_q = g.tendency_tmp_q; tmp_buf.tendency_tmp_cld = g.tendency_tmp_cld;
+    loc_sep.tendency_loc_t = f.tendency_loc_t; loc_sep.tendency_loc_a = f.tendency_loc_a;
+    loc_sep.tendency_loc_q = f.tendency_loc_q; loc_sep.tendency_loc_cld = f.tendency_loc_cld;
+    loc_buf.tendency_loc_t = g.tendency_loc_t; loc_buf.tendency_loc_a = g.tendency_loc_a;
+    loc_buf.tendency_loc_q = g.tendency_loc_q; loc_buf.tendency_loc_cld = g.tendency_loc_cld;
+    /* pack the expanded tendency_tmp_* into BUFFER_TMP (stream order: before the first step) */
+    if (!s->rc)
+      s->rc = cloudsc_fields_convert_tendbuf(s->device, NULL, s->ngptot, klev, s->precision, s->nproma, 0, &tmp_sep,
+                                             s->precision, s->nproma, tp, &tmp_buf);
+  }
   plude.plude = f.plude;
   /* plude is INOUT: expanded again before every step, outside the timing */
   for (int r = 0; r < s->warmup && !s->rc; r++) {
     if (r) s->rc = cloudsc_fields_expand(s->device, NULL, s->precision, s->ngptot, s->nproma, s->col_offset, s->tmpl, &plude);
-    if (!s->rc) s->rc = cloudsc_gpu_run(s->device, NULL, s->precision, variant, s->ngptot, s->nproma, klev, &f, ws);
+    if (!s->rc) s->rc = caller_step(s, variant, klev, &g, ws);
     if (!s->rc) s->rc = cloudsc_gpu_check(s->device, NULL, s->variant, ws);
   }
   pthread_barrier_wait(s->barrier);
@@ -378,18 +428,23 @@ static void shard_caller(shard_t *s) {
       s->rc = cloudsc_fields_expand(s->device, NULL, s->precision, s->ngptot, s->nproma, s->col_offset, s->tmpl, &plude);
     if (!s->rc) s->rc = cloudsc_gpu_check(s->device, NULL, CLOUDSC_VARIANT_KCACHE, NULL);   /* the expansion is done */
     const double k0 = now();
-    if (!s->rc) s->rc = cloudsc_gpu_run(s->device, NULL, s->precision, variant, s->ngptot, s->nproma, klev, &f, ws);
+    if (!s->rc) s->rc = caller_step(s, variant, klev, &g, ws);
     if (!s->rc) s->rc = cloudsc_gpu_check(s->device, NULL, s->variant, ws);
     s->kernel_ms[r] = (float)(1e3 * (now() - k0));   /* launch to the check's return, on the host clock */
     timed += now() - k0;
   }
   s->t_end = s->t_start + timed;
   pthread_barrier_wait(s->barrier);
+  if (!s->rc && tp)   /* unpack BUFFER_LOC into the separate tendency_loc_* arrays the validation reads */
+    s->rc = cloudsc_fields_convert_tendbuf(s->device, NULL, s->ngptot, klev, s->precision, s->nproma, tp, &loc_buf,
+                                           s->precision, s->nproma, 0, &loc_sep);
   if (!s->rc && s->ref)
     s->rc = cloudsc_fields_validate(s->device, NULL, s->precision, s->ngptot, s->nproma, klev, s->col_offset, &f, s->ref,
                                     s->stats);
   if (s->rc) snprintf(s->err, sizeof(s->err), "%s", cloudsc_last_hip_error());
   if (ws) dfree(ws);
+  if (buf_tmp) dfree(buf_tmp);
+  if (buf_loc) dfree(buf_loc);
   cloudsc_fields_free(s->device, &f);
 }
 
@@ -623,6 +678,18 @@ int main(int argc, char **argv) {
     return rc ? EXIT_FAILURE : EXIT_SUCCESS;
   }
 
+  if (o.tend_planes && o.fields_caller != 2) {
+    fprintf(stderr, "dwarf-cloudsc-amd: --tend-planes goes with --fields tendbuf\n");
+    cloudsc_io_free(&ds);
+    return EXIT_FAILURE;
+  }
+  if (o.fields_caller == 2 && (o.transfer || (o.variant != CLOUDSC_VARIANT_KSEG && o.variant != CLOUDSC_VARIANT_KCACHE))) {
+    fprintf(stderr, "dwarf-cloudsc-amd: --fields tendbuf runs --variant kseg|kcache on device fields (no --transfer, "
+                    "no cpu, scc or scc-private)\n");
+    cloudsc_io_free(&ds);
+    return EXIT_FAILURE;
+  }
+  if (o.fields_caller == 2 && !o.tend_planes) o.tend_planes = CLOUDSC_TENDBUF_PLANES_MIN;
   if (o.fields_caller && (o.transfer || o.variant == VARIANT_CPU)) {
     fprintf(stderr, "dwarf-cloudsc-amd: --fields caller runs the GPU variants on device fields (no --transfer, no "
                     "--variant cpu)\n");
@@ -710,6 +777,7 @@ int main(int argc, char **argv) {
     s->libm_bit = o.exact_libm ? CLOUDSC_FP32_EXACT_LIBM : 0;
     s->energy_s = o.energy_s;
     s->caller = o.fields_caller; s->place_on = place;
+    s->tend_planes = o.fields_caller == 2 ? o.tend_planes : 0;
     s->aerosols = ds.params.laericesed || ds.params.laericeauto;
     s->tmpl = &tmpl; s->params = &ds.params; s->ref = ds.has_reference ? &ref : NULL; s->barrier = &bar;
     s->kernel_ms = (float *)calloc((size_t)o.reps, sizeof(float));

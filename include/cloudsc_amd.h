@@ -299,6 +299,88 @@ int cloudsc_cpu_fields_convert(int nthreads, int ngptot, int klev,
                                int src_precision, int src_nproma, const cloudsc_fields_t *src,
                                int dst_precision, int dst_nproma, const cloudsc_fields_t *dst);
 
+/* ------------------------------------------------------------------------ */
+/* Packed tendency buffers (the reference's Fortran drivers)                 */
+/* ------------------------------------------------------------------------ */
+/* The reference's Fortran GPU, Loki and Python-interface drivers keep the
+ * tendencies in two packed buffers (cloudsc_driver_gpu_scc_mod.F90:50-52,146-147),
+ *
+ *   BUFFER_TMP(NPROMA, NLEV, 3+NCLV, NGPBLKS), BUFFER_LOC(NPROMA, NLEV, 3+NCLV, NGPBLKS)
+ *
+ * whose planes 1..8 are T, A, Q, CLD(1..5): in C order [nblocks][planes][klev]
+ * [nproma].  Inside a block a plane is an ordinary [klev][nproma] level field
+ * and the five CLD planes an ordinary [5][klev][nproma] species field; only the
+ * block stride differs: tend_planes * klev * nproma elements instead of klev *
+ * nproma (5 * klev * nproma).  The "tendbuf" entry points take field sets whose
+ * eight tendency members -- tendency_tmp_t/q/a/cld, tendency_loc_t/q/a/cld --
+ * have that stride: each member points at the start of its plane in block 0, so
+ * which plane a member is, and in which buffer, is the caller's choice.  Every
+ * other member is a plain array as everywhere else.  tend_planes is the
+ * number of planes per block, 8..64 (IFS builds carry more than 3 + NCLV). */
+#define CLOUDSC_TENDBUF_PLANES_MIN 8        /* 3 + CLOUDSC_NCLV                */
+#define CLOUDSC_TENDBUF_PLANES_MAX 64
+#define CLOUDSC_TENDBUF_T 0                 /* reference plane order, 0-based  */
+#define CLOUDSC_TENDBUF_A 1
+#define CLOUDSC_TENDBUF_Q 2
+#define CLOUDSC_TENDBUF_CLD 3
+
+/* Set the eight tendency members of *fields to the plane starts of the two
+ * buffers in the reference's plane order (CLOUDSC_TENDBUF_*): tendency_tmp_x =
+ * buffer_tmp + plane * klev * nproma elements of the precision's storage type,
+ * tendency_loc_x likewise in buffer_loc.  Pointer arithmetic only: host or
+ * device buffers, any tend_planes.  The other members are left as they are.
+ * CLOUDSC_EINVAL: a NULL argument, an unknown precision, nproma or klev < 1. */
+int cloudsc_tendbuf_bind(cloudsc_fields_t *fields, int precision, int nproma, int klev,
+                         const void *buffer_tmp, void *buffer_loc);
+
+/* cloudsc_gpu_run on a field set whose eight tendency members have the block
+ * stride tend_planes * klev * nproma (above); everything else -- arguments,
+ * asynchrony, workspace, narrow-block packing, outputs, cloudsc_gpu_check,
+ * cloudsc_gpu_scratch_bytes, cloudsc_gpu_launch_geometry -- is cloudsc_gpu_run's,
+ * and the output bits are those of cloudsc_gpu_run on the same values in
+ * separate arrays.  Only the elements of the planes the members point at are
+ * touched, and of those only the lanes of real columns: other planes of a
+ * buffer and padding lanes keep their contents.  A packed launch whose lane
+ * offsets in a buffer would not fit 32 bits -- pack * tend_planes * klev *
+ * nproma * 8 >= 2^32, i.e. KLEV >= 131072 at 64 planes -- runs unpacked;
+ * cloudsc_gpu_launch_geometry does not take tend_planes and reports the
+ * packed geometry for such a shape, the one case where it differs.
+ * KCACHE and KSEG only: CLOUDSC_VARIANT_SCC and CLOUDSC_VARIANT_SCC_PRIVATE
+ * have no tendency buffer form and return CLOUDSC_EINVAL.  So does the option
+ * bit CLOUDSC_FP32_EXACT_LIBM: fp32 runs its default exp/pow here.  Also
+ * CLOUDSC_EINVAL: tend_planes outside 8..64 and every argument error of
+ * cloudsc_gpu_run; all of these are checked before the first HIP call. */
+int cloudsc_gpu_run_tendbuf(int device, void *stream, int precision, int variant, int ngptot, int nproma,
+                            int klev, int tend_planes, const cloudsc_fields_t *device_fields, void *scratch);
+
+/* cloudsc_cpu_run_precision (below) on such a field set in HOST memory: the
+ * same phase functions with the same block stride, the same bits as
+ * cloudsc_cpu_run_precision on separate arrays.  Needs no GPU. */
+int cloudsc_cpu_run_tendbuf(int nthreads, int precision, int ngptot, int nproma, int klev, int tend_planes,
+                            const cloudsc_params_t *params, const cloudsc_fields_t *host_fields);
+
+/* cloudsc_fields_convert with the tendency members of either side in packed
+ * buffers: where src_tend_planes (dst_tend_planes) is non-zero, the eight
+ * tendency members of src (dst) have the block stride *_tend_planes * klev *
+ * *_nproma elements; 0 means separate arrays.  One launch packs (0 -> n),
+ * unpacks (n -> 0) or re-packs (n -> m), combined if wanted with re-blocking
+ * and re-typing; with 0 and 0 it is cloudsc_fields_convert.  Planes no member
+ * points at and padding lanes are never written.  CLOUDSC_EINVAL as
+ * cloudsc_fields_convert, and for a non-zero *_tend_planes outside 8..64.
+ * (Comparison, validation and expansion have no packed form: unpack first.) */
+int cloudsc_fields_convert_tendbuf(int device, void *stream, int ngptot, int klev,
+                                   int src_precision, int src_nproma, int src_tend_planes,
+                                   const cloudsc_fields_t *src,
+                                   int dst_precision, int dst_nproma, int dst_tend_planes,
+                                   const cloudsc_fields_t *dst);
+
+/* The same on HOST arrays, as cloudsc_cpu_fields_convert.  Needs no GPU. */
+int cloudsc_cpu_fields_convert_tendbuf(int nthreads, int ngptot, int klev,
+                                       int src_precision, int src_nproma, int src_tend_planes,
+                                       const cloudsc_fields_t *src,
+                                       int dst_precision, int dst_nproma, int dst_tend_planes,
+                                       const cloudsc_fields_t *dst);
+
 /* Bytes of device scratch a variant needs for (ngptot, nproma, klev, precision); 0 for KCACHE. */
 long long cloudsc_gpu_scratch_bytes(int precision, int variant, int ngptot, int nproma, int klev);
 
