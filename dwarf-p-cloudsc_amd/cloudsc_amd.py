@@ -504,6 +504,8 @@ def gpu_lib(path: Optional[str] = None):
     lib.cloudsc_debug_host_pipeline_mapping.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.cloudsc_debug_host_pinned.argtypes = [C.c_void_p, C.c_longlong]
     lib.cloudsc_debug_fp32_libm.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong]
+    lib.cloudsc_debug_fp64_libm.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_longlong]
     _lib = lib
     return lib
 

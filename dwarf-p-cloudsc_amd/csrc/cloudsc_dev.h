@@ -211,7 +211,8 @@ struct LdsLibmTabs {
   }
 };
 // The complete functions, out of line, for the arguments outside the hot
-// range (tables from __constant__ memory; never taken by CLOUDSC's data).
+// range (tables from __constant__ memory; never taken by CLOUDSC's data:
+// cloudsc_debug_fp64_libm runs them on every argument for the tests).
 struct ConstLibmTabs {
   __device__ __forceinline__ cloudsc_libm::ExpAddends exp_addends() const {
     return {cloudsc_libm::kC4, cloudsc_libm::kC2};
@@ -380,8 +381,29 @@ CLOUDSC_HD real cl_pow(const P&, typename std::common_type<real>::type x, typena
 // repeated divisor is shared (CSE).  div_scale only rescales operands whose
 // exponents are near the ends of the range (quotient or divisor beyond about
 // 2^+-1000, denormals), and the fix-up only changes non-finite or zero
-// divisors, so for every finite, normal-range operand pair the result is
-// bit-identical to a / b (correctly rounded).  CLOUDSC's divisions are all
+// operands.  What holds, and what tests/test_device_math_gpu.py asserts on the
+// device (cloudsc_debug_fp64_libm / cloudsc_debug_fp32_libm):
+//  - n and d normal, the quotient finite and normal, the reciprocal normal
+//    (|d| <= 2^1022; fp32 2^126) and the residual fma(-d, q, n) exact (|n| >=
+//    2^-967; fp32 2^-102): the result is bit-identical to n / d (correctly
+//    rounded).  Asserted for exponents of n and d in [-500, 500] (fp32: |d| in
+//    [2^-126, 2^126), |n| in [2^-100, 2^100], quotients down to 2^-126).
+//  - n = +-0 with such a d: a zero, with the IEEE sign EXCEPT -0 / +d, which
+//    is +0 (IEEE: -0).  q = -0 * r = -0 is right, but the residual
+//    fma(-d, -0, -0) is (+0) + (-0) = +0 and the last step fma(+0, r, -0) is
+//    (+0) + (-0) = +0.  (+0 / -d keeps its -0: there the last sum is
+//    (-0) + (-0).)  The same in fp32 and in the Recip forms below.  No
+//    division of the physics lets that sign reach an output: where a numerator
+//    can be -0 (a product of a zero and a negative factor, or a negated zero:
+//    the supersaturation and evaporation terms, zacond, the solver's -sb_ls /
+//    d_l and -sb_is / d_i) the quotient goes into fmax(., 0), fabs, or a
+//    product that is added to a value that is not -0, and x + (+-0) has one
+//    result for every such x (the division paragraph of §3.9).
+//  - outside that: a subnormal or zero divisor (v_rcp_f64 overflows), a
+//    non-finite operand or a quotient that overflows gives NaN where IEEE
+//    gives +-inf or 0; huge divisors and subnormal quotients are not asserted.
+//    The host form is n / d itself, IEEE everywhere.
+// CLOUDSC's divisions are all
 // guarded (divisors are max(x, eps), 1 + positive sums, or branch-protected
 // ratios of physical quantities), and the A/B identity check
 // (tools/ab_compare.py: reference state, scenarios, random perturbations,
@@ -416,8 +438,10 @@ CLOUDSC_HD float cl_div(float n, float d) {
 }
 // A divisor together with its refined reciprocal, for divisions that share a
 // divisor: cl_div(n, cl_recip(d)) runs exactly the steps of cl_div(n, d) with
-// the same reciprocal r, so the quotient is bit-identical -- the reciprocal
-// (v_rcp + its Newton steps) is computed once instead of once per division.
+// the same reciprocal r, so the quotient is bit-identical to cl_div(n, d) for
+// every operand pair, inside cl_div's domain and outside it (-0 / +d = +0
+// included) -- the reciprocal (v_rcp + its Newton steps) is computed once
+// instead of once per division.
 template <typename real>
 struct Recip {
   real d, r;
@@ -470,7 +494,10 @@ CLOUDSC_HD float cl_div(float n, const Recip<float>& rd) {
 // with the quarter-rate v_rcp).  With r = RN(1/d) the corrected quotient is
 // n/d correctly rounded (Markstein's theorem; tools/div_const_check.c: 0
 // mismatches over 1.4e8 numerators for CLOUDSC's divisors, and 1000 random
-// divisors, in fp64 and fp32).
+// divisors, in fp64 and fp32).  Domain and zero numerators as for cl_div: the
+// same bits as cl_div(n, d) wherever that is n / d, and -0 / +d = +0 here too
+// (tests/test_device_math_gpu.py runs this form on the device with the
+// compiler's IEEE 1 / d).
 // (real is deduced from the divisor; the numerator converts, e.g. from an LDS-carried value)
 template <typename real>
 CLOUDSC_HD real cl_div_known(typename std::common_type<real>::type n, real d, real rcp_d) {

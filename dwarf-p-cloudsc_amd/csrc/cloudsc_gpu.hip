@@ -1051,6 +1051,65 @@ int cloudsc_debug_fp32_libm(int device, int which, const float* x, const float* 
   return CLOUDSC_OK;
 }
 
+// Diagnostic: the double-precision device primitives of the kernels, element-wise
+// (tests/test_device_math_gpu.py compares them bit for bit with the host C
+// library's exp/pow and IEEE division / sqrt).  Every case calls the kernels'
+// own function.  Every thread copies the tables before the bounds check (the
+// copy ends in a barrier), with the stride of the launch's block size.
+__global__ void __launch_bounds__(256) fp64_libm_kernel(int which, const double* x, const double* y, double* out,
+                                                        long long n) {
+  libm_tables_to_lds<double>();
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double a = x[i], b = y[i];
+  double r;
+  switch (which) {
+    case 0: r = cl_exp_impl(a); break;
+    case 1: r = cl_powr(a, b); break;
+    case 2:
+    case 3: {
+      double r0, r1;
+      cloudsc_libm::exp_pair_split(a, b, &r0, &r1, LdsLibmTabs{}, DevLibmCold{});
+      r = which == 2 ? r0 : r1;
+      break;
+    }
+    case 4: r = cl_div(a, b); break;
+    case 5: r = cl_div(a, cl_recip(b)); break;
+    case 6: r = cl_div(a, Recip<double>{b, 1.0 / b}); break;   // cl_div_known / cl_div_lit: r = RN(1/d)
+    case 7: r = cl_sqrt_p<double>(DevParamsT<double, false>{}, a); break;
+    case 8: r = cl_exp_cold(a); break;
+    default: r = cl_pow_cold(a, b); break;
+  }
+  out[i] = r;
+}
+
+int cloudsc_debug_fp64_libm(int device, int which, int block_threads, const double* x, const double* y, double* out,
+                            long long n) {
+  const bool reads_y = which != 0 && which != 7 && which != 8;
+  if (which < 0 || which > 9 || !x || !out || n <= 0 || (reads_y && !y)) return CLOUDSC_EINVAL;
+  if (block_threads != 64 && block_threads != 128 && block_threads != 256) return CLOUDSC_EINVAL;
+  if ((n + block_threads - 1) / block_threads > 0x7fffffffLL) return CLOUDSC_EINVAL;
+  int nd = 0;
+  if (hipGetDeviceCount(&nd) != hipSuccess || device < 0 || device >= nd) return CLOUDSC_ENODEV;
+  HIPCHK(hipSetDevice(device));
+  double *dx = nullptr, *dy = nullptr, *dout = nullptr;
+  const size_t bytes = (size_t)n * sizeof(double);
+  hipError_t e = hipMalloc(&dx, bytes);
+  if (e == hipSuccess) e = hipMalloc(&dy, bytes);
+  if (e == hipSuccess) e = hipMalloc(&dout, bytes);
+  if (e == hipSuccess) e = hipMemcpy(dx, x, bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dy, reads_y ? y : x, bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(fp64_libm_kernel, dim3((unsigned)((n + block_threads - 1) / block_threads)),
+                       dim3(block_threads), 0, nullptr, which, dx, dy, dout, n);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost);
+  (void)hipFree(dx); (void)hipFree(dy); (void)hipFree(dout);
+  if (e != hipSuccess) return hip_fail(e, "fp64 libm diagnostic");
+  return CLOUDSC_OK;
+}
+
 long long cloudsc_abi_sizeof(int which) {
   switch (which) {
     case 0: return sizeof(cloudsc_params_t);

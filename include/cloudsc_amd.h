@@ -450,6 +450,23 @@ int cloudsc_debug_set_state_layout(long long stagger, unsigned alloc_flags);
  * 5 the exact kernels' division.  y is read for 1, 3, 4 and 5 only. */
 int cloudsc_debug_fp32_libm(int device, int which, const float *x, const float *y, float *out, long long n);
 
+/* Diagnostic: the kernels' double-precision device primitives, element-wise
+ * over n host values, one thread per element in workgroups of block_threads
+ * (64, 128 or 256, CLOUDSC_EINVAL otherwise; every thread copies the exp/pow
+ * tables to LDS first, with that stride).  which =
+ *   0 exp(x) (hot body from the LDS tables, range check after it)
+ *   1 pow(x, y) (the split form)
+ *   2, 3 the first / second result of the paired exp of (x, y)
+ *   4 x / y (hardware reciprocal, two Newton steps, one correction)
+ *   5 x / y with the shared-reciprocal form (cl_recip)
+ *   6 x / y with the known-divisor form, the reciprocal RN(1 / y)
+ *   7 sqrt(x) as the exact kernels call it
+ *   8, 9 the complete out-of-line exp(x), pow(x, y) (constant-memory tables)
+ *        on every argument, in range or not.
+ * y is read for every code except 0, 7 and 8. */
+int cloudsc_debug_fp64_libm(int device, int which, int block_threads, const double *x, const double *y, double *out,
+                            long long n);
+
 /* Human-readable message for an error code; last HIP error string of this thread. */
 const char *cloudsc_strerror(int code);
 const char *cloudsc_last_hip_error(void);
