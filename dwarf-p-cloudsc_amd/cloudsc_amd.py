@@ -146,6 +146,20 @@ class Placement(C.Structure):
 
 PLACE_NONE = 1
 ALLOC_AEROSOLS = 2
+# output selection (cloudsc_gpu_run_outputs, cloudsc_cpu_run_outputs, cloudsc_fields_alloc_outputs)
+OUTPUTS_ALL, OUTPUTS_PROGNOSTIC = 0, 1
+# the ten diagnostic flux outputs OUTPUTS_PROGNOSTIC leaves out: the running sums of section 8
+DIAGNOSTIC_FLUX_FIELDS = ("pfsqlf", "pfsqif", "pfcqnng", "pfcqlng", "pfsqrf", "pfsqsf", "pfcqrng", "pfcqsng",
+                          "pfsqltur", "pfsqitur")
+
+
+def selected_outputs(outputs: int = OUTPUTS_ALL) -> tuple:
+    """The output members (plude included) an output selection writes, in member order: all 21, or the
+    eleven OUTPUTS_PROGNOSTIC keeps."""
+    if outputs not in (OUTPUTS_ALL, OUTPUTS_PROGNOSTIC):
+        raise ValueError("unknown output selection: %r" % (outputs,))
+    return tuple(n for n in list(INOUT_FIELDS) + list(OUTPUT_FIELDS)
+                 if outputs == OUTPUTS_ALL or n not in DIAGNOSTIC_FLUX_FIELDS)
 
 
 class LaunchGeometry(C.Structure):
@@ -485,6 +499,9 @@ def gpu_lib(path: Optional[str] = None):
         [C.c_int] * 3 + [C.POINTER(Fields)]
     lib.cloudsc_cpu_fields_convert_tendbuf.argtypes = [C.c_int] * 6 + [C.POINTER(Fields)] + [C.c_int] * 3 + \
         [C.POINTER(Fields)]
+    lib.cloudsc_gpu_run_outputs.argtypes = [C.c_int, C.c_void_p] + [C.c_int] * 6 + [C.POINTER(Fields), C.c_void_p]
+    lib.cloudsc_cpu_run_outputs.argtypes = [C.c_int] * 6 + [C.POINTER(Params), C.POINTER(Fields)]
+    lib.cloudsc_fields_alloc_outputs.argtypes = [C.c_int] * 7 + [C.POINTER(Fields), C.POINTER(Placement)]
     lib.cloudsc_fields_compare.argtypes = lib.cloudsc_fields_convert.argtypes + [C.POINTER(FieldDiff)]
     lib.cloudsc_cpu_fields_compare.argtypes = lib.cloudsc_cpu_fields_convert.argtypes + [C.POINTER(FieldDiff)]
     lib.cloudsc_fields_validate.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong,
@@ -636,6 +653,23 @@ def cpu_run_tendbuf(params: "Params", f: "Fields", precision: int, ngptot: int, 
     """cloudsc_cpu_run_tendbuf: the CPU variant on HOST fields whose tendency members are planes of packed
     buffers (precision FP64 or MIXED)."""
     check(gpu_lib().cloudsc_cpu_run_tendbuf(nthreads, precision, ngptot, nproma, klev, tend_planes, C.byref(params),
+                                            C.byref(f)))
+
+
+def gpu_run_outputs(f: "Fields", precision: int, variant: int, outputs: int, ngptot: int, nproma: int, klev: int,
+                    scratch=None, device: int = 0, stream=None) -> None:
+    """cloudsc_gpu_run_outputs: one step on DEVICE fields with an output selection.  OUTPUTS_ALL is
+    cloudsc_gpu_run; with OUTPUTS_PROGNOSTIC the DIAGNOSTIC_FLUX_FIELDS members are neither read nor written
+    (they may be None).  Asynchronous on `stream`; KSEG callers follow it with cloudsc_gpu_check."""
+    check(gpu_lib().cloudsc_gpu_run_outputs(device, stream, precision, variant, outputs, ngptot, nproma, klev,
+                                            C.byref(f), scratch))
+
+
+def cpu_run_outputs(params: "Params", f: "Fields", precision: int, outputs: int, ngptot: int, nproma: int,
+                    klev: int, nthreads: int = 0) -> None:
+    """cloudsc_cpu_run_outputs: the CPU variant on HOST fields with an output selection (precision FP64 or
+    MIXED)."""
+    check(gpu_lib().cloudsc_cpu_run_outputs(nthreads, precision, outputs, ngptot, nproma, klev, C.byref(params),
                                             C.byref(f)))
 
 
@@ -987,17 +1021,24 @@ class DeviceFields:
     tend_planes (8..64): also allocate two packed tendency buffers of that many planes per block
     (self.buffer_tmp, self.buffer_loc, plain hipMalloc) and bind the eight tendency members of self.f to
     them in the reference's plane order -- the set then runs with gpu_run_tendbuf; self.separate keeps the
-    set with the tendency members as the separate arrays cloudsc_fields_alloc made."""
+    set with the tendency members as the separate arrays cloudsc_fields_alloc made.
+    outputs=OUTPUTS_PROGNOSTIC: cloudsc_fields_alloc_outputs -- the DIAGNOSTIC_FLUX_FIELDS members stay None and
+    the placement search runs over the eleven other outputs; the set runs with gpu_run_outputs."""
 
     def __init__(self, ngptot: int, nproma: int, klev: int, precision: int = FP64, device: int = 0,
-                 place: bool = True, aerosols: bool = False, tend_planes: int = 0):
+                 place: bool = True, aerosols: bool = False, tend_planes: int = 0, outputs: int = OUTPUTS_ALL):
         self.lib = gpu_lib()
         self.ngptot, self.nproma, self.klev, self.precision, self.device = ngptot, nproma, klev, precision, device
         self.f = Fields()
         self.report = Placement()
         flags = (0 if place else PLACE_NONE) | (ALLOC_AEROSOLS if aerosols else 0)
-        check(self.lib.cloudsc_fields_alloc(device, precision, ngptot, nproma, klev, flags, C.byref(self.f),
-                                            C.byref(self.report)))
+        self.outputs = outputs
+        if outputs == OUTPUTS_ALL:
+            check(self.lib.cloudsc_fields_alloc(device, precision, ngptot, nproma, klev, flags, C.byref(self.f),
+                                                C.byref(self.report)))
+        else:
+            check(self.lib.cloudsc_fields_alloc_outputs(device, precision, ngptot, nproma, klev, flags, outputs,
+                                                        C.byref(self.f), C.byref(self.report)))
         self.hip = _hip()
         self.tend_planes, self.separate, self.buffer_tmp, self.buffer_loc = 0, None, None, None
         if tend_planes:

@@ -38,8 +38,9 @@ struct HostColumn {
 };
 
 // real: the compute type, S: the fields' element type (float under double = CLOUDSC_MIXED);
-// TB: the tendency members are planes of packed buffers and A is a KArgsTB (cloudsc_kcache.h)
-template <typename real, bool AER, bool TB, typename S>
+// TB: the tendency members are planes of packed buffers and A is a KArgsTB (cloudsc_kcache.h);
+// PROG: the prognostic-outputs form, the ten diagnostic flux members of A never touched (flux_level)
+template <typename real, bool AER, bool TB, bool PROG = false, typename S>
 void run_block(const DevParams<real>& c, const KArgs<real, S>& A, int b, std::vector<HostColumn<real>>& col) {
   const int nproma = A.nproma, klev = A.klev;
   const int bsize = std::min(nproma, A.ngptot - b * nproma);
@@ -52,8 +53,8 @@ void run_block(const DevParams<real>& c, const KArgs<real, S>& A, int b, std::ve
   for (int jl = 0; jl < bsize; jl++) {
     const unsigned lo = (unsigned)jl * (unsigned)sizeof(S);
     HostColumn<real>& h = col[jl];
-    init_carry<real>(h.cs);
-    flux_top(c, A, uh, lo);
+    init_carry<real, PROG>(h.cs);
+    flux_top<PROG>(c, A, uh, lo);
     h.cc = column_constants(c, A, u1, uh, lo);
     h.nb.paph_k = ldg(A.paph, uh, lo);
     h.nb.paph_n = ldg(A.paph, uh + (size_t)nproma, lo);
@@ -81,7 +82,7 @@ void run_block(const DevParams<real>& c, const KArgs<real, S>& A, int b, std::ve
       po.zcovptot_out = R(0.0);
       if (physics) physics_level(c, k, klev, ncldtop0, cur, h.nb, h.cc, ls, h.cs, po);
       store_level<TB>(A, u2, u3, k, klev, nproma, lo, physics, ls, po);
-      flux_level(c, A, uh + (size_t)(k + 1) * nproma, lo, cur, ls, po, h.nb.paph_k, h.nb.paph_n, h.cs);
+      flux_level<PROG>(c, A, uh + (size_t)(k + 1) * nproma, lo, cur, ls, po, h.nb.paph_k, h.nb.paph_n, h.cs);
       h.cs.t_prev = ls.ztp1;
       h.cs.a_prev = ls.za;
       h.cs.pap_prev = cur.pap;
@@ -101,10 +102,10 @@ void run_block(const DevParams<real>& c, const KArgs<real, S>& A, int b, std::ve
 template <typename S>
 int cpu_run(int nthreads, int ngptot, int nproma, int klev, const cloudsc_params_t* params,
             const cloudsc_fields_t* f, double* seconds, double* thread_seconds, int* thread_blocks,
-            int* thread_columns, int tend_planes = 0) {
+            int* thread_columns, int tend_planes = 0, int outputs = CLOUDSC_OUTPUTS_ALL) {
   int rc = cloudsc_impl::check_params(params);
   if (rc) return rc;
-  if (!f || !cloudsc_impl::fields_complete(f) || ngptot <= 0 || nproma <= 0 || klev < 2) return CLOUDSC_EINVAL;
+  if (!f || !cloudsc_impl::fields_complete(f, outputs) || ngptot <= 0 || nproma <= 0 || klev < 2) return CLOUDSC_EINVAL;
   const bool aer = params->laericesed || params->laericeauto;
   if (aer && (!f->pre_ice || !f->picrit_aer || !f->pnice)) return CLOUDSC_EINVAL;
   if (nthreads <= 0 && (thread_seconds || thread_blocks || thread_columns)) return CLOUDSC_EINVAL;
@@ -129,7 +130,10 @@ int cpu_run(int nthreads, int ngptot, int nproma, int klev, const cloudsc_params
     std::vector<HostColumn<double>> col((size_t)nproma);
     int icalls = 0, igpc = 0;
     for (int b = next.fetch_add(1); b < nblocks; b = next.fetch_add(1)) {
-      if (tend_planes) {
+      if (outputs == CLOUDSC_OUTPUTS_PROGNOSTIC) {   // (no combined form with the tendency buffers)
+        if (aer) run_block<double, true, false, true>(c, A, b, col);
+        else run_block<double, false, false, true>(c, A, b, col);
+      } else if (tend_planes) {
         if (aer) run_block<double, true, true>(c, A, b, col);
         else run_block<double, false, true>(c, A, b, col);
       } else if (aer) {
@@ -199,6 +203,19 @@ extern "C" int cloudsc_cpu_run_tendbuf(int nthreads, int precision, int ngptot, 
       return cpu_run<double>(nthreads, ngptot, nproma, klev, params, f, nullptr, nullptr, nullptr, nullptr, tend_planes);
     case sizeof(float):
       return cpu_run<float>(nthreads, ngptot, nproma, klev, params, f, nullptr, nullptr, nullptr, nullptr, tend_planes);
+    default: return CLOUDSC_EINVAL;
+  }
+}
+
+extern "C" int cloudsc_cpu_run_outputs(int nthreads, int precision, int outputs, int ngptot, int nproma, int klev,
+                                       const cloudsc_params_t* params, const cloudsc_fields_t* f) {
+  if (outputs != CLOUDSC_OUTPUTS_ALL && outputs != CLOUDSC_OUTPUTS_PROGNOSTIC) return CLOUDSC_EINVAL;
+  if (!cloudsc_impl::precision_computes_double(precision)) return CLOUDSC_EINVAL;   // as cloudsc_cpu_run_precision
+  switch (cloudsc_impl::precision_storage_bytes(precision)) {
+    case sizeof(double):
+      return cpu_run<double>(nthreads, ngptot, nproma, klev, params, f, nullptr, nullptr, nullptr, nullptr, 0, outputs);
+    case sizeof(float):
+      return cpu_run<float>(nthreads, ngptot, nproma, klev, params, f, nullptr, nullptr, nullptr, nullptr, 0, outputs);
     default: return CLOUDSC_EINVAL;
   }
 }

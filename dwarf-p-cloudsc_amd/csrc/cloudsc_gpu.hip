@@ -133,10 +133,10 @@ const ParamSet* device_default_params(int device) {
   return g_default[device].dev ? &g_default[device] : nullptr;
 }
 
-bool fields_complete(const cloudsc_fields_t* f) {
+bool fields_complete(const cloudsc_fields_t* f, int outputs) {
   const void* const* p = (const void* const*)f;
   for (int m = 0; m < kNumFields; m++)
-    if (!p[m] && kFieldTable[m].dir != CLOUDSC_FD_AEROSOL) return false;
+    if (!p[m] && kFieldTable[m].dir != CLOUDSC_FD_AEROSOL && output_selected(m, outputs)) return false;
   return true;
 }
 
@@ -244,6 +244,39 @@ __global__ void __launch_bounds__(256, WAVES) kseg_tendbuf_packed_entry(const KA
   const cptr<KArgs<real, S>> ka = (cptr<KArgs<real, S>>)__builtin_amdgcn_kernarg_segment_ptr();
   cloudsc_kcache_persistent_body<real, PF, AER, false, true, true>(ka, params_of<real, FAST>(ka), pa, g);
 }
+// The prognostic-outputs form (cloudsc_gpu_run_outputs with CLOUDSC_OUTPUTS_PROGNOSTIC): the same
+// bodies with PROG on (cloudsc_kcache.h, flux_level), the plain KArgs whose ten diagnostic flux
+// members are never read.  Entry points of their own for every (compute, storage) pair, in the
+// product configuration only.
+template <typename real, typename S, int WAVES, int PF, bool AER, bool FAST = false>
+__global__ void __launch_bounds__(256, WAVES) kcache_outputs_entry(const KArgs<real, S> a) {
+  (void)a;
+  libm_tables_to_lds<real>();
+  const cptr<KArgs<real, S>> ka = (cptr<KArgs<real, S>>)__builtin_amdgcn_kernarg_segment_ptr();
+  cloudsc_kcache_body<real, PF, AER, false, false, true>(ka, params_of<real, FAST>(ka));
+}
+template <typename real, typename S, int WAVES, int PF, bool AER, bool FAST = false>
+__global__ void __launch_bounds__(256, WAVES) kseg_outputs_entry(const KArgs<real, S> a, const PersistArgs<real> pa) {
+  (void)a;
+  libm_tables_to_lds<real>();
+  const cptr<KArgs<real, S>> ka = (cptr<KArgs<real, S>>)__builtin_amdgcn_kernarg_segment_ptr();
+  cloudsc_kcache_persistent_body<real, PF, AER, false, false, false, true>(ka, params_of<real, FAST>(ka), pa);
+}
+template <typename real, typename S, int WAVES, int PF, bool AER, bool FAST = false>
+__global__ void __launch_bounds__(256, WAVES) kcache_outputs_packed_entry(const KArgs<real, S> a, const PackArgs g) {
+  (void)a;
+  libm_tables_to_lds<real>();
+  const cptr<KArgs<real, S>> ka = (cptr<KArgs<real, S>>)__builtin_amdgcn_kernarg_segment_ptr();
+  cloudsc_kcache_packed_body<real, PF, AER, false, false, true>(ka, params_of<real, FAST>(ka), g);
+}
+template <typename real, typename S, int WAVES, int PF, bool AER, bool FAST = false>
+__global__ void __launch_bounds__(256, WAVES) kseg_outputs_packed_entry(const KArgs<real, S> a,
+                                                                        const PersistArgs<real> pa, const PackArgs g) {
+  (void)a;
+  libm_tables_to_lds<real>();
+  const cptr<KArgs<real, S>> ka = (cptr<KArgs<real, S>>)__builtin_amdgcn_kernarg_segment_ptr();
+  cloudsc_kcache_persistent_body<real, PF, AER, false, true, false, true>(ka, params_of<real, FAST>(ka), pa, g);
+}
 template <typename real, bool AER, bool FAST = false>
 __global__ void __launch_bounds__(256) scc_entry(const KArgs<real> a, const SccScratch<real> s) {
   (void)a;
@@ -317,15 +350,19 @@ constexpr auto kcache_kernel() {
   if constexpr (std::is_same<real, S>::value) return kcache_entry<real, WAVES, PF, AER, LDSC, FAST>;
   else return kcache_mixed_entry<WAVES, PF, AER, LDSC>;
 }
-template <typename real, typename S, int WAVES, int PF, bool AER, bool LDSC, bool FAST, bool TB = false>
+template <typename real, typename S, int WAVES, int PF, bool AER, bool LDSC, bool FAST, bool TB = false,
+          bool PROG = false>
 constexpr auto kseg_kernel() {
-  if constexpr (TB) return kseg_tendbuf_entry<real, S, WAVES, PF, AER, FAST>;
+  if constexpr (PROG) return kseg_outputs_entry<real, S, WAVES, PF, AER, FAST>;
+  else if constexpr (TB) return kseg_tendbuf_entry<real, S, WAVES, PF, AER, FAST>;
   else if constexpr (std::is_same<real, S>::value) return kseg_entry<real, WAVES, PF, AER, LDSC, FAST>;
   else return kseg_mixed_entry<WAVES, PF, AER, LDSC>;
 }
-template <typename real, typename S, int WAVES, int PF, bool AER, bool LDSC, bool FAST, bool TB = false>
+template <typename real, typename S, int WAVES, int PF, bool AER, bool LDSC, bool FAST, bool TB = false,
+          bool PROG = false>
 constexpr auto kseg_packed_kernel() {
-  if constexpr (TB) return kseg_tendbuf_packed_entry<real, S, WAVES, PF, AER, FAST>;
+  if constexpr (PROG) return kseg_outputs_packed_entry<real, S, WAVES, PF, AER, FAST>;
+  else if constexpr (TB) return kseg_tendbuf_packed_entry<real, S, WAVES, PF, AER, FAST>;
   else return kseg_packed_entry<real, S, WAVES, PF, AER, LDSC, FAST>;
 }
 // the kernel arguments of a launch: a's, with tend_planes behind them in the tendency buffer form
@@ -415,6 +452,21 @@ int launch_kcache_tendbuf(hipStream_t st, const KArgsTB<real, S>& a, int nblocks
     launch_physics(kcache_tendbuf_packed_entry<real, S, W, PF, AER, FAST>, dim3(g.ngroups), dim3(64), 0, st, ev, a, g);
   } else {
     launch_physics(kcache_tendbuf_entry<real, S, W, PF, AER, FAST>, dim3(nblocks), dim3(nproma), 0, st, ev, a);
+  }
+  return CLOUDSC_OK;
+}
+
+// the prognostic-outputs form of launch_kcache and launch_kcache_packed: the product configuration, as the
+// tendency buffer form
+template <typename real, bool AER, bool FAST, typename S>
+int launch_kcache_outputs(hipStream_t st, const KArgs<real, S>& a, int nblocks, int nproma, int pack,
+                          const LaunchEvents* ev) {
+  constexpr int W = DefaultCfg<real>::waves, PF = DefaultCfg<real>::pf;
+  if (pack > 1) {
+    const PackArgs g{pack, nblocks, (nblocks + pack - 1) / pack};
+    launch_physics(kcache_outputs_packed_entry<real, S, W, PF, AER, FAST>, dim3(g.ngroups), dim3(64), 0, st, ev, a, g);
+  } else {
+    launch_physics(kcache_outputs_entry<real, S, W, PF, AER, FAST>, dim3(nblocks), dim3(nproma), 0, st, ev, a);
   }
   return CLOUDSC_OK;
 }
@@ -521,14 +573,15 @@ int kseg_grid_size(int per_cu, int ncu, int nitems, int nseg) {
 }
 
 // pk: the packed kernel (one 64-lane workgroup per group of blocks); NULL: the unpacked one;
-// tend_planes (TB): the tendency buffer form of either
-template <typename real, int WAVES, int PF, bool AER, bool LDSC, bool FAST, bool TB = false, typename S>
+// tend_planes (TB): the tendency buffer form of either; PROG: the prognostic-outputs form of either
+template <typename real, int WAVES, int PF, bool AER, bool LDSC, bool FAST, bool TB = false, bool PROG = false,
+          typename S>
 int launch_kseg_cfg(hipStream_t st, const KArgs<real, S>& a0, const PersistArgs<real>& pa, int nproma, int nitems,
                     int* grid_out, const LaunchEvents* ev, const PackArgs* pk = nullptr, int tend_planes = 0) {
   const int nseg = pa.nseg;
   const auto a = kernel_args<TB>(a0, tend_planes);
-  auto kern = kseg_kernel<real, S, WAVES, PF, AER, LDSC, FAST, TB>();
-  auto kern_packed = kseg_packed_kernel<real, S, WAVES, PF, AER, LDSC, FAST, TB>();
+  auto kern = kseg_kernel<real, S, WAVES, PF, AER, LDSC, FAST, TB, PROG>();
+  auto kern_packed = kseg_packed_kernel<real, S, WAVES, PF, AER, LDSC, FAST, TB, PROG>();
   const int wg = pk ? 64 : kseg_wg(nproma);
   const size_t lds = LDSC ? carry_lds_bytes<real>(wg) : 0;
   // Waves per SIMD: as many as fit, but no more than whole rounds of the work
@@ -596,7 +649,7 @@ int launch_kseg(hipStream_t st, const KArgs<real, S>& a, const PersistArgs<real>
 template <typename real, bool FAST, typename ST = real>
 int launch_v(hipStream_t st, int variant, const cloudsc_fields_t* f, int ngptot, int nproma, int klev,
              void* scratch, const void* plude_in, const ParamSet& ps, KsegEpoch* ep, const LaunchEvents* ev,
-             int tend_planes) {
+             int tend_planes, int outputs) {
 #ifdef CLOUDSC_ONLY_KSEG
   if (variant != CLOUDSC_VARIANT_KSEG || ps.aer || sizeof(real) != CLOUDSC_ONLY_KSEG || sizeof(ST) != sizeof(real))
     return CLOUDSC_EINVAL;
@@ -607,6 +660,11 @@ int launch_v(hipStream_t st, int variant, const cloudsc_fields_t* f, int ngptot,
   // in the product configuration only -- a CLOUDSC_DEBUG_KNOBS build's CLOUDSC_KCACHE_CFG does not apply to it
   constexpr bool kTendbuf = !(std::is_same<real, float>::value && !FAST);
   if (tend_planes && (!kTendbuf || (variant != CLOUDSC_VARIANT_KCACHE && variant != CLOUDSC_VARIANT_KSEG)))
+    return CLOUDSC_EINVAL;
+  // outputs == CLOUDSC_OUTPUTS_PROGNOSTIC: the prognostic-outputs form, where the tendency buffer form exists
+  // and not combined with it
+  const bool prog = outputs == CLOUDSC_OUTPUTS_PROGNOSTIC;
+  if (prog && (!kTendbuf || tend_planes || (variant != CLOUDSC_VARIANT_KCACHE && variant != CLOUDSC_VARIANT_KSEG)))
     return CLOUDSC_EINVAL;
   KArgs<real, ST> a = make_kargs<real, ST>(
       f, ngptot, nproma, klev, (const DevParams<real>*)((const char*)ps.dev + (sizeof(real) == 8 ? 0 : kSpOffset)));
@@ -627,6 +685,10 @@ int launch_v(hipStream_t st, int variant, const cloudsc_fields_t* f, int ngptot,
         if constexpr (kTendbuf)
           rc = aer ? launch_kcache_tendbuf<real, true, FAST>(st, kernel_args<true>(a, tend_planes), nblocks, nproma, pack, ev)
                    : launch_kcache_tendbuf<real, false, FAST>(st, kernel_args<true>(a, tend_planes), nblocks, nproma, pack, ev);
+      } else if (prog) {
+        if constexpr (kTendbuf)
+          rc = aer ? launch_kcache_outputs<real, true, FAST>(st, a, nblocks, nproma, pack, ev)
+                   : launch_kcache_outputs<real, false, FAST>(st, a, nblocks, nproma, pack, ev);
       } else if (pack > 1)
         rc = aer ? launch_kcache_packed<real, true, FAST>(st, a, nblocks, pack, ev)
                  : launch_kcache_packed<real, false, FAST>(st, a, nblocks, pack, ev);
@@ -694,6 +756,11 @@ int launch_v(hipStream_t st, int variant, const cloudsc_fields_t* f, int ngptot,
                                                                          tend_planes)
                  : launch_kseg_cfg<real, W, PF, false, false, FAST, true>(st, a, pa, nproma, pa.nitems, &grid, ev, pkp,
                                                                           tend_planes);
+    } else if (prog) {
+      if constexpr (kTendbuf && CLOUDSC_KEEP_KERNEL(real, true, true))
+        rc = aer ? launch_kseg_cfg<real, W, PF, true, false, FAST, false, true>(st, a, pa, nproma, pa.nitems, &grid, ev, pkp)
+                 : launch_kseg_cfg<real, W, PF, false, false, FAST, false, true>(st, a, pa, nproma, pa.nitems, &grid, ev,
+                                                                                 pkp);
     } else if constexpr (CLOUDSC_KEEP_KERNEL(real, true, true))
       rc = aer ? launch_kseg<real, true, FAST>(st, a, pa, nproma, pa.nitems, &grid, ev, pkp)
                : launch_kseg<real, false, FAST>(st, a, pa, nproma, pa.nitems, &grid, ev, pkp);
@@ -736,28 +803,32 @@ int launch_v(hipStream_t st, int variant, const cloudsc_fields_t* f, int ngptot,
 template <typename real>
 int launch(hipStream_t st, int variant, bool exact_libm, const cloudsc_fields_t* f, int ngptot, int nproma,
            int klev, void* scratch, const void* plude_in, const ParamSet& ps, KsegEpoch* ep, const LaunchEvents* ev,
-           int tend_planes) {
+           int tend_planes, int outputs) {
   if constexpr (std::is_same<real, float>::value) {
     if (!exact_libm)
-      return launch_v<real, true>(st, variant, f, ngptot, nproma, klev, scratch, plude_in, ps, ep, ev, tend_planes);
+      return launch_v<real, true>(st, variant, f, ngptot, nproma, klev, scratch, plude_in, ps, ep, ev, tend_planes,
+                                  outputs);
   }
   (void)exact_libm;
-  return launch_v<real, false>(st, variant, f, ngptot, nproma, klev, scratch, plude_in, ps, ep, ev, tend_planes);
+  return launch_v<real, false>(st, variant, f, ngptot, nproma, klev, scratch, plude_in, ps, ep, ev, tend_planes,
+                               outputs);
 }
 
 // The launch of a precision code.  CLOUDSC_MIXED is the fp64 launch (exp/pow,
 // parameter mirror, configuration, workspace) over float fields.
 int launch_precision(int precision, hipStream_t st, int variant, bool exact_libm, const cloudsc_fields_t* f,
                      int ngptot, int nproma, int klev, void* scratch, const void* plude_in, const ParamSet& ps,
-                     KsegEpoch* ep, const LaunchEvents* ev, int tend_planes) {
+                     KsegEpoch* ep, const LaunchEvents* ev, int tend_planes, int outputs) {
   switch (precision) {
     case CLOUDSC_FP64:
-      return launch<double>(st, variant, exact_libm, f, ngptot, nproma, klev, scratch, plude_in, ps, ep, ev, tend_planes);
+      return launch<double>(st, variant, exact_libm, f, ngptot, nproma, klev, scratch, plude_in, ps, ep, ev, tend_planes,
+                            outputs);
     case CLOUDSC_FP32:
-      return launch<float>(st, variant, exact_libm, f, ngptot, nproma, klev, scratch, plude_in, ps, ep, ev, tend_planes);
+      return launch<float>(st, variant, exact_libm, f, ngptot, nproma, klev, scratch, plude_in, ps, ep, ev, tend_planes,
+                           outputs);
     case CLOUDSC_MIXED:
       return launch_v<double, false, float>(st, variant, f, ngptot, nproma, klev, scratch, plude_in, ps, ep, ev,
-                                            tend_planes);
+                                            tend_planes, outputs);
     default: return CLOUDSC_EINVAL;
   }
 }
@@ -838,7 +909,7 @@ int validate_run_args(int device, int precision, int variant, int ngptot, int np
 // ps: the parameter set of the launch (NULL = the device's default set).
 int gpu_run_impl(int device, void* stream, int precision, int variant, int ngptot, int nproma, int klev,
                  const cloudsc_fields_t* f, void* scratch, const void* plude_in, const ParamSet* ps,
-                 KsegEpoch* ep, const LaunchEvents* lev, int tend_planes) {
+                 KsegEpoch* ep, const LaunchEvents* lev, int tend_planes, int outputs) {
   const bool exact_libm = (variant & CLOUDSC_FP32_EXACT_LIBM) != 0;
   variant = variant_kind(variant);
   int rc = validate_run_args(device, precision, variant, ngptot, nproma, klev);
@@ -846,11 +917,11 @@ int gpu_run_impl(int device, void* stream, int precision, int variant, int ngpto
   if (!ps) ps = device_default_params(device);
   if (!ps || !ps->dev) return CLOUDSC_ENOINIT;
   if (ps->device != device) return CLOUDSC_EINVAL;
-  if (!f || !fields_complete(f)) return CLOUDSC_EINVAL;
+  if (!f || !fields_complete(f, outputs)) return CLOUDSC_EINVAL;
   HIPCHK(hipSetDevice(device));
   hipStream_t st = (hipStream_t)stream;
   return launch_precision(precision, st, variant, exact_libm, f, ngptot, nproma, klev, scratch, plude_in, *ps, ep, lev,
-                          tend_planes);
+                          tend_planes, outputs);
 }
 
 int kseg_clock(int device, void* stream, void* scratch, bool reset, double* ghz, double* seconds) {
@@ -925,6 +996,22 @@ int cloudsc_gpu_run_tendbuf(int device, void* stream, int precision, int variant
   if (!f || !fields_complete(f) || (kind == CLOUDSC_VARIANT_KSEG && !scratch)) return CLOUDSC_EINVAL;
   return gpu_run_impl(device, stream, precision, variant, ngptot, nproma, klev, f, scratch, nullptr, nullptr, nullptr,
                       nullptr, tend_planes);
+}
+
+int cloudsc_gpu_run_outputs(int device, void* stream, int precision, int variant, int outputs, int ngptot, int nproma,
+                            int klev, const cloudsc_fields_t* f, void* scratch) {
+  if (outputs != CLOUDSC_OUTPUTS_ALL && outputs != CLOUDSC_OUTPUTS_PROGNOSTIC) return CLOUDSC_EINVAL;
+  if (outputs == CLOUDSC_OUTPUTS_ALL)   // cloudsc_gpu_run itself
+    return gpu_run_impl(device, stream, precision, variant, ngptot, nproma, klev, f, scratch, nullptr, nullptr);
+  // every argument rule first, the device's among them last: no HIP call before an argument error
+  if (variant & ~0xff) return CLOUDSC_EINVAL;                                                  // no option bits
+  const int kind = variant_kind(variant);
+  if (kind != CLOUDSC_VARIANT_KCACHE && kind != CLOUDSC_VARIANT_KSEG) return CLOUDSC_EINVAL;   // no SCC form
+  const int rc = validate_shape_args(precision, kind, ngptot, nproma, klev);
+  if (rc) return rc;
+  if (!f || !fields_complete(f, outputs) || (kind == CLOUDSC_VARIANT_KSEG && !scratch)) return CLOUDSC_EINVAL;
+  return gpu_run_impl(device, stream, precision, variant, ngptot, nproma, klev, f, scratch, nullptr, nullptr, nullptr,
+                      nullptr, 0, outputs);
 }
 
 int cloudsc_gpu_check(int device, void* stream, int variant, void* scratch) {

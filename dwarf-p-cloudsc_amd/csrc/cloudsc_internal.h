@@ -74,8 +74,18 @@ int hip_fail(hipError_t e, const char* what);
 void set_error_text(const char* text);
 // device / precision / variant / size checks shared by every entry point
 int validate_run_args(int device, int precision, int variant, int ngptot, int nproma, int klev);
-// every pointer the kernel reads or writes (aerosol inputs excepted) is set
-bool fields_complete(const cloudsc_fields_t* f);
+// The ten diagnostic flux members pfsqlf ... pfsqitur (consecutive in cloudsc_fields_t): running sums of
+// section 8 that nothing in the step reads back; CLOUDSC_OUTPUTS_PROGNOSTIC leaves them out
+constexpr bool is_flux_diagnostic(int member) { return member >= CLOUDSC_M_pfsqlf && member <= CLOUDSC_M_pfsqitur; }
+static_assert(CLOUDSC_M_pfsqitur - CLOUDSC_M_pfsqlf + 1 == 10 && CLOUDSC_M_pfplsl == CLOUDSC_M_pfsqitur + 1,
+              "the diagnostic flux members");
+// whether an output selection (CLOUDSC_OUTPUTS_*) touches member m
+constexpr bool output_selected(int member, int outputs) {
+  return outputs != CLOUDSC_OUTPUTS_PROGNOSTIC || !is_flux_diagnostic(member);
+}
+// every pointer the kernel reads or writes (aerosol inputs and, with CLOUDSC_OUTPUTS_PROGNOSTIC, the ten
+// diagnostic fluxes excepted) is set
+bool fields_complete(const cloudsc_fields_t* f, int outputs = CLOUDSC_OUTPUTS_ALL);
 // Host record of one KSEG workspace owned by a caller that launches on it in
 // stream order (a state): after the first launch zeroes it, later launches
 // continue its ticket counter and flag stamps instead of zeroing it again.
@@ -93,10 +103,12 @@ struct LaunchEvents {
 // an explicit parameter set (NULL = the device's default set), an optional
 // KSEG workspace record (NULL = zero the workspace before every KSEG launch)
 // and optional events timing the physics kernel (NULL = none); tend_planes != 0:
-// the tendency members of f are planes of packed buffers (cloudsc_gpu_run_tendbuf)
+// the tendency members of f are planes of packed buffers (cloudsc_gpu_run_tendbuf); outputs: CLOUDSC_OUTPUTS_*
+// (cloudsc_gpu_run_outputs)
 int gpu_run_impl(int device, void* stream, int precision, int variant, int ngptot, int nproma, int klev,
                  const cloudsc_fields_t* f, void* scratch, const void* plude_in, const ParamSet* ps,
-                 KsegEpoch* ep = nullptr, const LaunchEvents* lev = nullptr, int tend_planes = 0);
+                 KsegEpoch* ep = nullptr, const LaunchEvents* lev = nullptr, int tend_planes = 0,
+                 int outputs = CLOUDSC_OUTPUTS_ALL);
 // the kernel variant of a `variant` argument without its option bits (CLOUDSC_FP32_EXACT_LIBM)
 inline int variant_kind(int variant) { return variant & 0xff; }
 // waits for `stream` and returns CLOUDSC_EHANDOFF if the last KSEG launch on
@@ -112,10 +124,11 @@ int kseg_clock(int device, void* stream, void* scratch, bool reset, double* ghz,
 // `reps` timed launches after one untimed, ms; mode 0 outputs written only, 1
 // inputs read too (every non-NULL output of f is overwritten); strides (6, may
 // be NULL): the inputs' and outputs' block / row / species element strides of
-// another layout (cloudsc_debug_memory_probe_layout)
+// another layout (cloudsc_debug_memory_probe_layout); outputs: CLOUDSC_OUTPUTS_*,
+// with PROGNOSTIC the ten diagnostic flux members of f are not looked at
 int memory_probe(int device, hipStream_t stream, int precision, int ngptot, int nproma, int klev,
                  const cloudsc_fields_t* f, int mode, int reps, hipEvent_t e0, hipEvent_t e1, float* best_ms,
-                 const long long* strides = nullptr);
+                 const long long* strides = nullptr, int outputs = CLOUDSC_OUTPUTS_ALL);
 
 // What a placement search cost and found (cloudsc_place.hip)
 struct PlaceCost {

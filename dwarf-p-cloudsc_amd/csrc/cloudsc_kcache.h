@@ -1135,32 +1135,41 @@ CLOUDSC_HD void physics_level(const P& c, const int k, const int klev,
 }
 
 // ===== 8. flux diagnostics of one level (cloudsc_c.c:2521-2582), written at half level k+1 =====
-template <typename real, typename P, typename CS, typename S, typename LO>
+// PROG: the prognostic-outputs form (cloudsc_gpu_run_outputs, CLOUDSC_OUTPUTS_PROGNOSTIC).  The ten
+// diagnostic fluxes pfsqlf ... pfsqitur are running sums that nothing in the step reads back: with
+// PROG on they are neither computed nor stored, their six carried sums (fl_* of the carried state)
+// are never touched -- not initialised, not carried, not handed over between KSEG segments -- and
+// their members of the kernel arguments are never read (they may be NULL).  What stays is what
+// pfplsl, pfplsn, pfhpsl and pfhpsn need.  With PROG off the functions are the ones they were.
+template <bool PROG = false, typename real, typename P, typename CS, typename S, typename LO>
 CLOUDSC_HD void flux_level(const P& c, const KArgs<real, S>& A, size_t h, LO lane,
                                            const LevelIn<real>& in, const LevelState<real>& ls,
                                            const PhysOut<real>& po, real paph_k, real paph_n,
                                            CS& cs) {
-  const real zgdph_r = -c.zrg_r * (paph_n - paph_k) * c.zqtmst;
-  const real lf = cs.fl_lf, fi = cs.fl_if, lng = cs.fl_lng, nng = cs.fl_nng;
-  const real* zqxn = po.zqxn;
-  const real* zqx0 = ls.zqx0;
-  const real* zlneg = ls.zlneg;
-  const real plude_k = po.plude_k, zfoealfa = ls.zfoealfa;
-  cs.fl_lf = lf + (zqxn[QL] - zqx0[QL] + in.pvfl * c.ptsphy - zfoealfa * plude_k) * zgdph_r;
-  cs.fl_lng = lng + zlneg[QL] * zgdph_r;
-  cs.fl_ltur = cs.fl_ltur + (in.pvfl * c.ptsphy) * zgdph_r;
-  const real rf = lf + (zqxn[QR] - zqx0[QR]) * zgdph_r;
-  const real rng = lng + zlneg[QR] * zgdph_r;
-  cs.fl_if = fi + (zqxn[QI] - zqx0[QI] + in.pvfi * c.ptsphy - (R(1.0) - zfoealfa) * plude_k) * zgdph_r;
-  cs.fl_nng = nng + zlneg[QI] * zgdph_r;
-  cs.fl_itur = cs.fl_itur + (in.pvfi * c.ptsphy) * zgdph_r;
-  const real sf = fi + (zqxn[QS] - zqx0[QS]) * zgdph_r;
-  const real sng = nng + zlneg[QS] * zgdph_r;
+  if constexpr (!PROG) {
+    const real zgdph_r = -c.zrg_r * (paph_n - paph_k) * c.zqtmst;
+    const real lf = cs.fl_lf, fi = cs.fl_if, lng = cs.fl_lng, nng = cs.fl_nng;
+    const real* zqxn = po.zqxn;
+    const real* zqx0 = ls.zqx0;
+    const real* zlneg = ls.zlneg;
+    const real plude_k = po.plude_k, zfoealfa = ls.zfoealfa;
+    cs.fl_lf = lf + (zqxn[QL] - zqx0[QL] + in.pvfl * c.ptsphy - zfoealfa * plude_k) * zgdph_r;
+    cs.fl_lng = lng + zlneg[QL] * zgdph_r;
+    cs.fl_ltur = cs.fl_ltur + (in.pvfl * c.ptsphy) * zgdph_r;
+    const real rf = lf + (zqxn[QR] - zqx0[QR]) * zgdph_r;
+    const real rng = lng + zlneg[QR] * zgdph_r;
+    cs.fl_if = fi + (zqxn[QI] - zqx0[QI] + in.pvfi * c.ptsphy - (R(1.0) - zfoealfa) * plude_k) * zgdph_r;
+    cs.fl_nng = nng + zlneg[QI] * zgdph_r;
+    cs.fl_itur = cs.fl_itur + (in.pvfi * c.ptsphy) * zgdph_r;
+    const real sf = fi + (zqxn[QS] - zqx0[QS]) * zgdph_r;
+    const real sng = nng + zlneg[QS] * zgdph_r;
+    const unsigned lo = lo_half(lane);
+    stg(A.pfsqlf, h, lo, cs.fl_lf); stg(A.pfsqif, h, lo, cs.fl_if);
+    stg(A.pfcqlng, h, lo, cs.fl_lng); stg(A.pfcqnng, h, lo, cs.fl_nng);
+    stg(A.pfsqltur, h, lo, cs.fl_ltur); stg(A.pfsqitur, h, lo, cs.fl_itur);
+    stg(A.pfsqrf, h, lo, rf); stg(A.pfcqrng, h, lo, rng); stg(A.pfsqsf, h, lo, sf); stg(A.pfcqsng, h, lo, sng);
+  }
   const unsigned lo = lo_half(lane);
-  stg(A.pfsqlf, h, lo, cs.fl_lf); stg(A.pfsqif, h, lo, cs.fl_if);
-  stg(A.pfcqlng, h, lo, cs.fl_lng); stg(A.pfcqnng, h, lo, cs.fl_nng);
-  stg(A.pfsqltur, h, lo, cs.fl_ltur); stg(A.pfsqitur, h, lo, cs.fl_itur);
-  stg(A.pfsqrf, h, lo, rf); stg(A.pfcqrng, h, lo, rng); stg(A.pfsqsf, h, lo, sf); stg(A.pfcqsng, h, lo, sng);
   const real plsl = cs.pfx_r + R(0.0);      // zpfplsx[qr] + zpfplsx[ql] (ql flux is +0)
   const real plsn = cs.pfx_s + cs.pfx_i;
   stg(A.pfplsl, h, lo, plsl); stg(A.pfplsn, h, lo, plsn);
@@ -1168,13 +1177,15 @@ CLOUDSC_HD void flux_level(const P& c, const KArgs<real, S>& A, size_t h, LO lan
 }
 
 // level-0 half-level outputs (cloudsc_c.c:2523-2543, 2578-2579)
-template <typename real, typename P, typename S, typename LO>
+template <bool PROG = false, typename real, typename P, typename S, typename LO>
 CLOUDSC_HD void flux_top(const P& c, const KArgs<real, S>& A, size_t h0, LO lane) {
   const unsigned lo = lo_half(lane);
-  stg(A.pfsqlf, h0, lo, R(0.0)); stg(A.pfsqif, h0, lo, R(0.0)); stg(A.pfsqrf, h0, lo, R(0.0));
-  stg(A.pfsqsf, h0, lo, R(0.0)); stg(A.pfcqlng, h0, lo, R(0.0)); stg(A.pfcqnng, h0, lo, R(0.0));
-  stg(A.pfcqrng, h0, lo, R(0.0)); stg(A.pfcqsng, h0, lo, R(0.0));
-  stg(A.pfsqltur, h0, lo, R(0.0)); stg(A.pfsqitur, h0, lo, R(0.0));
+  if constexpr (!PROG) {
+    stg(A.pfsqlf, h0, lo, R(0.0)); stg(A.pfsqif, h0, lo, R(0.0)); stg(A.pfsqrf, h0, lo, R(0.0));
+    stg(A.pfsqsf, h0, lo, R(0.0)); stg(A.pfcqlng, h0, lo, R(0.0)); stg(A.pfcqnng, h0, lo, R(0.0));
+    stg(A.pfcqrng, h0, lo, R(0.0)); stg(A.pfcqsng, h0, lo, R(0.0));
+    stg(A.pfsqltur, h0, lo, R(0.0)); stg(A.pfsqitur, h0, lo, R(0.0));
+  }
   const real plsl = R(0.0) + R(0.0), plsn = R(0.0) + R(0.0);
   stg(A.pfplsl, h0, lo, plsl); stg(A.pfplsn, h0, lo, plsn);
   stg(A.pfhpsl, h0, lo, -c.rlvtt * plsl); stg(A.pfhpsn, h0, lo, -c.rlstt * plsn);
@@ -1221,13 +1232,13 @@ CLOUDSC_HD void store_level(const KArgs<real, S>& A, size_t u2, size_t u3, int k
   stg_sp<kSpOpaque<real, S>>(A.tlcld, t3 + ((size_t)4 * klev + k) * nproma, lsp, R(0.0));
 }
 
-template <typename real, typename CS>
+template <typename real, bool PROG = false, typename CS>
 CLOUDSC_HD void init_carry(CS& cs) {
   cs.t_prev = cs.a_prev = cs.pap_prev = R(0.0);
   cs.zanewm1 = cs.zcovptot = cs.zcovpmax = cs.zcldtopdist = cs.rainfrac = R(0.0);
   cs.qxnm1_l = cs.qxnm1_i = R(0.0);
   cs.pfx_i = cs.pfx_r = cs.pfx_s = R(0.0);
-  cs.fl_lf = cs.fl_if = cs.fl_lng = cs.fl_nng = cs.fl_ltur = cs.fl_itur = R(0.0);
+  if constexpr (!PROG) cs.fl_lf = cs.fl_if = cs.fl_lng = cs.fl_nng = cs.fl_ltur = cs.fl_itur = R(0.0);
 }
 
 // The level loop's parameter block: the VGPR copy (fp32) or the constant-space
@@ -1250,7 +1261,9 @@ __device__ __forceinline__ const auto& params_here(const PV& pv, cptr<PT> cpar) 
 // persistent kernel (below) runs a column in level segments.
 //
 // TB: the tendency buffer form (KArgsTB; `ka` then points at one).
-template <typename real, int PF, bool AER, bool TB = false, typename S, typename PT, typename CS, typename LO>
+// PROG: the prognostic-outputs form (flux_level).
+template <typename real, int PF, bool AER, bool TB = false, bool PROG = false, typename S, typename PT, typename CS,
+          typename LO>
 __device__ __forceinline__ void kcache_levels(cptr<KArgs<real, S>> ka, cptr<PT> cpar, int b,
                                               LO lo0, int lev0, int lev1, CS& cs) {
   if (lev0 >= lev1) return;
@@ -1400,7 +1413,7 @@ __device__ __forceinline__ void kcache_levels(cptr<KArgs<real, S>> ka, cptr<PT> 
       // offsets formed from it stay live across the physics)
       const LO los = PVR || std::is_same<LO, PackLo>::value ? launder_vgpr(lo0) : lo;
       store_level<TB>(A, u2, u3, k, klev, nproma, los, physics, ls, po);
-      flux_level(c, A, uh + (size_t)(k + 1) * nproma, los, cur, ls, po, nb.paph_k, nb.paph_n, cs);
+      flux_level<PROG>(c, A, uh + (size_t)(k + 1) * nproma, los, cur, ls, po, nb.paph_k, nb.paph_n, cs);
     }
 
     // ---- rotate carried state ----
@@ -1422,19 +1435,19 @@ struct CarryRegs : CarryState<real> {
 template <typename real, bool LDSC>
 using CarryOf = typename std::conditional<LDSC, CarryLds<real>, CarryRegs<real>>::type;
 
-template <typename real, int PF, bool AER, bool LDSC, bool TB = false, typename S, typename PT>
+template <typename real, int PF, bool AER, bool LDSC, bool TB = false, bool PROG = false, typename S, typename PT>
 __device__ __forceinline__ void cloudsc_kcache_body(cptr<KArgs<real, S>> ka, cptr<PT> cpar) {
   const KArgs<real, S>& A = *(const KArgs<real, S>*)ka;
   const int b = blockIdx.x, jl = threadIdx.x;
   if (jl >= A.nproma || b * A.nproma + jl >= A.ngptot) return;
   const unsigned lo = (unsigned)jl * (unsigned)sizeof(S);   // the lane's byte offset in a field plane
   CarryOf<real, LDSC> cs(carry_lds_base<real>());
-  init_carry<real>(cs);
+  init_carry<real, PROG>(cs);
   {
     CLOUDSC_PARAMS_HERE;
-    flux_top(c, A, (size_t)b * (A.klev + 1) * A.nproma, lo);
+    flux_top<PROG>(c, A, (size_t)b * (A.klev + 1) * A.nproma, lo);
   }
-  kcache_levels<real, PF, AER, TB>(ka, cpar, b, lo, 0, A.klev, cs);
+  kcache_levels<real, PF, AER, TB, PROG>(ka, cpar, b, lo, 0, A.klev, cs);
   stg(((const KArgs<real, S>*)launder_uniform(ka))->prainfrac, (size_t)b * A.nproma, lo, cs.rainfrac);
 }
 
@@ -1468,7 +1481,7 @@ __device__ __forceinline__ bool pack_lane(int ngptot, int nproma, int klev, cons
   return s < (unsigned)G.pack && b < (unsigned)G.nblocks && b * np + jl < (unsigned)ngptot;
 }
 
-template <typename real, int PF, bool AER, bool LDSC, bool TB = false, typename S, typename PT>
+template <typename real, int PF, bool AER, bool LDSC, bool TB = false, bool PROG = false, typename S, typename PT>
 __device__ __forceinline__ void cloudsc_kcache_packed_body(cptr<KArgs<real, S>> ka, cptr<PT> cpar,
                                                            const PackArgs& G) {
   const KArgs<real, S>& A = *(const KArgs<real, S>*)ka;
@@ -1477,12 +1490,12 @@ __device__ __forceinline__ void cloudsc_kcache_packed_body(cptr<KArgs<real, S>> 
   unsigned sub;
   if (!pack_lane<S>(A.ngptot, A.nproma, A.klev, G, b0, lo, sub)) return;
   CarryOf<real, LDSC> cs(carry_lds_base<real>());
-  init_carry<real>(cs);
+  init_carry<real, PROG>(cs);
   {
     CLOUDSC_PARAMS_HERE;
-    flux_top(c, A, (size_t)b0 * (A.klev + 1) * A.nproma, lo);
+    flux_top<PROG>(c, A, (size_t)b0 * (A.klev + 1) * A.nproma, lo);
   }
-  kcache_levels<real, PF, AER, TB>(ka, cpar, b0, lo, 0, A.klev, cs);
+  kcache_levels<real, PF, AER, TB, PROG>(ka, cpar, b0, lo, 0, A.klev, cs);
   stg(((const KArgs<real, S>*)launder_uniform(ka))->prainfrac, (size_t)b0 * A.nproma, lo_surf(lane_here(lo)),
       cs.rainfrac);
 }
@@ -1555,7 +1568,9 @@ __device__ __forceinline__ void stg_sc1(float* ubase, size_t uidx, unsigned lane
                      __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <typename real, typename CS>
+// PROG: the six flux planes 13..18 of the workspace are neither stored nor reloaded (their places
+// stay: one workspace serves launches of either form)
+template <bool PROG = false, typename real, typename CS>
 __device__ __forceinline__ void carry_io(real* st, size_t u, size_t plane, unsigned lo, CS& cs, bool save) {
 #define CLOUDSC_CARRY_IO(q, m)                                                  \
   if (save) stg_sc1(st, u + (size_t)(q) * plane, lo, (real)cs.m);               \
@@ -1564,16 +1579,19 @@ __device__ __forceinline__ void carry_io(real* st, size_t u, size_t plane, unsig
   CLOUDSC_CARRY_IO(3, zanewm1) CLOUDSC_CARRY_IO(4, zcovptot) CLOUDSC_CARRY_IO(5, zcovpmax)
   CLOUDSC_CARRY_IO(6, zcldtopdist) CLOUDSC_CARRY_IO(7, rainfrac) CLOUDSC_CARRY_IO(8, qxnm1_l)
   CLOUDSC_CARRY_IO(9, qxnm1_i) CLOUDSC_CARRY_IO(10, pfx_i) CLOUDSC_CARRY_IO(11, pfx_r)
-  CLOUDSC_CARRY_IO(12, pfx_s) CLOUDSC_CARRY_IO(13, fl_lf) CLOUDSC_CARRY_IO(14, fl_if)
-  CLOUDSC_CARRY_IO(15, fl_lng) CLOUDSC_CARRY_IO(16, fl_nng) CLOUDSC_CARRY_IO(17, fl_ltur)
-  CLOUDSC_CARRY_IO(18, fl_itur)
+  CLOUDSC_CARRY_IO(12, pfx_s)
+  if constexpr (!PROG) {
+    CLOUDSC_CARRY_IO(13, fl_lf) CLOUDSC_CARRY_IO(14, fl_if) CLOUDSC_CARRY_IO(15, fl_lng)
+    CLOUDSC_CARRY_IO(16, fl_nng) CLOUDSC_CARRY_IO(17, fl_ltur) CLOUDSC_CARRY_IO(18, fl_itur)
+  }
 #undef CLOUDSC_CARRY_IO
 }
 
 // PACK: the schedule runs over groups of G.pack blocks instead of blocks (items
 // are (segment, group), stripes are taken over groups, one flag per group: the
 // first G.ngroups words of the flag area); the carried state keeps its layout.
-template <typename real, int PF, bool AER, bool LDSC, bool PACK = false, bool TB = false, typename ST, typename PT>
+template <typename real, int PF, bool AER, bool LDSC, bool PACK = false, bool TB = false, bool PROG = false,
+          typename ST, typename PT>
 __device__ __forceinline__ void cloudsc_kcache_persistent_body(cptr<KArgs<real, ST>> ka, cptr<PT> cpar,
                                                                const PersistArgs<real>& P,
                                                                const PackArgs& G = PackArgs{1, 0, 0}) {
@@ -1640,10 +1658,10 @@ __device__ __forceinline__ void cloudsc_kcache_persistent_body(cptr<KArgs<real, 
     const size_t ust = (size_t)b * kCarryN * nproma;
     CarryOf<real, LDSC> cs(carry_lds_base<real>());
     if (seg == 0) {
-      init_carry<real>(cs);
+      init_carry<real, PROG>(cs);
       if (active) {
         CLOUDSC_PARAMS_HERE;
-        flux_top(c, A, (size_t)b * (A.klev + 1) * nproma, lo);
+        flux_top<PROG>(c, A, (size_t)b * (A.klev + 1) * nproma, lo);
       }
     } else {
       // consumer: one relaxed poll (bounded, with s_sleep), one agent acquire,
@@ -1666,15 +1684,15 @@ __device__ __forceinline__ void cloudsc_kcache_persistent_body(cptr<KArgs<real, 
 #ifdef CLOUDSC_KSEG_TRACE
       t_ready = __builtin_amdgcn_s_memrealtime();
 #endif
-      if (active) carry_io(P.state, ust, (size_t)nproma, lo_c, cs, false);
+      if (active) carry_io<PROG>(P.state, ust, (size_t)nproma, lo_c, cs, false);
     }
-    if (active) kcache_levels<real, PF, AER, TB>(ka, cpar, b, lo, P.lev[seg], P.lev[seg + 1], cs);
+    if (active) kcache_levels<real, PF, AER, TB, PROG>(ka, cpar, b, lo, P.lev[seg], P.lev[seg + 1], cs);
     const auto lo_e = lane_here(lo);   // packed: the offsets below formed here, not live across the levels
     if constexpr (PACK) lo_c = (lo_e.sb * (unsigned)kCarryN + lo_e.jb) / (unsigned)sizeof(ST) * (unsigned)sizeof(real);
     if (seg + 1 < P.nseg) {
       // producer (G16 R1): sc1 payload stores, every wave drains, barrier, the
       // flag stored with an agent atomic
-      if (active) carry_io(P.state, ust, (size_t)nproma, lo_c, cs, true);
+      if (active) carry_io<PROG>(P.state, ust, (size_t)nproma, lo_c, cs, true);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
       if (wave0) __hip_atomic_store(P.flags + sb, P.stamp + (unsigned)(seg + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -143,13 +143,15 @@ __global__ void __launch_bounds__(64) place_probe_kernel(const ProbeArgs a) {
   }
 }
 
-ProbeArgs probe_args(const cloudsc_fields_t* f, int ngptot, int nproma, int klev, bool read) {
+// outputs: with CLOUDSC_OUTPUTS_PROGNOSTIC the ten diagnostic flux members are not looked at: their slots
+// stay NULL, which the kernel skips like any other NULL member
+ProbeArgs probe_args(const cloudsc_fields_t* f, int ngptot, int nproma, int klev, bool read, int outputs) {
   ProbeArgs a;
   std::memset(&a, 0, sizeof(a));
   int nil = 0, nis = 0, nol = 0, noh = 0;
   for (int m = 0; m < kNumFields; m++) {
     const FieldDesc& d = kFieldTable[m];
-    void* p = ((void* const*)f)[m];
+    void* p = output_selected(m, outputs) ? ((void* const*)f)[m] : nullptr;
     if (d.dir == CLOUDSC_FD_IN && read) {
       if (d.kind == CLOUDSC_FK_LEVEL) a.in_level[nil++] = p;
       else if (d.kind == CLOUDSC_FK_SPECIES) a.in_species[nis++] = p;
@@ -179,8 +181,8 @@ namespace cloudsc_impl {
 // inputs.  Every non-NULL output of f is overwritten.
 int memory_probe(int device, hipStream_t stream, int precision, int ngptot, int nproma, int klev,
                  const cloudsc_fields_t* f, int mode, int reps, hipEvent_t e0, hipEvent_t e1, float* best_ms,
-                 const long long* strides) {
-  ProbeArgs a = probe_args(f, ngptot, nproma, klev, mode == 1);
+                 const long long* strides, int outputs) {
+  ProbeArgs a = probe_args(f, ngptot, nproma, klev, mode == 1, outputs);
   if (strides) {
     a.bs_in = strides[0]; a.rs_in = strides[1]; a.ss_in = strides[2];
     a.bs_out = strides[3]; a.rs_out = strides[4]; a.ss_out = strides[5];
@@ -480,8 +482,10 @@ size_t member_bytes(int m, int precision, int ngptot, int nproma, int klev) {
 
 extern "C" int cloudsc_fields_free(int device, cloudsc_fields_t* f);
 
-extern "C" int cloudsc_fields_alloc(int device, int precision, int ngptot, int nproma, int klev, int flags,
-                                    cloudsc_fields_t* out, cloudsc_placement_t* report) {
+// cloudsc_fields_alloc for an output selection: members the selection leaves out are not allocated (they stay
+// NULL) and take no part in the search or its probe
+static int fields_alloc(int device, int precision, int ngptot, int nproma, int klev, int flags, int outputs,
+                        cloudsc_fields_t* out, cloudsc_placement_t* report) {
   if (!out || (flags & ~(CLOUDSC_PLACE_NONE | CLOUDSC_ALLOC_AEROSOLS))) return CLOUDSC_EINVAL;
   int rc = validate_run_args(device, precision, CLOUDSC_VARIANT_KSEG, ngptot, nproma, klev);
   if (rc) return rc;
@@ -491,6 +495,7 @@ extern "C" int cloudsc_fields_alloc(int device, int precision, int ngptot, int n
   void** df = (void**)out;
   for (int m = 0; m < kNumFields; m++) {
     if (kFieldTable[m].dir == CLOUDSC_FD_AEROSOL && !(flags & CLOUDSC_ALLOC_AEROSOLS)) continue;
+    if (!output_selected(m, outputs)) continue;
     void* p = nullptr;
     const hipError_t e = dev_malloc(&p, member_bytes(m, precision, ngptot, nproma, klev));
     if (e != hipSuccess) {
@@ -507,7 +512,8 @@ extern "C" int cloudsc_fields_alloc(int device, int precision, int ngptot, int n
   size_t bytes[kNumFields], set_bytes = 0;
   int n = 0;
   for (int m = 0; m < kNumFields; m++)
-    if (kFieldTable[m].dir == CLOUDSC_FD_OUT || kFieldTable[m].dir == CLOUDSC_FD_INOUT) {
+    if ((kFieldTable[m].dir == CLOUDSC_FD_OUT || kFieldTable[m].dir == CLOUDSC_FD_INOUT) &&
+        output_selected(m, outputs)) {
       members[n] = m;
       bytes[n] = member_bytes(m, precision, ngptot, nproma, klev);
       set_bytes += bytes[n++];
@@ -530,7 +536,8 @@ extern "C" int cloudsc_fields_alloc(int device, int precision, int ngptot, int n
     // ranks placements at Pearson 0.986 / Spearman 0.988 against the kernel, the
     // write-only form at 0.980 / 0.939 (profiles/r06/place_corr_sc1_fp64.jsonl);
     // it reads the caller's own (not yet filled) input buffers, where they will stay
-    if (memory_probe(device, st, precision, ngptot, nproma, klev, &f, 1, 2, e0, e1, &ms) != CLOUDSC_OK) return -1.f;
+    if (memory_probe(device, st, precision, ngptot, nproma, klev, &f, 1, 2, e0, e1, &ms, nullptr, outputs) != CLOUDSC_OK)
+      return -1.f;
     return ms;
   };
   // the shader clock leaves its idle level over the first ~25 ms of work
@@ -571,6 +578,17 @@ extern "C" int cloudsc_fields_alloc(int device, int precision, int ngptot, int n
     report->method = CLOUDSC_PLACE_METHOD_RW_PROBE;
   }
   return CLOUDSC_OK;
+}
+
+extern "C" int cloudsc_fields_alloc(int device, int precision, int ngptot, int nproma, int klev, int flags,
+                                    cloudsc_fields_t* out, cloudsc_placement_t* report) {
+  return fields_alloc(device, precision, ngptot, nproma, klev, flags, CLOUDSC_OUTPUTS_ALL, out, report);
+}
+
+extern "C" int cloudsc_fields_alloc_outputs(int device, int precision, int ngptot, int nproma, int klev, int flags,
+                                            int outputs, cloudsc_fields_t* out, cloudsc_placement_t* report) {
+  if (outputs != CLOUDSC_OUTPUTS_ALL && outputs != CLOUDSC_OUTPUTS_PROGNOSTIC) return CLOUDSC_EINVAL;
+  return fields_alloc(device, precision, ngptot, nproma, klev, flags, outputs, out, report);
 }
 
 extern "C" int cloudsc_fields_free(int device, cloudsc_fields_t* f) {

@@ -381,6 +381,60 @@ int cloudsc_cpu_fields_convert_tendbuf(int nthreads, int ngptot, int klev,
                                        int dst_precision, int dst_nproma, int dst_tend_planes,
                                        const cloudsc_fields_t *dst);
 
+/* ------------------------------------------------------------------------ */
+/* Output selection: a step that writes only the prognostic outputs          */
+/* ------------------------------------------------------------------------ */
+/* Ten of the 21 outputs are diagnostic fluxes that nothing in the step reads
+ * back -- pfsqlf, pfsqif, pfcqnng, pfcqlng, pfsqrf, pfsqsf, pfcqrng, pfcqsng,
+ * pfsqltur, pfsqitur: the running sums of section 8, which a host model uses
+ * for budget diagnostics only.  They are 10 * (klev + 1) of the 24 * klev + 15
+ * values a column writes (42 % of the stores, 19.7 % of a step's bytes,
+ * DESIGN.md §3.5).  A caller that only advances its state needs the other
+ * eleven: plude, tendency_loc_t/q/a/cld, pcovptot, prainfrac_toprfz, pfplsl,
+ * pfplsn, pfhpsl, pfhpsn. */
+#define CLOUDSC_OUTPUTS_ALL        0   /* all 21 outputs, as cloudsc_gpu_run                        */
+#define CLOUDSC_OUTPUTS_PROGNOSTIC 1   /* the ten diagnostic fluxes neither computed nor written   */
+
+/* cloudsc_gpu_run with an output selection.  With CLOUDSC_OUTPUTS_ALL it IS
+ * cloudsc_gpu_run: the same kernels, the same argument rules.  With
+ * CLOUDSC_OUTPUTS_PROGNOSTIC the ten members above are neither read nor
+ * written: they may be NULL, and a non-NULL one keeps every byte.  Every other
+ * output has the bits cloudsc_gpu_run gives on the same inputs.  Everything
+ * else -- asynchrony, the workspace and cloudsc_gpu_scratch_bytes, narrow-block
+ * packing and cloudsc_gpu_launch_geometry, cloudsc_gpu_check -- is
+ * cloudsc_gpu_run's.  The KSEG workspace keeps its layout: one workspace serves
+ * launches of either selection in any order (the prognostic form does not
+ * store or reload the six flux planes of the hand-off).
+ * PROGNOSTIC exists for KCACHE and KSEG, in every precision, with and without
+ * aerosols, packed and unpacked.  CLOUDSC_VARIANT_SCC, CLOUDSC_VARIANT_SCC_PRIVATE
+ * and the option bit CLOUDSC_FP32_EXACT_LIBM have no such form: CLOUDSC_EINVAL,
+ * like an unknown `outputs` value and every argument error of cloudsc_gpu_run
+ * -- with PROGNOSTIC all of these are checked before the first HIP call.
+ * There is no combined form with the tendency buffers.
+ * cloudsc_fields_validate needs all 21 members: to check a prognostic set use
+ * cloudsc_fields_compare, which skips members that are NULL in both sets. */
+int cloudsc_gpu_run_outputs(int device, void *stream, int precision, int variant, int outputs,
+                            int ngptot, int nproma, int klev,
+                            const cloudsc_fields_t *device_fields, void *scratch);
+
+/* cloudsc_cpu_run_precision (below) with an output selection, on HOST arrays
+ * through the same phase functions: the same contract -- with PROGNOSTIC the
+ * ten members may be NULL, a non-NULL one keeps every byte, the other outputs
+ * have cloudsc_cpu_run_precision's bits.  CLOUDSC_EINVAL: an unknown `outputs`
+ * value and every argument error of cloudsc_cpu_run_precision.  Needs no GPU. */
+int cloudsc_cpu_run_outputs(int nthreads, int precision, int outputs, int ngptot, int nproma, int klev,
+                            const cloudsc_params_t *params, const cloudsc_fields_t *host_fields);
+
+/* cloudsc_fields_alloc for an output selection.  With CLOUDSC_OUTPUTS_ALL it is
+ * cloudsc_fields_alloc.  With CLOUDSC_OUTPUTS_PROGNOSTIC the ten diagnostic
+ * members are not allocated and stay NULL (10 * (klev + 1) elements per column
+ * of device memory less), and the placement search and its probe run over the
+ * eleven allocated outputs only.  cloudsc_fields_free frees such a set.
+ * CLOUDSC_EINVAL: an unknown `outputs` value (before the first HIP call) and
+ * every argument error of cloudsc_fields_alloc. */
+int cloudsc_fields_alloc_outputs(int device, int precision, int ngptot, int nproma, int klev, int flags,
+                                 int outputs, cloudsc_fields_t *fields, cloudsc_placement_t *report);
+
 /* Bytes of device scratch a variant needs for (ngptot, nproma, klev, precision); 0 for KCACHE. */
 long long cloudsc_gpu_scratch_bytes(int precision, int variant, int ngptot, int nproma, int klev);
 
@@ -808,7 +862,9 @@ int cloudsc_cpu_fields_compare(int nthreads, int ngptot, int klev,
                                cloudsc_field_diff_t *diff);
 
 /* cloudsc_state_validate for a caller-owned set: the 21 validated members of
- * `fields` (all must be set) against the KLON-column reference, read as
+ * `fields` (all must be set: a set of CLOUDSC_OUTPUTS_PROGNOSTIC, whose ten
+ * diagnostic fluxes are NULL, is checked with cloudsc_fields_compare instead,
+ * which skips members that are NULL in both sets) against the KLON-column reference, read as
  * ref[row][(col_offset + g) % klon] -- the comparison kernel with the
  * reference as its second operand.  The reference arrays are uploaded on
  * `stream`, ordered before the one launch; the call waits for that stream only
