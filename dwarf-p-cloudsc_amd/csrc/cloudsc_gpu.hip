@@ -150,132 +150,50 @@ template <typename real, bool FAST, typename S>
 __device__ __forceinline__ cptr<DevParamsT<real, FAST>> params_of(cptr<KArgs<real, S>> ka) {
   return (cptr<DevParamsT<real, FAST>>)((const KArgs<real, S>*)ka)->par;
 }
+template <typename F>
+__device__ __forceinline__ cptr<typename F::params> params_of(cptr<typename F::fields> ka) {
+  return params_of<typename F::real, F::fast>(ka);
+}
 
 }  // namespace
 
-// Kernel entry points.  The KArgs struct is the first explicit kernel argument,
-// i.e. it sits at offset 0 of the kernarg segment; the bodies read it (and the
-// parameter block it points at) through constant-address-space pointers.
-// FAST: fp32 exp/pow in their float-internal device forms (the CLOUDSC_FP32
-// default); false: the reference CPU build's algorithms (always for fp64).
-template <typename real, int WAVES, int PF, bool AER, bool LDSC, bool FAST = false>
-__global__ void __launch_bounds__(256, WAVES) kcache_entry(const KArgs<real> a) {
+// Kernel entry points.  The kernel-argument struct is the first explicit kernel
+// argument, i.e. it sits at offset 0 of the kernarg segment; the bodies read it
+// (and the parameter block it points at) through constant-address-space
+// pointers.
+//
+// The k-caching kernels are two templates over the form descriptor F (KForm,
+// cloudsc_kcache.h): kcache_entry<F>, one shot, and kseg_entry<F>, persistent
+// and level-segmented.  F names the compute and storage types (float fields
+// under double arithmetic are CLOUDSC_MIXED), the configuration and the form:
+//   F::fast  fp32 exp/pow in their float-internal device forms (the
+//            CLOUDSC_FP32 default); false: the reference CPU build's
+//            algorithms (always for fp64);
+//   F::tb    the tendency buffer form (cloudsc_gpu_run_tendbuf): the first
+//            argument is a KArgsTB, tend_planes directly behind the KArgs;
+//   F::prog  the prognostic-outputs form (CLOUDSC_OUTPUTS_PROGNOSTIC): the
+//            plain KArgs, whose ten diagnostic flux members are never read;
+//   F::pack  narrow blocks (NPROMA <= 32) packed into full waves: a workgroup
+//            is one wave that walks PackArgs::pack consecutive blocks.
+// A kernel has exactly the arguments its form needs: Pack is PackArgs for
+// F::pack and empty otherwise, so an unpacked kernel's kernarg segment holds
+// no PackArgs.
+template <typename F, typename... Pack>
+__global__ void __launch_bounds__(256, F::waves) kcache_entry(const typename F::kargs a, const Pack... g) {
+  static_assert(sizeof...(Pack) == (F::pack ? 1 : 0), "PackArgs exactly when the form is packed");
   (void)a;
-  libm_tables_to_lds<real>();
-  const cptr<KArgs<real>> ka = (cptr<KArgs<real>>)__builtin_amdgcn_kernarg_segment_ptr();
-  cloudsc_kcache_body<real, PF, AER, LDSC>(ka, params_of<real, FAST>(ka));
+  libm_tables_to_lds<typename F::real>();
+  const cptr<typename F::fields> ka = (cptr<typename F::fields>)__builtin_amdgcn_kernarg_segment_ptr();
+  cloudsc_kcache_body<F>(ka, params_of<F>(ka), g...);
 }
-template <typename real, int WAVES, int PF, bool AER, bool LDSC, bool FAST = false>
-__global__ void __launch_bounds__(256, WAVES) kseg_entry(const KArgs<real> a, const PersistArgs<real> pa) {
+template <typename F, typename... Pack>
+__global__ void __launch_bounds__(256, F::waves) kseg_entry(const typename F::kargs a,
+                                                            const PersistArgs<typename F::real> pa, const Pack... g) {
+  static_assert(sizeof...(Pack) == (F::pack ? 1 : 0), "PackArgs exactly when the form is packed");
   (void)a;
-  libm_tables_to_lds<real>();
-  const cptr<KArgs<real>> ka = (cptr<KArgs<real>>)__builtin_amdgcn_kernarg_segment_ptr();
-  cloudsc_kcache_persistent_body<real, PF, AER, LDSC>(ka, params_of<real, FAST>(ka), pa);
-}
-// CLOUDSC_MIXED: the fp64 physics on float fields (KArgs<double, float>), the
-// fp64 configuration, parameter block and workspace.  Entry points of their
-// own, so the fp64 and fp32 kernels keep their names and their code.
-template <int WAVES, int PF, bool AER, bool LDSC>
-__global__ void __launch_bounds__(256, WAVES) kcache_mixed_entry(const KArgs<double, float> a) {
-  (void)a;
-  libm_tables_to_lds<double>();
-  const cptr<KArgs<double, float>> ka = (cptr<KArgs<double, float>>)__builtin_amdgcn_kernarg_segment_ptr();
-  cloudsc_kcache_body<double, PF, AER, LDSC>(ka, params_of<double, false>(ka));
-}
-template <int WAVES, int PF, bool AER, bool LDSC>
-__global__ void __launch_bounds__(256, WAVES) kseg_mixed_entry(const KArgs<double, float> a,
-                                                               const PersistArgs<double> pa) {
-  (void)a;
-  libm_tables_to_lds<double>();
-  const cptr<KArgs<double, float>> ka = (cptr<KArgs<double, float>>)__builtin_amdgcn_kernarg_segment_ptr();
-  cloudsc_kcache_persistent_body<double, PF, AER, LDSC>(ka, params_of<double, false>(ka), pa);
-}
-// Narrow blocks (NPROMA <= 32) packed into full waves: a workgroup is one wave
-// that walks PackArgs::pack consecutive blocks (cloudsc_kcache.h).  Entry points
-// of their own for every (compute, storage) pair, so the kernels above keep
-// their names and their code.
-template <typename real, typename S, int WAVES, int PF, bool AER, bool LDSC, bool FAST = false>
-__global__ void __launch_bounds__(256, WAVES) kcache_packed_entry(const KArgs<real, S> a, const PackArgs g) {
-  (void)a;
-  libm_tables_to_lds<real>();
-  const cptr<KArgs<real, S>> ka = (cptr<KArgs<real, S>>)__builtin_amdgcn_kernarg_segment_ptr();
-  cloudsc_kcache_packed_body<real, PF, AER, LDSC>(ka, params_of<real, FAST>(ka), g);
-}
-template <typename real, typename S, int WAVES, int PF, bool AER, bool LDSC, bool FAST = false>
-__global__ void __launch_bounds__(256, WAVES) kseg_packed_entry(const KArgs<real, S> a, const PersistArgs<real> pa,
-                                                                const PackArgs g) {
-  (void)a;
-  libm_tables_to_lds<real>();
-  const cptr<KArgs<real, S>> ka = (cptr<KArgs<real, S>>)__builtin_amdgcn_kernarg_segment_ptr();
-  cloudsc_kcache_persistent_body<real, PF, AER, LDSC, true>(ka, params_of<real, FAST>(ka), pa, g);
-}
-// The tendency buffer form (cloudsc_gpu_run_tendbuf): the same bodies with TB
-// on, the kernel arguments a KArgsTB.  Entry points of their own for every
-// (compute, storage) pair, in the product configuration only.
-template <typename real, typename S, int WAVES, int PF, bool AER, bool FAST = false>
-__global__ void __launch_bounds__(256, WAVES) kcache_tendbuf_entry(const KArgsTB<real, S> a) {
-  (void)a;
-  libm_tables_to_lds<real>();
-  const cptr<KArgs<real, S>> ka = (cptr<KArgs<real, S>>)__builtin_amdgcn_kernarg_segment_ptr();
-  cloudsc_kcache_body<real, PF, AER, false, true>(ka, params_of<real, FAST>(ka));
-}
-template <typename real, typename S, int WAVES, int PF, bool AER, bool FAST = false>
-__global__ void __launch_bounds__(256, WAVES) kseg_tendbuf_entry(const KArgsTB<real, S> a,
-                                                                 const PersistArgs<real> pa) {
-  (void)a;
-  libm_tables_to_lds<real>();
-  const cptr<KArgs<real, S>> ka = (cptr<KArgs<real, S>>)__builtin_amdgcn_kernarg_segment_ptr();
-  cloudsc_kcache_persistent_body<real, PF, AER, false, false, true>(ka, params_of<real, FAST>(ka), pa);
-}
-template <typename real, typename S, int WAVES, int PF, bool AER, bool FAST = false>
-__global__ void __launch_bounds__(256, WAVES) kcache_tendbuf_packed_entry(const KArgsTB<real, S> a,
-                                                                          const PackArgs g) {
-  (void)a;
-  libm_tables_to_lds<real>();
-  const cptr<KArgs<real, S>> ka = (cptr<KArgs<real, S>>)__builtin_amdgcn_kernarg_segment_ptr();
-  cloudsc_kcache_packed_body<real, PF, AER, false, true>(ka, params_of<real, FAST>(ka), g);
-}
-template <typename real, typename S, int WAVES, int PF, bool AER, bool FAST = false>
-__global__ void __launch_bounds__(256, WAVES) kseg_tendbuf_packed_entry(const KArgsTB<real, S> a,
-                                                                        const PersistArgs<real> pa,
-                                                                        const PackArgs g) {
-  (void)a;
-  libm_tables_to_lds<real>();
-  const cptr<KArgs<real, S>> ka = (cptr<KArgs<real, S>>)__builtin_amdgcn_kernarg_segment_ptr();
-  cloudsc_kcache_persistent_body<real, PF, AER, false, true, true>(ka, params_of<real, FAST>(ka), pa, g);
-}
-// The prognostic-outputs form (cloudsc_gpu_run_outputs with CLOUDSC_OUTPUTS_PROGNOSTIC): the same
-// bodies with PROG on (cloudsc_kcache.h, flux_level), the plain KArgs whose ten diagnostic flux
-// members are never read.  Entry points of their own for every (compute, storage) pair, in the
-// product configuration only.
-template <typename real, typename S, int WAVES, int PF, bool AER, bool FAST = false>
-__global__ void __launch_bounds__(256, WAVES) kcache_outputs_entry(const KArgs<real, S> a) {
-  (void)a;
-  libm_tables_to_lds<real>();
-  const cptr<KArgs<real, S>> ka = (cptr<KArgs<real, S>>)__builtin_amdgcn_kernarg_segment_ptr();
-  cloudsc_kcache_body<real, PF, AER, false, false, true>(ka, params_of<real, FAST>(ka));
-}
-template <typename real, typename S, int WAVES, int PF, bool AER, bool FAST = false>
-__global__ void __launch_bounds__(256, WAVES) kseg_outputs_entry(const KArgs<real, S> a, const PersistArgs<real> pa) {
-  (void)a;
-  libm_tables_to_lds<real>();
-  const cptr<KArgs<real, S>> ka = (cptr<KArgs<real, S>>)__builtin_amdgcn_kernarg_segment_ptr();
-  cloudsc_kcache_persistent_body<real, PF, AER, false, false, false, true>(ka, params_of<real, FAST>(ka), pa);
-}
-template <typename real, typename S, int WAVES, int PF, bool AER, bool FAST = false>
-__global__ void __launch_bounds__(256, WAVES) kcache_outputs_packed_entry(const KArgs<real, S> a, const PackArgs g) {
-  (void)a;
-  libm_tables_to_lds<real>();
-  const cptr<KArgs<real, S>> ka = (cptr<KArgs<real, S>>)__builtin_amdgcn_kernarg_segment_ptr();
-  cloudsc_kcache_packed_body<real, PF, AER, false, false, true>(ka, params_of<real, FAST>(ka), g);
-}
-template <typename real, typename S, int WAVES, int PF, bool AER, bool FAST = false>
-__global__ void __launch_bounds__(256, WAVES) kseg_outputs_packed_entry(const KArgs<real, S> a,
-                                                                        const PersistArgs<real> pa, const PackArgs g) {
-  (void)a;
-  libm_tables_to_lds<real>();
-  const cptr<KArgs<real, S>> ka = (cptr<KArgs<real, S>>)__builtin_amdgcn_kernarg_segment_ptr();
-  cloudsc_kcache_persistent_body<real, PF, AER, false, true, false, true>(ka, params_of<real, FAST>(ka), pa, g);
+  libm_tables_to_lds<typename F::real>();
+  const cptr<typename F::fields> ka = (cptr<typename F::fields>)__builtin_amdgcn_kernarg_segment_ptr();
+  cloudsc_kcache_persistent_body<F>(ka, params_of<F>(ka), pa, g...);
 }
 template <typename real, bool AER, bool FAST = false>
 __global__ void __launch_bounds__(256) scc_entry(const KArgs<real> a, const SccScratch<real> s) {
@@ -343,34 +261,87 @@ void launch_physics(void (*kern)(Args...), dim3 grid, dim3 block, size_t lds, hi
   else hipLaunchKernelGGL(kern, grid, block, lds, st, args...);
 }
 
-// the k-caching kernels of a (compute, storage) pair: the plain entries when
-// the two are one type, the mixed entries otherwise
-template <typename real, typename S, int WAVES, int PF, bool AER, bool LDSC, bool FAST>
-constexpr auto kcache_kernel() {
-  if constexpr (std::is_same<real, S>::value) return kcache_entry<real, WAVES, PF, AER, LDSC, FAST>;
-  else return kcache_mixed_entry<WAVES, PF, AER, LDSC>;
+// a launch's runtime conditions as compile-time constants, in one place:
+// dispatch_bools(f, c0, c1, ...) calls f(std::bool_constant<c0>{}, std::bool_constant<c1>{}, ...)
+template <bool... Bs, typename Fn>
+int dispatch_bools(Fn&& f) {
+  return f(std::integral_constant<bool, Bs>{}...);
 }
-template <typename real, typename S, int WAVES, int PF, bool AER, bool LDSC, bool FAST, bool TB = false,
-          bool PROG = false>
-constexpr auto kseg_kernel() {
-  if constexpr (PROG) return kseg_outputs_entry<real, S, WAVES, PF, AER, FAST>;
-  else if constexpr (TB) return kseg_tendbuf_entry<real, S, WAVES, PF, AER, FAST>;
-  else if constexpr (std::is_same<real, S>::value) return kseg_entry<real, WAVES, PF, AER, LDSC, FAST>;
-  else return kseg_mixed_entry<WAVES, PF, AER, LDSC>;
+template <bool... Bs, typename Fn, typename... Rest>
+int dispatch_bools(Fn&& f, bool c, Rest... rest) {
+  return c ? dispatch_bools<Bs..., true>(f, rest...) : dispatch_bools<Bs..., false>(f, rest...);
 }
-template <typename real, typename S, int WAVES, int PF, bool AER, bool LDSC, bool FAST, bool TB = false,
-          bool PROG = false>
-constexpr auto kseg_packed_kernel() {
-  if constexpr (PROG) return kseg_outputs_packed_entry<real, S, WAVES, PF, AER, FAST>;
-  else if constexpr (TB) return kseg_tendbuf_packed_entry<real, S, WAVES, PF, AER, FAST>;
-  else return kseg_packed_entry<real, S, WAVES, PF, AER, LDSC, FAST>;
+
+// The support matrix: whether (variant kind, precision, fp32 exact-libm, form bits kFormTb and
+// kFormProg) has a kernel.  MIXED runs on the k-caching variants only; so do the tendency buffer
+// and the prognostic-outputs forms, which are not combined and which fp32 has with its default
+// exp/pow only; the SCC variants are plain.  (The exact-libm bit means nothing outside fp32;
+// every k-caching kernel has its packed twin, so kFormPack is not asked about.)
+constexpr bool form_exists(int kind, int precision, bool exact_libm, unsigned form) {
+  const bool tb = (form & kFormTb) != 0, prog = (form & kFormProg) != 0;
+  const bool kcaching = kind == CLOUDSC_VARIANT_KCACHE || kind == CLOUDSC_VARIANT_KSEG;
+  if (!kcaching && kind != CLOUDSC_VARIANT_SCC && kind != CLOUDSC_VARIANT_SCC_PRIVATE) return false;
+  if (precision != CLOUDSC_FP64 && precision != CLOUDSC_FP32 && precision != CLOUDSC_MIXED) return false;
+  if (precision == CLOUDSC_MIXED && !kcaching) return false;
+  if (tb || prog) return kcaching && !(tb && prog) && !(precision == CLOUDSC_FP32 && exact_libm);
+  return true;
 }
+// the precision code of a (compute, storage) pair
+template <typename real, typename S>
+constexpr int kPrecisionOf = !std::is_same<real, S>::value ? CLOUDSC_MIXED : sizeof(real) == 8 ? CLOUDSC_FP64 : CLOUDSC_FP32;
+
+// Whether this build instantiates the kernels of (variant kind, compute, storage, exact-libm, AER,
+// form bits): those that exist.  Experiment builds (make variant VFLAGS=-DCLOUDSC_ONLY_KSEG=8 ...) keep only
+// the plain KSEG kernels of one element size without aerosols -- for the per-phase ablation builds of
+// tools/ablation.sh; every other combination returns CLOUDSC_EINVAL.
+template <typename real, typename S, bool FAST>
+constexpr bool kernel_kept(int kind, bool aer, unsigned form = 0u) {
+#ifdef CLOUDSC_ONLY_KSEG
+  if (kind != CLOUDSC_VARIANT_KSEG || aer || (form & (kFormTb | kFormProg)) || sizeof(real) != CLOUDSC_ONLY_KSEG ||
+      sizeof(S) != CLOUDSC_ONLY_KSEG)
+    return false;
+#endif
+  (void)aer;
+  return form_exists(kind, kPrecisionOf<real, S>, std::is_same<real, float>::value && !FAST, form);
+}
+
+// The descriptors of one launch, one per configuration (WAVES, PF, LDSC).  The product library
+// instantiates `product` alone.  with_cfg calls f(F{}) for the descriptor F to launch: in a
+// CLOUDSC_DEBUG_KNOBS build the configuration that CLOUDSC_KCACHE_CFG names, for the kernels the
+// table applies to (TABLE: the plain unpacked KCACHE kernels and the plain KSEG kernels, packed or
+// not); packed KCACHE and the tendency buffer and prognostic-outputs forms stay in the product
+// configuration in every build.
+template <typename real, typename S, bool AER, bool FAST, unsigned FORM>
+struct LaunchForm {
+  template <int WAVES, int PF, bool LDSC>
+  using cfg = KForm<real, S, WAVES, PF, AER, LDSC, FAST, FORM>;
+  using product = cfg<DefaultCfg<real>::waves, DefaultCfg<real>::pf, false>;
+};
+constexpr bool cfg_table_applies(int kind, unsigned form) {
+  return !(form & (kFormTb | kFormProg)) && (kind == CLOUDSC_VARIANT_KSEG || !(form & kFormPack));
+}
+template <typename LF, bool TABLE, typename Fn>
+int with_cfg(Fn&& f) {
+#ifdef CLOUDSC_DEBUG_KNOBS
+  if constexpr (TABLE) {
+    switch (env_int("CLOUDSC_KCACHE_CFG", DefaultCfg<typename LF::product::real>::code)) {
+#define X(code, w, pf, ldsc) \
+  case code: return f(typename LF::template cfg<w, pf, ldsc>{});
+      CLOUDSC_FOR_EACH_CFG(X)
+#undef X
+      default: return CLOUDSC_EINVAL;
+    }
+  }
+#endif
+  return f(typename LF::product{});
+}
+
 // the kernel arguments of a launch: a's, with tend_planes behind them in the tendency buffer form
-template <bool TB, typename real, typename S>
-auto kernel_args(const KArgs<real, S>& a, int tend_planes) {
-  if constexpr (TB) {
-    KArgsTB<real, S> t;
-    static_cast<KArgs<real, S>&>(t) = a;
+template <typename F>
+typename F::kargs kernel_args(const typename F::fields& a, int tend_planes) {
+  if constexpr (F::tb) {
+    typename F::kargs t;
+    static_cast<typename F::fields&>(t) = a;
     t.tend_planes = tend_planes;
     return t;
   } else {
@@ -379,24 +350,15 @@ auto kernel_args(const KArgs<real, S>& a, int tend_planes) {
   }
 }
 
-template <typename real, bool AER, bool FAST, typename S>
-int launch_kcache(hipStream_t st, const KArgs<real, S>& a, int nblocks, int nproma, const LaunchEvents* ev) {
-#ifdef CLOUDSC_DEBUG_KNOBS
-  switch (env_int("CLOUDSC_KCACHE_CFG", DefaultCfg<real>::code)) {
-#define X(code, w, pf, ldsc)                                                                                 \
-  case code:                                                                                                 \
-    launch_physics(kcache_kernel<real, S, w, pf, AER, ldsc, FAST>(), dim3(nblocks), dim3(nproma),            \
-                   ldsc ? carry_lds_bytes<real>(nproma) : 0, st, ev, a);                                     \
-    return CLOUDSC_OK;
-    CLOUDSC_FOR_EACH_CFG(X)
-#undef X
-    default: return CLOUDSC_EINVAL;
-  }
-#else
-  launch_physics(kcache_kernel<real, S, DefaultCfg<real>::waves, DefaultCfg<real>::pf, AER, false, FAST>(),
-                 dim3(nblocks), dim3(nproma), 0, st, ev, a);
+// The KCACHE launch: a workgroup of nproma threads per block, or (F::pack) one wave per group of pk.pack blocks
+template <typename F>
+int launch_kcache(hipStream_t st, const typename F::kargs& a, int nblocks, int nproma, const PackArgs& pk,
+                  const LaunchEvents* ev) {
+  const int wg = F::pack ? 64 : nproma;
+  const size_t lds = F::ldsc ? carry_lds_bytes<typename F::real>(wg) : 0;
+  if constexpr (F::pack) launch_physics(kcache_entry<F, PackArgs>, dim3(pk.ngroups), dim3(wg), lds, st, ev, a, pk);
+  else launch_physics(kcache_entry<F>, dim3(nblocks), dim3(wg), lds, st, ev, a);
   return CLOUDSC_OK;
-#endif
 }
 
 // ---- narrow blocks packed into full waves ----
@@ -429,48 +391,6 @@ int narrow_pack_factor(int precision, int variant, int nproma, int klev, bool ae
     return 1;
   return p;
 }
-int precision_code(double, double) { return CLOUDSC_FP64; }
-int precision_code(float, float) { return CLOUDSC_FP32; }
-int precision_code(double, float) { return CLOUDSC_MIXED; }
-
-template <typename real, bool AER, bool FAST, typename S>
-int launch_kcache_packed(hipStream_t st, const KArgs<real, S>& a, int nblocks, int pack, const LaunchEvents* ev) {
-  const PackArgs g{pack, nblocks, (nblocks + pack - 1) / pack};
-  launch_physics(kcache_packed_entry<real, S, DefaultCfg<real>::waves, DefaultCfg<real>::pf, AER, false, FAST>,
-                 dim3(g.ngroups), dim3(64), 0, st, ev, a, g);
-  return CLOUDSC_OK;
-}
-
-// the tendency buffer form of launch_kcache and launch_kcache_packed: the product configuration (in a
-// CLOUDSC_DEBUG_KNOBS build too: CLOUDSC_KCACHE_CFG selects among the plain kernels only)
-template <typename real, bool AER, bool FAST, typename S>
-int launch_kcache_tendbuf(hipStream_t st, const KArgsTB<real, S>& a, int nblocks, int nproma, int pack,
-                          const LaunchEvents* ev) {
-  constexpr int W = DefaultCfg<real>::waves, PF = DefaultCfg<real>::pf;
-  if (pack > 1) {
-    const PackArgs g{pack, nblocks, (nblocks + pack - 1) / pack};
-    launch_physics(kcache_tendbuf_packed_entry<real, S, W, PF, AER, FAST>, dim3(g.ngroups), dim3(64), 0, st, ev, a, g);
-  } else {
-    launch_physics(kcache_tendbuf_entry<real, S, W, PF, AER, FAST>, dim3(nblocks), dim3(nproma), 0, st, ev, a);
-  }
-  return CLOUDSC_OK;
-}
-
-// the prognostic-outputs form of launch_kcache and launch_kcache_packed: the product configuration, as the
-// tendency buffer form
-template <typename real, bool AER, bool FAST, typename S>
-int launch_kcache_outputs(hipStream_t st, const KArgs<real, S>& a, int nblocks, int nproma, int pack,
-                          const LaunchEvents* ev) {
-  constexpr int W = DefaultCfg<real>::waves, PF = DefaultCfg<real>::pf;
-  if (pack > 1) {
-    const PackArgs g{pack, nblocks, (nblocks + pack - 1) / pack};
-    launch_physics(kcache_outputs_packed_entry<real, S, W, PF, AER, FAST>, dim3(g.ngroups), dim3(64), 0, st, ev, a, g);
-  } else {
-    launch_physics(kcache_outputs_entry<real, S, W, PF, AER, FAST>, dim3(nblocks), dim3(nproma), 0, st, ev, a);
-  }
-  return CLOUDSC_OK;
-}
-
 // ---- persistent segmented variant ----
 // Every item is one wave: a block of NPROMA > 64 columns is run as
 // ceil(NPROMA/64) 64-column sub-blocks (the block layout is unchanged: sub-block
@@ -572,18 +492,23 @@ int kseg_grid_size(int per_cu, int ncu, int nitems, int nseg) {
   return grid;
 }
 
-// pk: the packed kernel (one 64-lane workgroup per group of blocks); NULL: the unpacked one;
-// tend_planes (TB): the tendency buffer form of either; PROG: the prognostic-outputs form of either
-template <typename real, int WAVES, int PF, bool AER, bool LDSC, bool FAST, bool TB = false, bool PROG = false,
-          typename S>
-int launch_kseg_cfg(hipStream_t st, const KArgs<real, S>& a0, const PersistArgs<real>& pa, int nproma, int nitems,
-                    int* grid_out, const LaunchEvents* ev, const PackArgs* pk = nullptr, int tend_planes = 0) {
+// Resident workgroups per compute unit of kseg_entry<F>, by workgroup size (0: not asked yet): one
+// table per kernel.  Threads driving different devices may race here, hence atomics.
+template <typename F>
+std::atomic<int> g_kseg_per_cu[65];
+
+// The KSEG launch.  F::pack: one 64-lane workgroup per group of pk.pack blocks.
+template <typename F>
+int launch_kseg_cfg(hipStream_t st, const typename F::kargs& a, const PersistArgs<typename F::real>& pa, int nproma,
+                    int nitems, int* grid_out, const LaunchEvents* ev, const PackArgs& pk) {
+  using real = typename F::real;
   const int nseg = pa.nseg;
-  const auto a = kernel_args<TB>(a0, tend_planes);
-  auto kern = kseg_kernel<real, S, WAVES, PF, AER, LDSC, FAST, TB, PROG>();
-  auto kern_packed = kseg_packed_kernel<real, S, WAVES, PF, AER, LDSC, FAST, TB, PROG>();
-  const int wg = pk ? 64 : kseg_wg(nproma);
-  const size_t lds = LDSC ? carry_lds_bytes<real>(wg) : 0;
+  const auto kern = [] {
+    if constexpr (F::pack) return &kseg_entry<F, PackArgs>;
+    else return &kseg_entry<F>;
+  }();
+  const int wg = F::pack ? 64 : kseg_wg(nproma);
+  const size_t lds = F::ldsc ? carry_lds_bytes<real>(wg) : 0;
   // Waves per SIMD: as many as fit, but no more than whole rounds of the work
   // units (one column's 64-column sub-block) per SIMD: 2560 units on 1024 SIMDs
   // take 2 waves each; a third resident wave (fp32 fits 3) would only find a
@@ -591,17 +516,14 @@ int launch_kseg_cfg(hipStream_t st, const KArgs<real, S>& a0, const PersistArgs<
   // at 2 waves/SIMD against 1.23 ms at 3, profiles/r02/kseg_grid_sweep.jsonl).
   // An over-estimate of residency only delays the extra workgroups: progress
   // never depends on it, items are dequeued in order.
-  // Cached per workgroup size; threads driving different devices may race here, hence atomics.
-  static std::atomic<int> cache[66];   // [65]: the packed kernel
-  const int slot = pk ? 65 : wg;
-  int per_cu = cache[slot].load(std::memory_order_relaxed);
+  std::atomic<int>& cached = g_kseg_per_cu<F>[wg];
+  int per_cu = cached.load(std::memory_order_relaxed);
   if (!per_cu) {
     int n = 0;
-    const hipError_t e = pk ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern_packed, wg, lds)
-                            : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, wg, lds);
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, wg, lds);
     if (e != hipSuccess || n <= 0) n = 1;
     per_cu = n;
-    cache[slot].store(n, std::memory_order_relaxed);
+    cached.store(n, std::memory_order_relaxed);
   }
   int dev = 0, ncu = 0;
   if (hipGetDevice(&dev) != hipSuccess ||
@@ -610,39 +532,11 @@ int launch_kseg_cfg(hipStream_t st, const KArgs<real, S>& a0, const PersistArgs<
   const int grid = kseg_grid_size(per_cu, ncu, nitems, nseg);
   PersistArgs<real> pg = pa;
   pg.nstripes = kseg_nstripes(grid);
-  if (pk) launch_physics(kern_packed, dim3(grid), dim3(wg), lds, st, ev, a, pg, *pk);
+  if constexpr (F::pack) launch_physics(kern, dim3(grid), dim3(wg), lds, st, ev, a, pg, pk);
   else launch_physics(kern, dim3(grid), dim3(wg), lds, st, ev, a, pg);
   *grid_out = grid;
   return CLOUDSC_OK;
 }
-
-template <typename real, bool AER, bool FAST, typename S>
-int launch_kseg(hipStream_t st, const KArgs<real, S>& a, const PersistArgs<real>& pa, int nproma, int nitems,
-                int* grid_out, const LaunchEvents* ev, const PackArgs* pk) {
-#ifdef CLOUDSC_DEBUG_KNOBS
-  switch (env_int("CLOUDSC_KCACHE_CFG", DefaultCfg<real>::code)) {
-#define X(code, w, pf, ldsc) \
-  case code: return launch_kseg_cfg<real, w, pf, AER, ldsc, FAST>(st, a, pa, nproma, nitems, grid_out, ev, pk);
-    CLOUDSC_FOR_EACH_CFG(X)
-#undef X
-    default: return CLOUDSC_EINVAL;
-  }
-#else
-  return launch_kseg_cfg<real, DefaultCfg<real>::waves, DefaultCfg<real>::pf, AER, false, FAST>(st, a, pa, nproma, nitems,
-                                                                                        grid_out, ev, pk);
-#endif
-}
-
-// Experiment builds (make variant VFLAGS=-DCLOUDSC_ONLY_KSEG=8 ...) instantiate
-// only the KSEG kernel of one element size without aerosols -- one kernel to
-// compile instead of twelve, for the per-phase ablation builds of
-// tools/ablation.sh; every other combination returns CLOUDSC_EINVAL.
-#ifdef CLOUDSC_ONLY_KSEG
-#define CLOUDSC_KEEP_KERNEL(real_, kseg_, aer_) \
-  (sizeof(real_) == CLOUDSC_ONLY_KSEG && sizeof(ST) == CLOUDSC_ONLY_KSEG && (kseg_) && !(aer_))
-#else
-#define CLOUDSC_KEEP_KERNEL(real_, kseg_, aer_) true
-#endif
 
 // real: the compute type; ST: the fields' element type (float under a double
 // `real` is CLOUDSC_MIXED: the k-caching kernels only)
@@ -650,52 +544,39 @@ template <typename real, bool FAST, typename ST = real>
 int launch_v(hipStream_t st, int variant, const cloudsc_fields_t* f, int ngptot, int nproma, int klev,
              void* scratch, const void* plude_in, const ParamSet& ps, KsegEpoch* ep, const LaunchEvents* ev,
              int tend_planes, int outputs) {
-#ifdef CLOUDSC_ONLY_KSEG
-  if (variant != CLOUDSC_VARIANT_KSEG || ps.aer || sizeof(real) != CLOUDSC_ONLY_KSEG || sizeof(ST) != sizeof(real))
-    return CLOUDSC_EINVAL;
-#endif
-  constexpr bool kPlain = std::is_same<real, ST>::value;
-  if (!kPlain && variant != CLOUDSC_VARIANT_KCACHE && variant != CLOUDSC_VARIANT_KSEG) return CLOUDSC_EINVAL;
-  // tend_planes != 0: the tendency buffer form: KCACHE and KSEG, fp64, fp32 (its default exp/pow) and mixed,
-  // in the product configuration only -- a CLOUDSC_DEBUG_KNOBS build's CLOUDSC_KCACHE_CFG does not apply to it
-  constexpr bool kTendbuf = !(std::is_same<real, float>::value && !FAST);
-  if (tend_planes && (!kTendbuf || (variant != CLOUDSC_VARIANT_KCACHE && variant != CLOUDSC_VARIANT_KSEG)))
-    return CLOUDSC_EINVAL;
-  // outputs == CLOUDSC_OUTPUTS_PROGNOSTIC: the prognostic-outputs form, where the tendency buffer form exists
-  // and not combined with it
-  const bool prog = outputs == CLOUDSC_OUTPUTS_PROGNOSTIC;
-  if (prog && (!kTendbuf || tend_planes || (variant != CLOUDSC_VARIANT_KCACHE && variant != CLOUDSC_VARIANT_KSEG)))
-    return CLOUDSC_EINVAL;
+  // tend_planes != 0: the tendency buffer form; outputs == CLOUDSC_OUTPUTS_PROGNOSTIC: the prognostic-outputs form
+  const bool aer = ps.aer, tb = tend_planes != 0, prog = outputs == CLOUDSC_OUTPUTS_PROGNOSTIC;
+  if (!kernel_kept<real, ST, FAST>(variant, aer, (tb ? kFormTb : 0u) | (prog ? kFormProg : 0u))) return CLOUDSC_EINVAL;
   KArgs<real, ST> a = make_kargs<real, ST>(
       f, ngptot, nproma, klev, (const DevParams<real>*)((const char*)ps.dev + (sizeof(real) == 8 ? 0 : kSpOffset)));
   if (plude_in) a.plude_in = (const ST*)plude_in;
   const int nblocks = ngptot / nproma + (ngptot % nproma ? 1 : 0);
-  const bool aer = ps.aer;
   if (aer && (!f->pre_ice || !f->picrit_aer || !f->pnice)) return CLOUDSC_EINVAL;
   int rc = CLOUDSC_OK;
   // blocks per wave (1 = unpacked) and the packed launches' extra kernel argument
-  int pack = narrow_pack_factor(precision_code(real(), ST()), variant, nproma, klev, aer);
+  int pack = narrow_pack_factor(kPrecisionOf<real, ST>, variant, nproma, klev, aer);
   // (a packed lane's offset in a tendency buffer: below pack * tend_planes * klev * nproma elements)
   if ((unsigned long long)pack * (unsigned)tend_planes * (unsigned long long)klev * (unsigned)nproma * 8ull >= (1ull << 32))
     pack = 1;
   const PackArgs pk{pack, nblocks, (nblocks + pack - 1) / pack};
+  // The k-caching launch of this call: go(F{}) with the descriptor F of its kernel -- the runtime
+  // conditions become F's members here, and only kernels that exist are instantiated
+  const auto with_form = [&](auto kind, auto&& go) {
+    return dispatch_bools(
+        [&](auto AER, auto PACK, auto TB, auto PROG) {
+          constexpr unsigned form = (PACK ? kFormPack : 0u) | (TB ? kFormTb : 0u) | (PROG ? kFormProg : 0u);
+          if constexpr (kernel_kept<real, ST, FAST>(kind, AER, form))
+            return with_cfg<LaunchForm<real, ST, AER, FAST, form>, cfg_table_applies(kind, form)>(go);
+          else
+            return (int)CLOUDSC_EINVAL;
+        },
+        aer, pack > 1, tb, prog);
+  };
   if (variant == CLOUDSC_VARIANT_KCACHE) {
-    if constexpr (CLOUDSC_KEEP_KERNEL(real, false, false)) {
-      if (tend_planes) {
-        if constexpr (kTendbuf)
-          rc = aer ? launch_kcache_tendbuf<real, true, FAST>(st, kernel_args<true>(a, tend_planes), nblocks, nproma, pack, ev)
-                   : launch_kcache_tendbuf<real, false, FAST>(st, kernel_args<true>(a, tend_planes), nblocks, nproma, pack, ev);
-      } else if (prog) {
-        if constexpr (kTendbuf)
-          rc = aer ? launch_kcache_outputs<real, true, FAST>(st, a, nblocks, nproma, pack, ev)
-                   : launch_kcache_outputs<real, false, FAST>(st, a, nblocks, nproma, pack, ev);
-      } else if (pack > 1)
-        rc = aer ? launch_kcache_packed<real, true, FAST>(st, a, nblocks, pack, ev)
-                 : launch_kcache_packed<real, false, FAST>(st, a, nblocks, pack, ev);
-      else
-        rc = aer ? launch_kcache<real, true, FAST>(st, a, nblocks, nproma, ev)
-                 : launch_kcache<real, false, FAST>(st, a, nblocks, nproma, ev);
-    }
+    rc = with_form(std::integral_constant<int, CLOUDSC_VARIANT_KCACHE>{}, [&](auto form) {
+      using F = decltype(form);
+      return launch_kcache<F>(st, kernel_args<F>(a, tend_planes), nblocks, nproma, pk, ev);
+    });
   } else if (variant == CLOUDSC_VARIANT_KSEG) {
     if (!scratch) return CLOUDSC_EINVAL;
     PersistArgs<real> pa;
@@ -708,7 +589,6 @@ int launch_v(hipStream_t st, int variant, const cloudsc_fields_t* f, int ngptot,
     // the schedule's units: blocks, or groups of `pack` blocks (one flag each:
     // the first pk.ngroups words of the flag area)
     const int nunits = pack > 1 ? pk.ngroups : nblocks;
-    const PackArgs* const pkp = pack > 1 ? &pk : nullptr;
     pa.spin_limit = g_kseg_spin_limit.load(std::memory_order_relaxed);
     // item order (segment, block, sub-block); (segment, sub-block, block) measured
     // the same within noise at NPROMA 128, 2 % slower at 256 (profiles/r01/kseg_subblock_order.jsonl)
@@ -749,23 +629,10 @@ int launch_v(hipStream_t st, int variant, const cloudsc_fields_t* f, int ngptot,
     for (int q = 0; q < kKsegStripes; q++) pa.base[q] = zero_ws ? 0u : ep->base[q];
     pa.stamp = zero_ws ? 0u : ep->stamp;
     int grid = 0;
-    constexpr int W = DefaultCfg<real>::waves, PF = DefaultCfg<real>::pf;
-    if (tend_planes) {
-      if constexpr (kTendbuf && CLOUDSC_KEEP_KERNEL(real, true, true))
-        rc = aer ? launch_kseg_cfg<real, W, PF, true, false, FAST, true>(st, a, pa, nproma, pa.nitems, &grid, ev, pkp,
-                                                                         tend_planes)
-                 : launch_kseg_cfg<real, W, PF, false, false, FAST, true>(st, a, pa, nproma, pa.nitems, &grid, ev, pkp,
-                                                                          tend_planes);
-    } else if (prog) {
-      if constexpr (kTendbuf && CLOUDSC_KEEP_KERNEL(real, true, true))
-        rc = aer ? launch_kseg_cfg<real, W, PF, true, false, FAST, false, true>(st, a, pa, nproma, pa.nitems, &grid, ev, pkp)
-                 : launch_kseg_cfg<real, W, PF, false, false, FAST, false, true>(st, a, pa, nproma, pa.nitems, &grid, ev,
-                                                                                 pkp);
-    } else if constexpr (CLOUDSC_KEEP_KERNEL(real, true, true))
-      rc = aer ? launch_kseg<real, true, FAST>(st, a, pa, nproma, pa.nitems, &grid, ev, pkp)
-               : launch_kseg<real, false, FAST>(st, a, pa, nproma, pa.nitems, &grid, ev, pkp);
-    else if constexpr (CLOUDSC_KEEP_KERNEL(real, true, false))
-      rc = launch_kseg<real, false, FAST>(st, a, pa, nproma, pa.nitems, &grid, ev, pkp);
+    rc = with_form(std::integral_constant<int, CLOUDSC_VARIANT_KSEG>{}, [&](auto form) {
+      using F = decltype(form);
+      return launch_kseg_cfg<F>(st, kernel_args<F>(a, tend_planes), pa, nproma, pa.nitems, &grid, ev, pk);
+    });
     if (rc) return rc;
     HIPCHK(hipGetLastError());
     if (ep) {   // the next launch on this workspace continues where this one ends
@@ -781,17 +648,23 @@ int launch_v(hipStream_t st, int variant, const cloudsc_fields_t* f, int ngptot,
     }
   } else if (variant == CLOUDSC_VARIANT_SCC_PRIVATE) {
     if (klev > kPrivKlev) return CLOUDSC_EINVAL;    // the private arrays are sized at compile time
-    if constexpr (kPlain && CLOUDSC_KEEP_KERNEL(real, false, false)) {
-      if (aer) launch_physics(scc_private_entry<real, true, FAST>, dim3(nblocks), dim3(nproma), 0, st, ev, a);
-      else launch_physics(scc_private_entry<real, false, FAST>, dim3(nblocks), dim3(nproma), 0, st, ev, a);
-    }
+    rc = dispatch_bools(
+        [&](auto AER) {
+          if constexpr (kernel_kept<real, ST, FAST>(CLOUDSC_VARIANT_SCC_PRIVATE, AER))
+            launch_physics(scc_private_entry<real, AER, FAST>, dim3(nblocks), dim3(nproma), 0, st, ev, a);
+          return (int)CLOUDSC_OK;
+        },
+        aer);
   } else {
     if (!scratch) return CLOUDSC_EINVAL;
-    if constexpr (kPlain && CLOUDSC_KEEP_KERNEL(real, false, false)) {
-      SccScratch<real> s = scc_scratch_carve<real>((char*)scratch, nblocks, nproma, klev);
-      if (aer) launch_physics(scc_entry<real, true, FAST>, dim3(nblocks), dim3(nproma), 0, st, ev, a, s);
-      else launch_physics(scc_entry<real, false, FAST>, dim3(nblocks), dim3(nproma), 0, st, ev, a, s);
-    }
+    rc = dispatch_bools(
+        [&](auto AER) {
+          if constexpr (kernel_kept<real, ST, FAST>(CLOUDSC_VARIANT_SCC, AER))
+            launch_physics(scc_entry<real, AER, FAST>, dim3(nblocks), dim3(nproma), 0, st, ev, a,
+                           scc_scratch_carve<real>((char*)scratch, nblocks, nproma, klev));
+          return (int)CLOUDSC_OK;
+        },
+        aer);
   }
   if (rc) return rc;
   HIPCHK(hipGetLastError());
@@ -988,11 +861,11 @@ int cloudsc_gpu_run_tendbuf(int device, void* stream, int precision, int variant
                             int tend_planes, const cloudsc_fields_t* f, void* scratch) {
   // every argument rule first, the device's among them last: no HIP call before an argument error
   if (tend_planes < CLOUDSC_TENDBUF_PLANES_MIN || tend_planes > CLOUDSC_TENDBUF_PLANES_MAX) return CLOUDSC_EINVAL;
-  if (variant & ~0xff) return CLOUDSC_EINVAL;                                                  // no option bits
+  if (variant & ~0xff) return CLOUDSC_EINVAL;   // no option bits (so no fp32 exact-libm)
   const int kind = variant_kind(variant);
-  if (kind != CLOUDSC_VARIANT_KCACHE && kind != CLOUDSC_VARIANT_KSEG) return CLOUDSC_EINVAL;   // no SCC form
   const int rc = validate_shape_args(precision, kind, ngptot, nproma, klev);
   if (rc) return rc;
+  if (!form_exists(kind, precision, /*exact_libm=*/false, kFormTb)) return CLOUDSC_EINVAL;   // no SCC form
   if (!f || !fields_complete(f) || (kind == CLOUDSC_VARIANT_KSEG && !scratch)) return CLOUDSC_EINVAL;
   return gpu_run_impl(device, stream, precision, variant, ngptot, nproma, klev, f, scratch, nullptr, nullptr, nullptr,
                       nullptr, tend_planes);
@@ -1004,11 +877,11 @@ int cloudsc_gpu_run_outputs(int device, void* stream, int precision, int variant
   if (outputs == CLOUDSC_OUTPUTS_ALL)   // cloudsc_gpu_run itself
     return gpu_run_impl(device, stream, precision, variant, ngptot, nproma, klev, f, scratch, nullptr, nullptr);
   // every argument rule first, the device's among them last: no HIP call before an argument error
-  if (variant & ~0xff) return CLOUDSC_EINVAL;                                                  // no option bits
+  if (variant & ~0xff) return CLOUDSC_EINVAL;   // no option bits (so no fp32 exact-libm)
   const int kind = variant_kind(variant);
-  if (kind != CLOUDSC_VARIANT_KCACHE && kind != CLOUDSC_VARIANT_KSEG) return CLOUDSC_EINVAL;   // no SCC form
   const int rc = validate_shape_args(precision, kind, ngptot, nproma, klev);
   if (rc) return rc;
+  if (!form_exists(kind, precision, /*exact_libm=*/false, kFormProg)) return CLOUDSC_EINVAL;   // no SCC form
   if (!f || !fields_complete(f, outputs) || (kind == CLOUDSC_VARIANT_KSEG && !scratch)) return CLOUDSC_EINVAL;
   return gpu_run_impl(device, stream, precision, variant, ngptot, nproma, klev, f, scratch, nullptr, nullptr, nullptr,
                       nullptr, 0, outputs);

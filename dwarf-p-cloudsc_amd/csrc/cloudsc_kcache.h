@@ -60,6 +60,28 @@ struct KArgsTB : KArgs<real, store> {
   int tend_planes;
 };
 
+// One k-caching kernel, described at compile time: the compute and storage
+// types, the configuration (occupancy target WAVES, load schedule PF, aerosol
+// inputs AER, carried state in LDS LDSC, float-internal exp/pow FAST) and the
+// form, a set of kForm* bits:
+//   kFormPack  narrow blocks packed into full waves (PackArgs, below)
+//   kFormTb    the tendency buffer form (KArgsTB)
+//   kFormProg  the prognostic-outputs form (flux_level)
+// The kernel entries, the bodies below and the host's launch path all take the
+// descriptor and read its members by name.
+enum : unsigned { kFormPack = 1u, kFormTb = 2u, kFormProg = 4u };
+template <typename Real, typename Store, int WAVES, int PF, bool AER, bool LDSC, bool FAST, unsigned FORM = 0u>
+struct KForm {
+  using real = Real;
+  using store = Store;
+  static constexpr int waves = WAVES, pf = PF;
+  static constexpr bool aer = AER, ldsc = LDSC, fast = FAST;
+  static constexpr bool pack = (FORM & kFormPack) != 0, tb = (FORM & kFormTb) != 0, prog = (FORM & kFormProg) != 0;
+  using fields = KArgs<real, store>;   // what the bodies read: the kernel arguments, or their base in the TB form
+  using kargs = typename std::conditional<tb, KArgsTB<real, store>, fields>::type;   // the kernel's first argument
+  using params = DevParamsT<real, fast>;                                              // the parameter block
+};
+
 enum { QL = 0, QI = 1, QR = 2, QS = 3, QV = 4 };
 
 // Field access = uniform element index (SGPR arithmetic on a uniform base
@@ -1260,12 +1282,16 @@ __device__ __forceinline__ const auto& params_here(const PV& pv, cptr<PT> cpar) 
 // the carried state `cs`; the plain kernel runs [0, klev) in one go, the
 // persistent kernel (below) runs a column in level segments.
 //
-// TB: the tendency buffer form (KArgsTB; `ka` then points at one).
-// PROG: the prognostic-outputs form (flux_level).
-template <typename real, int PF, bool AER, bool TB = false, bool PROG = false, typename S, typename PT, typename CS,
-          typename LO>
-__device__ __forceinline__ void kcache_levels(cptr<KArgs<real, S>> ka, cptr<PT> cpar, int b,
+// F: the kernel's descriptor (KForm).  F::tb: the tendency buffer form (`ka`
+// then points at a KArgsTB); F::prog: the prognostic-outputs form (flux_level).
+template <typename F, typename CS, typename LO>
+__device__ __forceinline__ void kcache_levels(cptr<typename F::fields> ka, cptr<typename F::params> cpar, int b,
                                               LO lo0, int lev0, int lev1, CS& cs) {
+  using real = typename F::real;
+  using S = typename F::store;
+  using PT = typename F::params;
+  constexpr int PF = F::pf;
+  constexpr bool AER = F::aer;
   if (lev0 >= lev1) return;
   const LO lo = lane_here(lo0);                        // empty segment: no loads at lev0 (may be == klev)
   // PF: 0 = loads at the top of their level, 1 = level k+1 prefetched into
@@ -1301,9 +1327,9 @@ __device__ __forceinline__ void kcache_levels(cptr<KArgs<real, S>> ka, cptr<PT> 
     nb.pmfu_n = ldg(A.pmfu, u2 + (size_t)l1 * nproma, lo_full(lo));
     nb.pmfd_n = ldg(A.pmfd, u2 + (size_t)l1 * nproma, lo_full(lo));
     nb.plu_n = ldg(A.plu, u2 + (size_t)l1 * nproma, lo_full(lo));
-    if (PFX) load_level<real, AER, TB>(cur, A, u2, u3, lev0, klev, nproma, lo);
-    if (PFM) load_early<real, TB>(nxt_e, A, u2, u3, lev0, klev, nproma, lo);
-    if (PFA) load_level<real, AER, TB>(nxt, A, u2, u3, lev0, klev, nproma, lo);
+    if (PFX) load_level<real, AER, F::tb>(cur, A, u2, u3, lev0, klev, nproma, lo);
+    if (PFM) load_early<real, F::tb>(nxt_e, A, u2, u3, lev0, klev, nproma, lo);
+    if (PFA) load_level<real, AER, F::tb>(nxt, A, u2, u3, lev0, klev, nproma, lo);
   }
 #if defined(__HIP_DEVICE_COMPILE__)
   // PF 1: drain the prologue's loads once (per segment) before the level loop.
@@ -1349,13 +1375,13 @@ __device__ __forceinline__ void kcache_levels(cptr<KArgs<real, S>> ka, cptr<PT> 
       const int k1 = k + 1 < klev ? k + 1 : klev - 1;
       const int k2 = k + 2 < klev ? k + 2 : klev - 1;
       const int kh2 = k + 2 < klev + 1 ? k + 2 : klev;
-      if (!PFX && !PFM && !PFA) load_level<real, AER, TB>(cur, A, u2, u3, k, klev, nproma, lo);
+      if (!PFX && !PFM && !PFA) load_level<real, AER, F::tb>(cur, A, u2, u3, k, klev, nproma, lo);
       if (PFA) cur = nxt;
       if (PFM) {
         load_late<real, AER>(cur, A, u2, k, nproma, lo);
         take_early(cur, nxt_e);
       }
-      if (PFX) load_level<real, AER, TB>(nxt, A, u2, u3, k1, klev, nproma, lo);
+      if (PFX) load_level<real, AER, F::tb>(nxt, A, u2, u3, k1, klev, nproma, lo);
       if (NBR) {
         nb.paph_k = ldg(A.paph, uh + (size_t)k * nproma, lo_half(lo));
         nb.paph_n = ldg(A.paph, uh + (size_t)(k + 1) * nproma, lo_half(lo));
@@ -1388,10 +1414,10 @@ __device__ __forceinline__ void kcache_levels(cptr<KArgs<real, S>> ka, cptr<PT> 
         if (PFM || PFA) {
           const int k1 = k + 1 < klev ? k + 1 : klev - 1;
           if (PFM)
-            load_early<real, TB>(nxt_e, *(const KArgs<real, S>*)launder_uniform(ka), u2, u3, k1, klev, nproma,
+            load_early<real, F::tb>(nxt_e, *(const KArgs<real, S>*)launder_uniform(ka), u2, u3, k1, klev, nproma,
                              launder_vgpr(lo0));
           else
-            load_level<real, AER, TB>(nxt, *(const KArgs<real, S>*)launder_uniform(ka), u2, u3, k1, klev, nproma,
+            load_level<real, AER, F::tb>(nxt, *(const KArgs<real, S>*)launder_uniform(ka), u2, u3, k1, klev, nproma,
                                   launder_vgpr(lo0));
         }
       };
@@ -1412,8 +1438,8 @@ __device__ __forceinline__ void kcache_levels(cptr<KArgs<real, S>> ka, cptr<PT> 
       // (packed: a fresh copy as well, so that neither the top-of-level copy nor the
       // offsets formed from it stay live across the physics)
       const LO los = PVR || std::is_same<LO, PackLo>::value ? launder_vgpr(lo0) : lo;
-      store_level<TB>(A, u2, u3, k, klev, nproma, los, physics, ls, po);
-      flux_level<PROG>(c, A, uh + (size_t)(k + 1) * nproma, los, cur, ls, po, nb.paph_k, nb.paph_n, cs);
+      store_level<F::tb>(A, u2, u3, k, klev, nproma, los, physics, ls, po);
+      flux_level<F::prog>(c, A, uh + (size_t)(k + 1) * nproma, los, cur, ls, po, nb.paph_k, nb.paph_n, cs);
     }
 
     // ---- rotate carried state ----
@@ -1434,22 +1460,6 @@ struct CarryRegs : CarryState<real> {
 };
 template <typename real, bool LDSC>
 using CarryOf = typename std::conditional<LDSC, CarryLds<real>, CarryRegs<real>>::type;
-
-template <typename real, int PF, bool AER, bool LDSC, bool TB = false, bool PROG = false, typename S, typename PT>
-__device__ __forceinline__ void cloudsc_kcache_body(cptr<KArgs<real, S>> ka, cptr<PT> cpar) {
-  const KArgs<real, S>& A = *(const KArgs<real, S>*)ka;
-  const int b = blockIdx.x, jl = threadIdx.x;
-  if (jl >= A.nproma || b * A.nproma + jl >= A.ngptot) return;
-  const unsigned lo = (unsigned)jl * (unsigned)sizeof(S);   // the lane's byte offset in a field plane
-  CarryOf<real, LDSC> cs(carry_lds_base<real>());
-  init_carry<real, PROG>(cs);
-  {
-    CLOUDSC_PARAMS_HERE;
-    flux_top<PROG>(c, A, (size_t)b * (A.klev + 1) * A.nproma, lo);
-  }
-  kcache_levels<real, PF, AER, TB, PROG>(ka, cpar, b, lo, 0, A.klev, cs);
-  stg(((const KArgs<real, S>*)launder_uniform(ka))->prainfrac, (size_t)b * A.nproma, lo, cs.rainfrac);
-}
 
 // ===================== narrow blocks packed into full waves =====================
 // NPROMA <= 32: one wave walks pack = 64 / nproma consecutive blocks b0 .. b0 +
@@ -1481,22 +1491,33 @@ __device__ __forceinline__ bool pack_lane(int ngptot, int nproma, int klev, cons
   return s < (unsigned)G.pack && b < (unsigned)G.nblocks && b * np + jl < (unsigned)ngptot;
 }
 
-template <typename real, int PF, bool AER, bool LDSC, bool TB = false, bool PROG = false, typename S, typename PT>
-__device__ __forceinline__ void cloudsc_kcache_packed_body(cptr<KArgs<real, S>> ka, cptr<PT> cpar,
-                                                           const PackArgs& G) {
+// The one-shot kernel: a workgroup runs every level of its block (F::pack: one
+// wave those of its group of G.pack blocks, b then the group's first block).
+template <typename F>
+__device__ __forceinline__ void cloudsc_kcache_body(cptr<typename F::fields> ka, cptr<typename F::params> cpar,
+                                                    const PackArgs& G = PackArgs{1, 0, 0}) {
+  using real = typename F::real;
+  using S = typename F::store;
+  using PT = typename F::params;
   const KArgs<real, S>& A = *(const KArgs<real, S>*)ka;
-  const int b0 = (int)blockIdx.x * G.pack;
-  PackLo lo;
-  unsigned sub;
-  if (!pack_lane<S>(A.ngptot, A.nproma, A.klev, G, b0, lo, sub)) return;
-  CarryOf<real, LDSC> cs(carry_lds_base<real>());
-  init_carry<real, PROG>(cs);
+  const int b = F::pack ? (int)blockIdx.x * G.pack : (int)blockIdx.x;
+  typename std::conditional<F::pack, PackLo, unsigned>::type lo;   // the lane's byte offset in a field plane
+  if constexpr (F::pack) {
+    unsigned sub;
+    if (!pack_lane<S>(A.ngptot, A.nproma, A.klev, G, b, lo, sub)) return;
+  } else {
+    const int jl = threadIdx.x;
+    if (jl >= A.nproma || b * A.nproma + jl >= A.ngptot) return;
+    lo = (unsigned)jl * (unsigned)sizeof(S);
+  }
+  CarryOf<real, F::ldsc> cs(carry_lds_base<real>());
+  init_carry<real, F::prog>(cs);
   {
     CLOUDSC_PARAMS_HERE;
-    flux_top<PROG>(c, A, (size_t)b0 * (A.klev + 1) * A.nproma, lo);
+    flux_top<F::prog>(c, A, (size_t)b * (A.klev + 1) * A.nproma, lo);
   }
-  kcache_levels<real, PF, AER, TB, PROG>(ka, cpar, b0, lo, 0, A.klev, cs);
-  stg(((const KArgs<real, S>*)launder_uniform(ka))->prainfrac, (size_t)b0 * A.nproma, lo_surf(lane_here(lo)),
+  kcache_levels<F>(ka, cpar, b, lo, 0, A.klev, cs);
+  stg(((const KArgs<real, S>*)launder_uniform(ka))->prainfrac, (size_t)b * A.nproma, lo_surf(lane_here(lo)),
       cs.rainfrac);
 }
 
@@ -1587,14 +1608,18 @@ __device__ __forceinline__ void carry_io(real* st, size_t u, size_t plane, unsig
 #undef CLOUDSC_CARRY_IO
 }
 
-// PACK: the schedule runs over groups of G.pack blocks instead of blocks (items
+// F::pack: the schedule runs over groups of G.pack blocks instead of blocks (items
 // are (segment, group), stripes are taken over groups, one flag per group: the
 // first G.ngroups words of the flag area); the carried state keeps its layout.
-template <typename real, int PF, bool AER, bool LDSC, bool PACK = false, bool TB = false, bool PROG = false,
-          typename ST, typename PT>
-__device__ __forceinline__ void cloudsc_kcache_persistent_body(cptr<KArgs<real, ST>> ka, cptr<PT> cpar,
-                                                               const PersistArgs<real>& P,
+template <typename F>
+__device__ __forceinline__ void cloudsc_kcache_persistent_body(cptr<typename F::fields> ka,
+                                                               cptr<typename F::params> cpar,
+                                                               const PersistArgs<typename F::real>& P,
                                                                const PackArgs& G = PackArgs{1, 0, 0}) {
+  using real = typename F::real;
+  using ST = typename F::store;
+  using PT = typename F::params;
+  constexpr bool PACK = F::pack;
   __shared__ int s_item;
   const KArgs<real, ST>& A = *(const KArgs<real, ST>*)ka;
   const int nproma = A.nproma, nsub = PACK ? 1 : P.nsub;
@@ -1656,12 +1681,12 @@ __device__ __forceinline__ void cloudsc_kcache_persistent_body(cptr<KArgs<real, 
     unsigned long long t_ready = t_start;
 #endif
     const size_t ust = (size_t)b * kCarryN * nproma;
-    CarryOf<real, LDSC> cs(carry_lds_base<real>());
+    CarryOf<real, F::ldsc> cs(carry_lds_base<real>());
     if (seg == 0) {
-      init_carry<real, PROG>(cs);
+      init_carry<real, F::prog>(cs);
       if (active) {
         CLOUDSC_PARAMS_HERE;
-        flux_top<PROG>(c, A, (size_t)b * (A.klev + 1) * nproma, lo);
+        flux_top<F::prog>(c, A, (size_t)b * (A.klev + 1) * nproma, lo);
       }
     } else {
       // consumer: one relaxed poll (bounded, with s_sleep), one agent acquire,
@@ -1684,15 +1709,15 @@ __device__ __forceinline__ void cloudsc_kcache_persistent_body(cptr<KArgs<real, 
 #ifdef CLOUDSC_KSEG_TRACE
       t_ready = __builtin_amdgcn_s_memrealtime();
 #endif
-      if (active) carry_io<PROG>(P.state, ust, (size_t)nproma, lo_c, cs, false);
+      if (active) carry_io<F::prog>(P.state, ust, (size_t)nproma, lo_c, cs, false);
     }
-    if (active) kcache_levels<real, PF, AER, TB, PROG>(ka, cpar, b, lo, P.lev[seg], P.lev[seg + 1], cs);
+    if (active) kcache_levels<F>(ka, cpar, b, lo, P.lev[seg], P.lev[seg + 1], cs);
     const auto lo_e = lane_here(lo);   // packed: the offsets below formed here, not live across the levels
     if constexpr (PACK) lo_c = (lo_e.sb * (unsigned)kCarryN + lo_e.jb) / (unsigned)sizeof(ST) * (unsigned)sizeof(real);
     if (seg + 1 < P.nseg) {
       // producer (G16 R1): sc1 payload stores, every wave drains, barrier, the
       // flag stored with an agent atomic
-      if (active) carry_io<PROG>(P.state, ust, (size_t)nproma, lo_c, cs, true);
+      if (active) carry_io<F::prog>(P.state, ust, (size_t)nproma, lo_c, cs, true);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
       if (wave0) __hip_atomic_store(P.flags + sb, P.stamp + (unsigned)(seg + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -1,7 +1,8 @@
 """Host-side pieces of the round-5 measurements, without a GPU: the board-power
 sampler of bench.py (cloudsc_power), the selection of the timed launches from a
 rocprofv3 kernel trace (tools/timed_stats.py), the counter calibration's
-analysis (tools/calib_counters.py), the argument checks of the new C entry
+analysis (tools/calib_counters.py), the device assembly comparison
+(tools/asm_compare.py), the argument checks of the new C entry
 points that run before any device call, and the CLI's --place option."""
 import csv
 import ctypes as C
@@ -90,6 +91,58 @@ def test_calibration_analysis(tmp_path):
     for width in (4, 8, 16):
         assert res["read_%dB_per_lane" % width]["FETCH_SIZE"]["bytes_per_counter_byte"] == 2.0
         assert res["write_%dB_per_lane" % width]["WRITE_SIZE"]["bytes_per_counter_byte"] == 1.0
+
+
+def _asm_function(number, name, body, kernel=True):
+    """One function as the compiler writes it: directives, the label, the body, the kernel descriptor."""
+    text = "\t.globl\t%s\n\t.p2align\t8\n\t.type\t%s,@function\n%s:  ; @%s\n; %%bb.0:\n" % (name, name, name, name)
+    text += body.replace("LBB_", "LBB%d_" % number)
+    if kernel:
+        text += ("\t.section\t.rodata,\"a\",@progbits\n\t.amdhsa_kernel %s\n\t\t.amdhsa_next_free_vgpr %d\n"
+                 "\t.end_amdhsa_kernel\n\t.text\n" % (name, 8 + number))
+    return text + ".Lfunc_end%d:\n\t.size\t%s, .Lfunc_end%d-%s\n\t; -- End function\n" % (number, name, number, name)
+
+
+def test_asm_compare_counts_differing_lines_per_function(tmp_path):
+    import asm_compare
+    loop = ("\ts_load_dword s2, s[0:1], 0x0 ; %s\n\ts_cbranch_execz .LBB_2\n.LBB_1:  ; =>This Loop Header\n"
+            "\tv_add_u32_e32 v0, s2, v0\n\ts_cbranch_execnz .LBB_1\n.LBB_2:\n\ts_endpgm\n")
+    straight = "\tv_mov_b32_e32 v1, %s\n\tglobal_store_dword v0, v1, s[0:1]\n\ts_endpgm\n"
+    helper = "\tv_mul_f32_e32 v0, v0, v0\n\ts_setpc_b64 s[30:31]\n"
+    # B has one more function in front (other label numbers and comments), one changed instruction in
+    # `scale`, `old_entry` under the name `new_entry`, and no `gone`
+    a = (_asm_function(0, "same", loop % "first comment") + _asm_function(1, "scale", straight % "0") +
+         _asm_function(2, "old_entry", loop % "x") + _asm_function(3, "helper", helper, kernel=False) +
+         _asm_function(4, "gone", straight % "3"))
+    b = (_asm_function(0, "added", straight % "7") + _asm_function(1, "same", loop % "another comment") +
+         _asm_function(2, "scale", straight % "1") + _asm_function(3, "new_entry", loop % "y") +
+         _asm_function(4, "helper", helper, kernel=False))
+    lines, bad = asm_compare.compare(a, b, [("old_entry", "new_entry")])
+    assert lines[0] == "kernels: A 4, B 4"
+    found = {ln.split("differing")[1].split()[0]: (int(ln.split()[0]), int(ln.split()[2]))
+             for ln in lines if " differing " in ln}
+    assert found == {"same": (7, 0), "scale": (3, 1), "new_entry": (7, 0), "helper": (2, 0)}
+    assert "only in A: gone" in lines and "only in B: added" in lines
+    assert bad == 3                                   # scale differs, gone and added have no partner
+    # without the map the renamed function has no partner on either side
+    lines, bad = asm_compare.compare(a, b)
+    assert "only in A: old_entry" in lines and "only in B: new_entry" in lines and bad == 5
+    # the command line: the map from a file, a literal and a regular-expression rule; exit status 1 on a difference
+    fa, fb, fm = tmp_path / "a.s", tmp_path / "b.s", tmp_path / "map.txt"
+    fa.write_text(a)
+    fb.write_text(b)
+    fm.write_text("# renames\nre: old_(\\w+) => new_\\1\ngone => added\n")
+    run = subprocess.run([sys.executable, os.path.join(TOOLS, "asm_compare.py"), str(fa), str(fb), "--map", str(fm)],
+                         capture_output=True, text=True)
+    out = run.stdout.splitlines()
+    assert run.returncode == 1 and out[0] == "kernels: A 4, B 4"
+    assert "     7 instr     0 differing  new_entry  (was old_entry)" in out
+    assert "     3 instr     1 differing  scale" in out
+    assert "     3 instr     1 differing  added  (was gone)" in out
+    assert not [ln for ln in out if ln.startswith("only in")]
+    same = subprocess.run([sys.executable, os.path.join(TOOLS, "asm_compare.py"), str(fa), str(fa)],
+                          capture_output=True, text=True)
+    assert same.returncode == 0 and same.stdout.splitlines()[0] == "kernels: A 4, B 4"
 
 
 @pytest.fixture(scope="module")

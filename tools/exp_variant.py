@@ -11,6 +11,8 @@ import subprocess
 import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from asm_compare import demangle  # noqa: E402  (mangled name -> demangled name without the parameter list)
 
 
 def main():
@@ -38,13 +40,17 @@ def main():
     r = subprocess.run(cmd[:-2 - len(srcs)] + [os.path.join(tmp, "csrc", "cloudsc_gpu.hip"), "-S",
                         "--cuda-device-only", "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"],
                        capture_output=True, text=True)
+    # (by demangled name: the plain unpacked fp64 kernels and the fp32 KSEG ones)
+    main_kernels = ("void kseg_entry<cloudsc::KForm<double, double, ", "void kcache_entry<cloudsc::KForm<double, double, ",
+                    "void kseg_entry<cloudsc::KForm<float, float, ")
     cur = None
     for line in r.stderr.splitlines():
         if "Function Name:" in line:
-            cur = line.split("Function Name:")[1].split()[0]
-        elif cur and ("kseg_entryId" in cur or "kcache_entryId" in cur or "kseg_entryIf" in cur) and \
+            sym = line.split("Function Name:")[1].split()[0]
+            cur = demangle([sym])[sym]
+        elif cur and cur.startswith(main_kernels) and cur.endswith(", 0u>>") and \
                 ("VGPRs:" in line or "ScratchSize" in line or "Occupancy" in line):
-            print(cur[:40], line.split("remark:")[1].split("[-R")[0].strip())
+            print(cur[5:], line.split("remark:")[1].split("[-R")[0].strip())
     print("built", out)
 
 

@@ -17,6 +17,8 @@ import sys
 import tempfile
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from asm_compare import demangle  # noqa: E402  (mangled name -> demangled name without the parameter list)
 
 
 def main():
@@ -29,10 +31,13 @@ def main():
                            "--cuda-device-only", "-S", os.path.join(REPO, "dwarf-p-cloudsc_amd", "csrc", "cloudsc_gpu.hip"),
                            "-o", out] + sys.argv[2:], stderr=subprocess.DEVNULL)
     L = open(out).read().split("\n")
-    # the product kernel: no aerosols, no LDS carry; fp32 FAST (last flag 1), fp64 exact (0)
-    name = r"^_Z10kseg_entryI%sLi2ELi%dELb0ELb0ELb%dE.*:" % ("d" if es == 8 else "f", 3 if es == 8 else 1,
-                                                             0 if es == 8 else 1)
-    st = next(i for i, l in enumerate(L) if re.match(name, l))
+    # the product kernel, by demangled name: plain and unpacked, no aerosols, no LDS carry; fp32 FAST, fp64 exact
+    t = "double" if es == 8 else "float"
+    want = "void kseg_entry<cloudsc::KForm<%s, %s, 2, %d, false, false, %s, 0u>>" % (
+        t, t, 3 if es == 8 else 1, "false" if es == 8 else "true")
+    syms = [m.group(1) for l in L for m in [re.match(r"^(\w+):", l)] if m and "kseg_entry" in m.group(1)]
+    name = next(sym for sym, dem in demangle(syms).items() if dem == want)
+    st = L.index(next(l for l in L if l.startswith(name + ":")))
     en = next(i for i in range(st, len(L)) if L[i].startswith(".Lfunc_end"))
     L = L[st:en]
     labels = {m.group(1): i for i, l in enumerate(L) for m in [re.match(r"^(\.LBB\d+_\d+):", l)] if m}
