@@ -27,6 +27,13 @@ _oracle = None
 _ref = None
 
 
+def use_oracle_library(path: str) -> None:
+    """Load the restatement from another build of oracle/cloudsc_oracle.c (tools/oracle_coverage.py: one
+    compiled with --coverage) instead of liboracle.so, for the run_oracle calls that follow."""
+    global _oracle, ORACLE_LIB
+    ORACLE_LIB, _oracle = path, None
+
+
 def oracle_lib():
     global _oracle
     if _oracle is None:

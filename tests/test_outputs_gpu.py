@@ -165,10 +165,11 @@ class Sets:
             s.close()
 
 
-def prognostic_parity(s, variant, oracle=None, stream=None):
-    """cloudsc_gpu_run on "all", PROGNOSTIC on "null" and "kept"; the eleven kept members on the device and on
-    the host."""
-    s.run("all", variant, None, stream)
+def prognostic_parity(s, variant, oracle=None, stream=None, run_all=True):
+    """cloudsc_gpu_run on "all" (run_all False: the caller has run it), PROGNOSTIC on "null" and "kept"; the
+    eleven kept members on the device and on the host."""
+    if run_all:
+        s.run("all", variant, None, stream)
     for w in ("null", "kept"):
         s.run(w, variant, ca.OUTPUTS_PROGNOSTIC, stream)
         assert not any(getattr(s.sets["null"].f, n) for n in DIAG)

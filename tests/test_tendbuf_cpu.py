@@ -149,9 +149,10 @@ def test_cli_fields_tendbuf_refusals(extra):
 _plain = {}
 
 
-def plain_run(ds, ngptot, nproma, precision):
-    """cloudsc_cpu_run_precision on separate arrays: {name: block-layout array}, once per case, read-only."""
-    key = (ngptot, nproma, precision)
+def plain_run(ds, ngptot, nproma, precision, key="ds"):
+    """cloudsc_cpu_run_precision on separate arrays: {name: block-layout array}, once per case (key: a name
+    for the dataset), read-only."""
+    key = (key, ngptot, nproma, precision)
     if key not in _plain:
         st, _ = ca.cpu_run(ds, ngptot, nproma, nthreads=4, precision=precision)
         for a in st.arrays.values():
@@ -172,7 +173,17 @@ CPU_SHAPES = list(tb.SHAPES)
 @pytest.mark.parametrize("precision", [ca.FP64, ca.MIXED])
 @pytest.mark.parametrize("ngptot,nproma", CPU_SHAPES)
 def test_cpu_run_tendbuf_bitwise(ds, oracle_mod, ngptot, nproma, precision, tend_planes, order):
-    ref = plain_run(ds, ngptot, nproma, precision)
+    got = run_tendbuf_checked(ds, ngptot, nproma, precision, tend_planes, order)
+    if precision == ca.FP64:
+        ost, _ = oracle_mod.run_oracle(ds, ngptot, nproma)
+        for k in NAMES:
+            assert np.array_equal(tb.bits(columns(got[k], ngptot)), tb.bits(columns(ost.arrays[k], ngptot))), k
+
+
+def run_tendbuf_checked(ds, ngptot, nproma, precision, tend_planes, order, key="ds"):
+    """cloudsc_cpu_run_tendbuf on the dataset (key: a name for it), checked against cloudsc_cpu_run_precision
+    and for the sentinels; returns {name: block-layout array} of the 21 fields."""
+    ref = plain_run(ds, ngptot, nproma, precision, key)
     st = ca.make_host_state(ds, ngptot, nproma, precision)
     nb, dt = ca.nblocks_of(ngptot, nproma), ca.storage_dtype(precision)
     lay = tb.layout(order, tend_planes)
@@ -190,17 +201,13 @@ def test_cpu_run_tendbuf_bitwise(ds, oracle_mod, ngptot, nproma, precision, tend
                        nthreads=3)
     assert np.array_equal(tb.bits(buf_tmp), tb.bits(tmp_before))            # inputs are only read
     assert tb.is_sentinel(buf_loc, tb.untouched_mask(buf_loc, lay, tb.LOC, ngptot), tb.SENTINEL_LOC)
+    got = {k: tb.take(buf_loc, lay[k], k) if k in tb.LOC else st.arrays[k] for k in NAMES}
     bad = {}
     for k in NAMES:
-        got = tb.take(buf_loc, lay[k], k) if k in tb.LOC else st.arrays[k]
-        if not np.array_equal(tb.bits(columns(got, ngptot)), tb.bits(columns(ref[k], ngptot))):
+        if not np.array_equal(tb.bits(columns(got[k], ngptot)), tb.bits(columns(ref[k], ngptot))):
             bad[k] = "differs from cloudsc_cpu_run_precision"
     assert bad == {}
-    if precision == ca.FP64:
-        ost, _ = oracle_mod.run_oracle(ds, ngptot, nproma)
-        for k in NAMES:
-            got = tb.take(buf_loc, lay[k], k) if k in tb.LOC else st.arrays[k]
-            assert np.array_equal(tb.bits(columns(got, ngptot)), tb.bits(columns(ost.arrays[k], ngptot))), k
+    return got
 
 
 # ---------------------------------------------------------------------------

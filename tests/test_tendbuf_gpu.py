@@ -93,11 +93,13 @@ class Pair:
         p = ca.Params.from_dict(ds.params)
         ca.check(lib.cloudsc_gpu_init(0, C.byref(p)))
 
-    def fill(self):
-        self.plain.upload(self.host)
-        self.packed.upload({k: v for k, v in self.host.items() if not k.startswith("tendency_")})
-        assert self.hip.hipMemcpy(self.packed.buffer_tmp, self.buf_tmp.ctypes.data, self.buf_tmp.nbytes, 1) == 0
-        assert self.hip.hipMemcpy(self.packed.buffer_loc, self.buf_loc.ctypes.data, self.buf_loc.nbytes, 1) == 0
+    def fill(self, which=("plain", "packed")):
+        if "plain" in which:
+            self.plain.upload(self.host)
+        if "packed" in which:
+            self.packed.upload({k: v for k, v in self.host.items() if not k.startswith("tendency_")})
+            assert self.hip.hipMemcpy(self.packed.buffer_tmp, self.buf_tmp.ctypes.data, self.buf_tmp.nbytes, 1) == 0
+            assert self.hip.hipMemcpy(self.packed.buffer_loc, self.buf_loc.ctypes.data, self.buf_loc.nbytes, 1) == 0
 
     def scratch(self, variant):
         if variant & 0xff == ca.VARIANT_KSEG and not self.ws.value:
@@ -108,16 +110,18 @@ class Pair:
             assert self.hip.hipMemset(self.ws, 0, C.c_size_t(256)) == 0
         return self.ws
 
-    def run_both(self, variant, stream=None):
+    def run_both(self, variant, stream=None, which=("plain", "packed")):
         """cloudsc_gpu_run on `plain`, cloudsc_gpu_run_tendbuf on `packed` (each followed by its check)."""
         ws = self.scratch(variant)
         k = self.ds.klev
-        ca.check(self.lib.cloudsc_gpu_run(0, stream, self.precision, variant, self.ngptot, self.nproma, k,
-                                          C.byref(self.plain.f), ws))
-        assert self.lib.cloudsc_gpu_check(0, stream, variant & 0xff, ws) == 0
-        ca.gpu_run_tendbuf(self.packed.f, self.precision, variant, self.ngptot, self.nproma, k, self.tend_planes,
-                           scratch=ws, stream=stream)
-        assert self.lib.cloudsc_gpu_check(0, stream, variant & 0xff, ws) == 0
+        if "plain" in which:
+            ca.check(self.lib.cloudsc_gpu_run(0, stream, self.precision, variant, self.ngptot, self.nproma, k,
+                                              C.byref(self.plain.f), ws))
+            assert self.lib.cloudsc_gpu_check(0, stream, variant & 0xff, ws) == 0
+        if "packed" in which:
+            ca.gpu_run_tendbuf(self.packed.f, self.precision, variant, self.ngptot, self.nproma, k, self.tend_planes,
+                               scratch=ws, stream=stream)
+            assert self.lib.cloudsc_gpu_check(0, stream, variant & 0xff, ws) == 0
 
     def device_mismatches(self, stream=None):
         """Unpack BUFFER_LOC into the packed set's separate arrays, then cloudsc_fields_compare of its 21
