@@ -508,6 +508,19 @@ def gpu_lib(path: Optional[str] = None):
                                             C.POINTER(Fields), C.POINTER(Reference), C.POINTER(Stats)]
     lib.cloudsc_fields_expand.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_longlong,
                                           C.POINTER(Template), C.POINTER(Fields)]
+    # the tendency buffers with an output selection, and compare / validate / expand on them in place
+    if hasattr(lib, "cloudsc_gpu_run_tendbuf_outputs"):   # (an older library under CLOUDSC_AMD_LIB, for A/B runs, lacks them)
+        lib.cloudsc_gpu_run_tendbuf_outputs.argtypes = [C.c_int, C.c_void_p] + [C.c_int] * 7 + [C.POINTER(Fields),
+                                                                                                 C.c_void_p]
+        lib.cloudsc_cpu_run_tendbuf_outputs.argtypes = [C.c_int] * 7 + [C.POINTER(Params), C.POINTER(Fields)]
+        lib.cloudsc_fields_compare_tendbuf.argtypes = lib.cloudsc_fields_convert_tendbuf.argtypes + \
+            [C.POINTER(FieldDiff)]
+        lib.cloudsc_cpu_fields_compare_tendbuf.argtypes = lib.cloudsc_cpu_fields_convert_tendbuf.argtypes + \
+            [C.POINTER(FieldDiff)]
+        lib.cloudsc_fields_validate_tendbuf.argtypes = [C.c_int, C.c_void_p] + [C.c_int] * 6 + [
+            C.c_longlong, C.POINTER(Fields), C.POINTER(Reference), C.POINTER(Stats)]
+        lib.cloudsc_fields_expand_tendbuf.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                      C.c_longlong, C.POINTER(Template), C.POINTER(Fields)]
     lib.cloudsc_fields_diff_sizeof.restype = C.c_longlong
     lib.cloudsc_fields_compare_release.argtypes = [C.c_int]
     lib.cloudsc_debug_set_compare_grid.argtypes = [C.c_int]
@@ -673,6 +686,23 @@ def cpu_run_outputs(params: "Params", f: "Fields", precision: int, outputs: int,
                                             C.byref(f)))
 
 
+def gpu_run_tendbuf_outputs(f: "Fields", precision: int, variant: int, outputs: int, ngptot: int, nproma: int,
+                            klev: int, tend_planes: int, scratch=None, device: int = 0, stream=None) -> None:
+    """cloudsc_gpu_run_tendbuf_outputs: gpu_run_tendbuf with an output selection.  OUTPUTS_ALL is
+    cloudsc_gpu_run_tendbuf; with OUTPUTS_PROGNOSTIC the DIAGNOSTIC_FLUX_FIELDS members are neither read nor
+    written (they may be None).  Asynchronous on `stream`; KSEG callers follow it with cloudsc_gpu_check."""
+    check(gpu_lib().cloudsc_gpu_run_tendbuf_outputs(device, stream, precision, variant, outputs, ngptot, nproma,
+                                                    klev, tend_planes, C.byref(f), scratch))
+
+
+def cpu_run_tendbuf_outputs(params: "Params", f: "Fields", precision: int, outputs: int, ngptot: int, nproma: int,
+                            klev: int, tend_planes: int, nthreads: int = 0) -> None:
+    """cloudsc_cpu_run_tendbuf_outputs: the CPU variant on HOST fields whose tendency members are planes of
+    packed buffers, with an output selection (precision FP64 or MIXED)."""
+    check(gpu_lib().cloudsc_cpu_run_tendbuf_outputs(nthreads, precision, outputs, ngptot, nproma, klev, tend_planes,
+                                                    C.byref(params), C.byref(f)))
+
+
 def convert_fields_tendbuf(src: "Fields", dst: "Fields", ngptot: int, klev: int, src_precision: int,
                            src_nproma: int, src_tend_planes: int, dst_precision: int, dst_nproma: int,
                            dst_tend_planes: int, device: int = 0, stream=None) -> None:
@@ -719,6 +749,50 @@ def cpu_compare_fields(a: "HostState", b: "HostState", names=None, nthreads: int
     check(gpu_lib().cloudsc_cpu_fields_compare(nthreads, a.ngptot, a.klev, a.precision, a.nproma, C.byref(fa),
                                                b.precision, b.nproma, C.byref(fb), diffs))
     return _diffs_to_dict(diffs)
+
+
+def compare_fields_tendbuf(a: "Fields", b: "Fields", ngptot: int, klev: int, a_precision: int, a_nproma: int,
+                           a_tend_planes: int, b_precision: int, b_nproma: int, b_tend_planes: int,
+                           device: int = 0, stream=None) -> Dict[str, dict]:
+    """cloudsc_fields_compare_tendbuf: compare_fields with the tendency members of a and / or b read in place
+    from packed buffers (*_tend_planes planes per block, 0 = separate arrays)."""
+    diffs = (FieldDiff * len(ALL_FIELDS))()
+    check(gpu_lib().cloudsc_fields_compare_tendbuf(device, stream, ngptot, klev, a_precision, a_nproma,
+                                                   a_tend_planes, C.byref(a), b_precision, b_nproma, b_tend_planes,
+                                                   C.byref(b), diffs))
+    return _diffs_to_dict(diffs)
+
+
+def cpu_compare_fields_tendbuf(a: "Fields", b: "Fields", ngptot: int, klev: int, a_precision: int, a_nproma: int,
+                               a_tend_planes: int, b_precision: int, b_nproma: int, b_tend_planes: int,
+                               nthreads: int = 0) -> Dict[str, dict]:
+    """cloudsc_cpu_fields_compare_tendbuf: the same on HOST arrays."""
+    diffs = (FieldDiff * len(ALL_FIELDS))()
+    check(gpu_lib().cloudsc_cpu_fields_compare_tendbuf(nthreads, ngptot, klev, a_precision, a_nproma, a_tend_planes,
+                                                       C.byref(a), b_precision, b_nproma, b_tend_planes, C.byref(b),
+                                                       diffs))
+    return _diffs_to_dict(diffs)
+
+
+def validate_fields_tendbuf(f: "Fields", ref: "Reference", precision: int, ngptot: int, nproma: int, klev: int,
+                            tend_planes: int, outputs: int = OUTPUTS_ALL, col_offset: int = 0, device: int = 0,
+                            stream=None) -> list:
+    """cloudsc_fields_validate_tendbuf: the validated members of DEVICE fields against the KLON-column
+    reference, the tendency members read in place from packed buffers (tend_planes 0 = separate arrays).  With
+    OUTPUTS_PROGNOSTIC the DIAGNOSTIC_FLUX_FIELDS members and their reference arrays may be None: their
+    records are the skipped record.  Returns the Stats array in VALIDATED order (waits for `stream`)."""
+    stats = (Stats * len(VALIDATED))()
+    check(gpu_lib().cloudsc_fields_validate_tendbuf(device, stream, precision, ngptot, nproma, klev, tend_planes,
+                                                    outputs, col_offset, C.byref(f), C.byref(ref), stats))
+    return stats
+
+
+def expand_fields_tendbuf(f: "Fields", tmpl: "Template", precision: int, ngptot: int, nproma: int, tend_planes: int,
+                          col_offset: int = 0, device: int = 0, stream=None) -> None:
+    """cloudsc_fields_expand_tendbuf: fill the non-None input members of DEVICE fields from the template,
+    tendency_tmp_* straight into their planes of a packed buffer.  Asynchronous on `stream`."""
+    check(gpu_lib().cloudsc_fields_expand_tendbuf(device, stream, precision, ngptot, nproma, tend_planes, col_offset,
+                                                  C.byref(tmpl), C.byref(f)))
 
 
 def compare_grid(workgroups: int = 0) -> None:
@@ -1115,7 +1189,7 @@ class DeviceFields:
     def validate(self, ds: "Dataset", col_offset: int = 0, stream=None) -> list:
         """cloudsc_fields_validate: the 21 validated fields against ds.reference on the device; the list
         of 7-tuples GpuState.validate returns.  (A tend_planes set: its separate arrays, self.separate --
-        the validation has no packed form; unpack BUFFER_LOC first.)"""
+        unpack BUFFER_LOC first, or validate it in place with validate_fields_tendbuf.)"""
         keep: list = []
         ref = make_reference(ds, keep)
         st = (Stats * 21)()
@@ -1127,8 +1201,8 @@ class DeviceFields:
     def expand(self, ds: "Dataset", col_offset: int = 0, stream=None) -> None:
         """cloudsc_fields_expand: fill every input member this set holds (plude included) from the
         dataset's template on the device.  Asynchronous on `stream` (None = the default stream).
-        (A tend_planes set: its separate arrays, self.separate -- the expansion has no packed form; pack
-        tendency_tmp_* afterwards.)"""
+        (A tend_planes set: its separate arrays, self.separate -- pack tendency_tmp_* afterwards, or fill the buffers
+        in place with expand_fields_tendbuf.)"""
         if ds.klev != self.klev:
             raise ValueError("expand: the dataset's klev is not this set's")
         keep: list = []

@@ -200,6 +200,41 @@ struct CmpItem {
   __device__ __forceinline__ void left(const Args&, int m, bool touched) { cmp_flush(part + m, acc, touched); }
 };
 
+// The same with the tendency members of either side in packed buffers (cloudsc_fields_compare_tendbuf,
+// cloudsc_fields_validate_tendbuf): the block strides come from the table, everything else is CmpItem's --
+// the key and the rows stay the member's own.
+struct CmpTendArgs : CmpArgs {
+  long long abrows[kFsMaxEntries], bbrows[kFsMaxEntries];   // rows between consecutive blocks of a and b
+};
+template <int AB, int BB, bool REF>
+struct CmpTendItem {
+  using Args = CmpTendArgs;
+  using A = typename CmpReal<AB>::type;
+  using B = typename std::conditional<REF, W8Ref, typename CmpReal<BB>::type>::type;
+  CmpRec acc = cmp_neutral();
+  CmpRec* part;   // this workgroup's
+  __device__ CmpTendItem(const Args& a) : part(a.part + (size_t)blockIdx.x * a.n) {}
+  __device__ __forceinline__ void item(const Args& a, int m, unsigned g, unsigned long long chunk) {
+    const unsigned anp = (unsigned)a.anp;
+    const FsPos ap = fs_pos(g, anp);
+    const FsRows r = fs_rows(a, m, chunk);
+    const size_t ao = fs_offset_strided(ap, anp, r, (size_t)a.abrows[m]);
+    size_t bo, bs;
+    if constexpr (REF) {
+      bs = (size_t)a.klon;
+      bo = fs_wrapped(g, a.col_offset, a.klon, r);
+    } else {
+      const unsigned bnp = (unsigned)a.bnp;
+      bs = bnp;
+      bo = fs_offset_strided(fs_pos(g, bnp), bnp, r, (size_t)a.bbrows[m]);
+    }
+    const unsigned long long key0 = (unsigned long long)g * r.rows + r.row0;
+    if (!REF && (a.int_mask >> m & 1)) cmp_rows<WInt, WInt>(a.e[m].a, a.e[m].b, ao, bo, anp, bs, r.nrows, key0, acc);
+    else cmp_rows<A, B>(a.e[m].a, a.e[m].b, ao, bo, anp, bs, r.nrows, key0, acc);
+  }
+  __device__ __forceinline__ void left(const Args&, int m, bool touched) { cmp_flush(part + m, acc, touched); }
+};
+
 // one wave per member: the partials of the member in workgroup order (lane l takes workgroups l, l + 64, ...,
 // then the lanes combine in a fixed tree)
 __global__ void __launch_bounds__(64) fields_compare_combine_kernel(const CmpRec* __restrict__ part, int nwg, int n,
@@ -240,6 +275,26 @@ struct ExpItem {
   __device__ __forceinline__ void left(const Args&, int, bool) {}
 };
 
+// The same writing the tendency members straight into their planes of a packed buffer
+// (cloudsc_fields_expand_tendbuf): the destination's block strides come from the table.
+struct ExpTendArgs : ExpArgs {
+  long long bbrows[kFsMaxEntries];   // rows between consecutive blocks of the destination
+};
+template <typename D>
+struct ExpTendItem {
+  using Args = ExpTendArgs;
+  __device__ ExpTendItem(const Args&) {}
+  __device__ __forceinline__ void item(const Args& a, int m, unsigned g, unsigned long long chunk) {
+    const unsigned np = (unsigned)a.bnp;
+    const FsPos p = fs_pos(g, np);
+    const FsRows r = fs_rows(a, m, chunk);
+    const size_t so = fs_wrapped(g, a.col_offset, a.klon, r), doff = fs_offset_strided(p, np, r, (size_t)a.bbrows[m]);
+    if (a.int_mask >> m & 1) exp_rows<int, int>(a.e[m].a, a.e[m].b, so, doff, (size_t)a.klon, np, r.nrows);
+    else exp_rows<double, D>(a.e[m].a, a.e[m].b, so, doff, (size_t)a.klon, np, r.nrows);
+  }
+  __device__ __forceinline__ void left(const Args&, int, bool) {}
+};
+
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
@@ -259,28 +314,32 @@ void diff_from(cloudsc_field_diff_t* d, const CmpRec& r, long long rows, int ngp
 }
 
 // the columns of block ab of set a of one entry, on the host: the kernel's index arithmetic in plain loops
+// abrows / bbrows: the rows between consecutive blocks of the entry in a / b (its own rows, or a packed buffer's)
 template <typename A, typename B>
-void cmp_block_entry(const FsEntry<const void>& e, const CmpArgs& a, long long ab, CmpRec& acc) {
+void cmp_block_entry(const FsEntry<const void>& e, const CmpArgs& a, long long ab, long long abrows, long long bbrows,
+                     CmpRec& acc) {
   const long long anp = a.anp, bnp = a.bnp, g0 = ab * anp;
   const long long bsize = std::min<long long>(anp, a.ngptot - g0);
   const typename A::word* x = (const typename A::word*)e.a;
   const typename B::word* y = (const typename B::word*)e.b;
   for (long long row = 0; row < e.rows; row++) {
-    const typename A::word* xrow = x + (size_t)(ab * e.rows + row) * (size_t)anp;
+    const typename A::word* xrow = x + (size_t)(ab * abrows + row) * (size_t)anp;
     fs_runs(g0, bsize, bnp, [&](long long jl, long long bb, long long bj, long long run) {
-      const typename B::word* yrow = y + (size_t)(bb * e.rows + row) * (size_t)bnp + bj;
+      const typename B::word* yrow = y + (size_t)(bb * bbrows + row) * (size_t)bnp + bj;
       const unsigned long long g = (unsigned long long)(g0 + jl), rows = (unsigned long long)e.rows;
       for (long long i = 0; i < run; i++) cmp_elem<A, B>(xrow[jl + i], yrow[i], (g + i) * rows + row, acc);
     });
   }
 }
+// abrows / bbrows: per entry (NULL: every entry's own rows)
 template <int AB, int BB>
-void cmp_block(const CmpArgs& a, long long ab, CmpRec* acc) {
+void cmp_block(const CmpArgs& a, long long ab, const long long* abrows, const long long* bbrows, CmpRec* acc) {
   using A = typename CmpReal<AB>::type;
   using B = typename CmpReal<BB>::type;
   for (int m = 0; m < a.n; m++) {
-    if (a.int_mask >> m & 1) cmp_block_entry<WInt, WInt>(a.e[m], a, ab, acc[m]);
-    else cmp_block_entry<A, B>(a.e[m], a, ab, acc[m]);
+    const long long ar = abrows ? abrows[m] : a.e[m].rows, br = bbrows ? bbrows[m] : a.e[m].rows;
+    if (a.int_mask >> m & 1) cmp_block_entry<WInt, WInt>(a.e[m], a, ab, ar, br, acc[m]);
+    else cmp_block_entry<A, B>(a.e[m], a, ab, ar, br, acc[m]);
   }
 }
 
@@ -342,21 +401,22 @@ int ws_grow_stage(CmpWorkspace& ws, size_t bytes, bool host_too) {
 }
 
 // with ws.mu held: launch both kernels over the table, wait for `st`, leave the n records in ws.hres
-template <bool REF>
-int cmp_launch(CmpWorkspace& ws, int ncu, hipStream_t st, CmpArgs& a, bool a8, bool b8) {
+// Item: CmpItem over a CmpArgs, CmpTendItem over a CmpTendArgs
+template <bool REF, template <int, int, bool> class Item = CmpItem, typename Args = CmpArgs>
+int cmp_launch(CmpWorkspace& ws, int ncu, hipStream_t st, Args& a, bool a8, bool b8) {
   const unsigned grid = fs_grid(a, ncu, g_cmp_grid.load(std::memory_order_relaxed));
   int rc = ws_grow_part(ws, (size_t)grid * a.n);
   if (rc) return rc;
   a.part = ws.part;
   const dim3 g(grid), wg(kFsThreads);
   if (REF) {
-    if (a8) hipLaunchKernelGGL((fs_kernel<CmpItem<8, 8, true>>), g, wg, 0, st, a);
-    else hipLaunchKernelGGL((fs_kernel<CmpItem<4, 8, true>>), g, wg, 0, st, a);
+    if (a8) hipLaunchKernelGGL((fs_kernel<Item<8, 8, true>>), g, wg, 0, st, a);
+    else hipLaunchKernelGGL((fs_kernel<Item<4, 8, true>>), g, wg, 0, st, a);
   } else {
-    if (a8 && b8) hipLaunchKernelGGL((fs_kernel<CmpItem<8, 8, false>>), g, wg, 0, st, a);
-    else if (a8) hipLaunchKernelGGL((fs_kernel<CmpItem<8, 4, false>>), g, wg, 0, st, a);
-    else if (b8) hipLaunchKernelGGL((fs_kernel<CmpItem<4, 8, false>>), g, wg, 0, st, a);
-    else hipLaunchKernelGGL((fs_kernel<CmpItem<4, 4, false>>), g, wg, 0, st, a);
+    if (a8 && b8) hipLaunchKernelGGL((fs_kernel<Item<8, 8, false>>), g, wg, 0, st, a);
+    else if (a8) hipLaunchKernelGGL((fs_kernel<Item<8, 4, false>>), g, wg, 0, st, a);
+    else if (b8) hipLaunchKernelGGL((fs_kernel<Item<4, 8, false>>), g, wg, 0, st, a);
+    else hipLaunchKernelGGL((fs_kernel<Item<4, 4, false>>), g, wg, 0, st, a);
   }
   HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(fields_compare_combine_kernel, dim3(a.n), dim3(64), 0, st, (const CmpRec*)ws.part, (int)grid, a.n,
@@ -404,27 +464,127 @@ extern "C" int cloudsc_fields_compare(int device, void* stream, int ngptot, int 
   return CLOUDSC_OK;
 }
 
-extern "C" int cloudsc_cpu_fields_compare(int nthreads, int ngptot, int klev, int a_precision, int a_nproma,
-                                          const cloudsc_fields_t* fa, int b_precision, int b_nproma,
-                                          const cloudsc_fields_t* fb, cloudsc_field_diff_t* diff) {
+// the host comparison; a_planes / b_planes: the tendency members of that side are planes of a packed buffer
+// with so many planes per block (0: separate arrays)
+static int cpu_compare(int nthreads, int ngptot, int klev, int a_precision, int a_nproma, int a_planes,
+                       const cloudsc_fields_t* fa, int b_precision, int b_nproma, int b_planes,
+                       const cloudsc_fields_t* fb, cloudsc_field_diff_t* diff) {
   CmpArgs a = {};
   int member[kFsMaxEntries];
-  if (!diff) return CLOUDSC_EINVAL;
+  if (!diff || !fs_tend_planes_ok(a_planes) || !fs_tend_planes_ok(b_planes)) return CLOUDSC_EINVAL;
   int rc = fs_build(ngptot, klev, a_precision, a_nproma, fa, b_precision, b_nproma, fb, &a, member);
   if (rc) return rc;
+  long long abrows[kFsMaxEntries], bbrows[kFsMaxEntries];
+  for (int i = 0; i < a.n; i++) {
+    abrows[i] = fs_tend_brows(a, i, member[i], klev, a_planes);
+    bbrows[i] = fs_tend_brows(a, i, member[i], klev, b_planes);
+  }
   const bool a8 = precision_storage_bytes(a_precision) == 8, b8 = precision_storage_bytes(b_precision) == 8;
-  void (*block)(const CmpArgs&, long long, CmpRec*) =
+  void (*block)(const CmpArgs&, long long, const long long*, const long long*, CmpRec*) =
       a8 && b8 ? cmp_block<8, 8> : a8 ? cmp_block<8, 4> : b8 ? cmp_block<4, 8> : cmp_block<4, 4>;
   const long long nblocks = ((long long)ngptot + a_nproma - 1) / a_nproma;
   nthreads = fs_threads(nthreads, nblocks);
   std::vector<CmpRec> acc((size_t)nthreads * a.n, cmp_neutral());   // one record per (thread, member)
-  fs_run_blocks(nthreads, nblocks, [&](int t, long long b) { block(a, b, &acc[(size_t)t * a.n]); });
+  fs_run_blocks(nthreads, nblocks, [&](int t, long long b) { block(a, b, abrows, bbrows, &acc[(size_t)t * a.n]); });
   for (int m = 0; m < kNumFields; m++) diff_skipped(&diff[m]);
   for (int i = 0; i < a.n; i++) {
     CmpRec r = cmp_neutral();
     for (int t = 0; t < nthreads; t++) cmp_combine(r, acc[(size_t)t * a.n + i]);   // in thread order
     diff_from(&diff[member[i]], r, a.e[i].rows, ngptot);
   }
+  return CLOUDSC_OK;
+}
+
+extern "C" int cloudsc_cpu_fields_compare(int nthreads, int ngptot, int klev, int a_precision, int a_nproma,
+                                          const cloudsc_fields_t* fa, int b_precision, int b_nproma,
+                                          const cloudsc_fields_t* fb, cloudsc_field_diff_t* diff) {
+  return cpu_compare(nthreads, ngptot, klev, a_precision, a_nproma, 0, fa, b_precision, b_nproma, 0, fb, diff);
+}
+
+extern "C" int cloudsc_cpu_fields_compare_tendbuf(int nthreads, int ngptot, int klev, int a_precision, int a_nproma,
+                                                  int a_tend_planes, const cloudsc_fields_t* fa, int b_precision,
+                                                  int b_nproma, int b_tend_planes, const cloudsc_fields_t* fb,
+                                                  cloudsc_field_diff_t* diff) {
+  return cpu_compare(nthreads, ngptot, klev, a_precision, a_nproma, a_tend_planes, fa, b_precision, b_nproma,
+                     b_tend_planes, fb, diff);
+}
+
+extern "C" int cloudsc_fields_compare_tendbuf(int device, void* stream, int ngptot, int klev, int a_precision,
+                                              int a_nproma, int a_tend_planes, const cloudsc_fields_t* fa,
+                                              int b_precision, int b_nproma, int b_tend_planes,
+                                              const cloudsc_fields_t* fb, cloudsc_field_diff_t* diff) {
+  if (!fs_tend_planes_ok(a_tend_planes) || !fs_tend_planes_ok(b_tend_planes)) return CLOUDSC_EINVAL;
+  if (!a_tend_planes && !b_tend_planes)   // cloudsc_fields_compare itself
+    return cloudsc_fields_compare(device, stream, ngptot, klev, a_precision, a_nproma, fa, b_precision, b_nproma, fb,
+                                  diff);
+  CmpTendArgs a = {};
+  int member[kFsMaxEntries], ncu = 0;
+  if (!diff) return CLOUDSC_EINVAL;
+  int rc = fs_build(ngptot, klev, a_precision, a_nproma, fa, b_precision, b_nproma, fb,
+                    static_cast<FsTable<const void>*>(&a), member);
+  if (rc) return rc;
+  for (int i = 0; i < a.n; i++) {
+    a.abrows[i] = fs_tend_brows(a, i, member[i], klev, a_tend_planes);
+    a.bbrows[i] = fs_tend_brows(a, i, member[i], klev, b_tend_planes);
+  }
+  CmpWorkspace* ws = nullptr;
+  std::unique_lock<std::mutex> lock;
+  if ((rc = ws_open(device, lock, &ws, &ncu))) return rc;
+  rc = cmp_launch<false, CmpTendItem>(*ws, ncu, (hipStream_t)stream, a, precision_storage_bytes(a_precision) == 8,
+                                      precision_storage_bytes(b_precision) == 8);
+  if (rc) return rc;
+  for (int m = 0; m < kNumFields; m++) diff_skipped(&diff[m]);
+  for (int i = 0; i < a.n; i++) diff_from(&diff[member[i]], ws->hres[i], a.e[i].rows, ngptot);
+  return CLOUDSC_OK;
+}
+
+extern "C" int cloudsc_fields_validate_tendbuf(int device, void* stream, int precision, int ngptot, int nproma,
+                                               int klev, int tend_planes, int outputs, long long col_offset,
+                                               const cloudsc_fields_t* fields, const cloudsc_reference_t* ref,
+                                               cloudsc_stats_t* stats) {
+  if (!fs_tend_planes_ok(tend_planes)) return CLOUDSC_EINVAL;
+  if (outputs != CLOUDSC_OUTPUTS_ALL && outputs != CLOUDSC_OUTPUTS_PROGNOSTIC) return CLOUDSC_EINVAL;
+  if (!tend_planes && outputs == CLOUDSC_OUTPUTS_ALL)   // cloudsc_fields_validate itself
+    return cloudsc_fields_validate(device, stream, precision, ngptot, nproma, klev, col_offset, fields, ref, stats);
+  if (!fields || !ref || !stats || col_offset < 0) return CLOUDSC_EINVAL;
+  if (!precision_storage_bytes(precision)) return CLOUDSC_EINVAL;
+  if (ngptot < 1 || klev < 1 || nproma < 1 || nproma > kFsMaxNproma) return CLOUDSC_EINVAL;
+  if (ref->klon <= 0 || ref->klev != klev) return CLOUDSC_EINVAL;
+  int member[CLOUDSC_NVALID];
+  valid_members(member);
+  CmpTendArgs a = {};
+  int id_of[CLOUDSC_NVALID];               // the validated field of each entry
+  size_t off[CLOUDSC_NVALID], total = 0;   // bytes of each entry's reference array in the stage
+  for (int id = 0; id < CLOUDSC_NVALID; id++) {
+    const void* p = ((const void* const*)fields)[member[id]];
+    const bool optional = !output_selected(member[id], outputs);
+    if (optional && !p && !ref->field[id]) continue;   // skipped: absent on both sides
+    if (!p || !ref->field[id]) return CLOUDSC_EINVAL;
+    const int i = a.n;
+    fs_add<const void>(&a, member[id], klev, p, nullptr);   // b: the staged reference, below
+    a.abrows[i] = a.bbrows[i] = fs_tend_brows(a, i, member[id], klev, tend_planes);
+    id_of[i] = id;
+    off[i] = total;
+    total += (size_t)a.e[i].rows * ref->klon * sizeof(double);
+  }
+  fs_shape(&a, ngptot, nproma, 1);
+  a.klon = ref->klon;
+  a.col_offset = col_offset % ref->klon;
+  CmpWorkspace* ws = nullptr;
+  std::unique_lock<std::mutex> lock;
+  int ncu = 0, rc = ws_open(device, lock, &ws, &ncu);
+  if (rc || (rc = ws_grow_stage(*ws, total, false))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  for (int i = 0; i < a.n; i++) {
+    // on `stream`, ordered before the kernel that reads it
+    HIPCHK(hipMemcpyAsync(ws->stage + off[i], ref->field[id_of[i]], (size_t)a.e[i].rows * ref->klon * sizeof(double),
+                          hipMemcpyHostToDevice, st));
+    a.e[i].b = ws->stage + off[i];
+  }
+  rc = cmp_launch<true, CmpTendItem>(*ws, ncu, st, a, precision_storage_bytes(precision) == 8, true);
+  if (rc) return rc;
+  for (int id = 0; id < CLOUDSC_NVALID; id++) stats[id] = {__DBL_MAX__, -__DBL_MAX__, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int i = 0; i < a.n; i++) stats[id_of[i]] = rec_stats(ws->hres[i]);
   return CLOUDSC_OK;
 }
 
@@ -466,9 +626,10 @@ extern "C" int cloudsc_fields_validate(int device, void* stream, int precision, 
   return CLOUDSC_OK;
 }
 
-extern "C" int cloudsc_fields_expand(int device, void* stream, int precision, int ngptot, int nproma,
-                                     long long col_offset, const cloudsc_template_t* t,
-                                     const cloudsc_fields_t* fields) {
+// the expansion; tend_planes: the tendency members of `fields` are planes of a packed buffer with so many
+// planes per block (0: separate arrays)
+static int expand_impl(int device, void* stream, int precision, int ngptot, int nproma, int tend_planes,
+                       long long col_offset, const cloudsc_template_t* t, const cloudsc_fields_t* fields) {
   if (!t || !fields || col_offset < 0) return CLOUDSC_EINVAL;
   if (!precision_storage_bytes(precision)) return CLOUDSC_EINVAL;
   if (ngptot < 1 || nproma < 1 || nproma > kFsMaxNproma || t->klon <= 0 || t->klev < 1) return CLOUDSC_EINVAL;
@@ -476,7 +637,7 @@ extern "C" int cloudsc_fields_expand(int device, void* stream, int precision, in
 #define TEMPLATE_OF(n) tmpl[CLOUDSC_M_##n] = t->n;
   CLOUDSC_TEMPLATE_ORDER(TEMPLATE_OF)
 #undef TEMPLATE_OF
-  ExpArgs a = {};
+  ExpTendArgs a = {};
   const void* host[kFsMaxEntries];
   size_t off[kFsMaxEntries], bytes[kFsMaxEntries], total = 0;
   for (int m = 0; m < kNumFields; m++) {
@@ -485,7 +646,8 @@ extern "C" int cloudsc_fields_expand(int device, void* stream, int precision, in
     if (!d) continue;
     if (!tmpl[m]) return CLOUDSC_EINVAL;   // a member to fill that the template does not hold
     const int i = a.n;
-    fs_add(&a, m, t->klev, nullptr, d);   // a: the staged template, below
+    fs_add<void>(&a, m, t->klev, nullptr, d);   // a: the staged template, below
+    a.bbrows[i] = fs_tend_brows(a, i, m, t->klev, tend_planes);
     host[i] = tmpl[m];
     off[i] = total;
     bytes[i] = (size_t)a.e[i].rows * t->klon * (kFieldTable[m].is_int ? sizeof(int) : sizeof(double));
@@ -507,13 +669,33 @@ extern "C" int cloudsc_fields_expand(int device, void* stream, int precision, in
   hipStream_t st = (hipStream_t)stream;
   HIPCHK(hipMemcpyAsync(ws->stage, ws->hstage, total, hipMemcpyHostToDevice, st));
   const dim3 grid(fs_grid(a, ncu)), wg(kFsThreads);   // cloudsc_debug_set_compare_grid does not apply
-  if (precision_storage_bytes(precision) == 8) hipLaunchKernelGGL(fs_kernel<ExpItem<double>>, grid, wg, 0, st, a);
-  else hipLaunchKernelGGL(fs_kernel<ExpItem<float>>, grid, wg, 0, st, a);
+  const bool d8 = precision_storage_bytes(precision) == 8;
+  if (tend_planes) {
+    if (d8) hipLaunchKernelGGL(fs_kernel<ExpTendItem<double>>, grid, wg, 0, st, a);
+    else hipLaunchKernelGGL(fs_kernel<ExpTendItem<float>>, grid, wg, 0, st, a);
+  } else {
+    const ExpArgs& plain = a;
+    if (d8) hipLaunchKernelGGL(fs_kernel<ExpItem<double>>, grid, wg, 0, st, plain);
+    else hipLaunchKernelGGL(fs_kernel<ExpItem<float>>, grid, wg, 0, st, plain);
+  }
   HIPCHK(hipGetLastError());
   // the staged template is read until the kernel ends: the next call on this device waits for this event
   HIPCHK(hipEventRecord(ws->busy, st));
   ws->pending = true;
   return CLOUDSC_OK;
+}
+
+extern "C" int cloudsc_fields_expand(int device, void* stream, int precision, int ngptot, int nproma,
+                                     long long col_offset, const cloudsc_template_t* t,
+                                     const cloudsc_fields_t* fields) {
+  return expand_impl(device, stream, precision, ngptot, nproma, 0, col_offset, t, fields);
+}
+
+extern "C" int cloudsc_fields_expand_tendbuf(int device, void* stream, int precision, int ngptot, int nproma,
+                                             int tend_planes, long long col_offset, const cloudsc_template_t* t,
+                                             const cloudsc_fields_t* fields) {
+  if (tend_planes < CLOUDSC_TENDBUF_PLANES_MIN || tend_planes > CLOUDSC_TENDBUF_PLANES_MAX) return CLOUDSC_EINVAL;
+  return expand_impl(device, stream, precision, ngptot, nproma, tend_planes, col_offset, t, fields);
 }
 
 extern "C" int cloudsc_fields_compare_release(int device) {

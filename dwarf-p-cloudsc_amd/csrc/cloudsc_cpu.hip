@@ -130,7 +130,10 @@ int cpu_run(int nthreads, int ngptot, int nproma, int klev, const cloudsc_params
     std::vector<HostColumn<double>> col((size_t)nproma);
     int icalls = 0, igpc = 0;
     for (int b = next.fetch_add(1); b < nblocks; b = next.fetch_add(1)) {
-      if (outputs == CLOUDSC_OUTPUTS_PROGNOSTIC) {   // (no combined form with the tendency buffers)
+      if (outputs == CLOUDSC_OUTPUTS_PROGNOSTIC && tend_planes) {
+        if (aer) run_block<double, true, true, true>(c, A, b, col);
+        else run_block<double, false, true, true>(c, A, b, col);
+      } else if (outputs == CLOUDSC_OUTPUTS_PROGNOSTIC) {
         if (aer) run_block<double, true, false, true>(c, A, b, col);
         else run_block<double, false, false, true>(c, A, b, col);
       } else if (tend_planes) {
@@ -216,6 +219,23 @@ extern "C" int cloudsc_cpu_run_outputs(int nthreads, int precision, int outputs,
       return cpu_run<double>(nthreads, ngptot, nproma, klev, params, f, nullptr, nullptr, nullptr, nullptr, 0, outputs);
     case sizeof(float):
       return cpu_run<float>(nthreads, ngptot, nproma, klev, params, f, nullptr, nullptr, nullptr, nullptr, 0, outputs);
+    default: return CLOUDSC_EINVAL;
+  }
+}
+
+extern "C" int cloudsc_cpu_run_tendbuf_outputs(int nthreads, int precision, int outputs, int ngptot, int nproma,
+                                               int klev, int tend_planes, const cloudsc_params_t* params,
+                                               const cloudsc_fields_t* f) {
+  if (outputs != CLOUDSC_OUTPUTS_ALL && outputs != CLOUDSC_OUTPUTS_PROGNOSTIC) return CLOUDSC_EINVAL;
+  if (tend_planes < CLOUDSC_TENDBUF_PLANES_MIN || tend_planes > CLOUDSC_TENDBUF_PLANES_MAX) return CLOUDSC_EINVAL;
+  if (!cloudsc_impl::precision_computes_double(precision)) return CLOUDSC_EINVAL;   // as cloudsc_cpu_run_precision
+  switch (cloudsc_impl::precision_storage_bytes(precision)) {
+    case sizeof(double):
+      return cpu_run<double>(nthreads, ngptot, nproma, klev, params, f, nullptr, nullptr, nullptr, nullptr, tend_planes,
+                             outputs);
+    case sizeof(float):
+      return cpu_run<float>(nthreads, ngptot, nproma, klev, params, f, nullptr, nullptr, nullptr, nullptr, tend_planes,
+                            outputs);
     default: return CLOUDSC_EINVAL;
   }
 }

@@ -170,6 +170,12 @@ inline bool fs_is_tendency(int m) { return std::strncmp(kFieldTable[m].name, "te
 inline bool fs_tend_planes_ok(int planes) {
   return planes == 0 || (planes >= CLOUDSC_TENDBUF_PLANES_MIN && planes <= CLOUDSC_TENDBUF_PLANES_MAX);
 }
+// the rows between consecutive blocks of entry i of a table, for a side with `planes` planes (0: separate
+// arrays), member = the entry's cloudsc_fields_t position
+template <typename B>
+inline long long fs_tend_brows(const FsTable<B>& a, int i, int member, int klev, int planes) {
+  return planes && fs_is_tendency(member) ? (long long)planes * klev : a.e[i].rows;
+}
 // fs_build, then the block strides of the two sides; member: scratch of kFsMaxEntries ints
 inline int fs_build_tend(int ngptot, int klev, int a_precision, int a_nproma, int a_planes, const cloudsc_fields_t* fa,
                          int b_precision, int b_nproma, int b_planes, const cloudsc_fields_t* fb, FsTendTable* a) {
@@ -178,9 +184,8 @@ inline int fs_build_tend(int ngptot, int klev, int a_precision, int a_nproma, in
   const int rc = fs_build<void>(ngptot, klev, a_precision, a_nproma, fa, b_precision, b_nproma, fb, a, member);
   if (rc) return rc;
   for (int i = 0; i < a->n; i++) {
-    const bool tend = fs_is_tendency(member[i]);
-    a->abrows[i] = tend && a_planes ? (long long)a_planes * klev : a->e[i].rows;
-    a->bbrows[i] = tend && b_planes ? (long long)b_planes * klev : a->e[i].rows;
+    a->abrows[i] = fs_tend_brows(*a, i, member[i], klev, a_planes);
+    a->bbrows[i] = fs_tend_brows(*a, i, member[i], klev, b_planes);
   }
   return CLOUDSC_OK;
 }

@@ -274,7 +274,7 @@ int dispatch_bools(Fn&& f, bool c, Rest... rest) {
 
 // The support matrix: whether (variant kind, precision, fp32 exact-libm, form bits kFormTb and
 // kFormProg) has a kernel.  MIXED runs on the k-caching variants only; so do the tendency buffer
-// and the prognostic-outputs forms, which are not combined and which fp32 has with its default
+// and the prognostic-outputs forms, alone or combined, which fp32 has with its default
 // exp/pow only; the SCC variants are plain.  (The exact-libm bit means nothing outside fp32;
 // every k-caching kernel has its packed twin, so kFormPack is not asked about.)
 constexpr bool form_exists(int kind, int precision, bool exact_libm, unsigned form) {
@@ -283,7 +283,7 @@ constexpr bool form_exists(int kind, int precision, bool exact_libm, unsigned fo
   if (!kcaching && kind != CLOUDSC_VARIANT_SCC && kind != CLOUDSC_VARIANT_SCC_PRIVATE) return false;
   if (precision != CLOUDSC_FP64 && precision != CLOUDSC_FP32 && precision != CLOUDSC_MIXED) return false;
   if (precision == CLOUDSC_MIXED && !kcaching) return false;
-  if (tb || prog) return kcaching && !(tb && prog) && !(precision == CLOUDSC_FP32 && exact_libm);
+  if (tb || prog) return kcaching && !(precision == CLOUDSC_FP32 && exact_libm);
   return true;
 }
 // the precision code of a (compute, storage) pair
@@ -885,6 +885,23 @@ int cloudsc_gpu_run_outputs(int device, void* stream, int precision, int variant
   if (!f || !fields_complete(f, outputs) || (kind == CLOUDSC_VARIANT_KSEG && !scratch)) return CLOUDSC_EINVAL;
   return gpu_run_impl(device, stream, precision, variant, ngptot, nproma, klev, f, scratch, nullptr, nullptr, nullptr,
                       nullptr, 0, outputs);
+}
+
+int cloudsc_gpu_run_tendbuf_outputs(int device, void* stream, int precision, int variant, int outputs, int ngptot,
+                                    int nproma, int klev, int tend_planes, const cloudsc_fields_t* f, void* scratch) {
+  if (outputs != CLOUDSC_OUTPUTS_ALL && outputs != CLOUDSC_OUTPUTS_PROGNOSTIC) return CLOUDSC_EINVAL;
+  if (outputs == CLOUDSC_OUTPUTS_ALL)   // cloudsc_gpu_run_tendbuf itself
+    return cloudsc_gpu_run_tendbuf(device, stream, precision, variant, ngptot, nproma, klev, tend_planes, f, scratch);
+  // every argument rule first, the device's among them last: no HIP call before an argument error
+  if (tend_planes < CLOUDSC_TENDBUF_PLANES_MIN || tend_planes > CLOUDSC_TENDBUF_PLANES_MAX) return CLOUDSC_EINVAL;
+  if (variant & ~0xff) return CLOUDSC_EINVAL;   // no option bits (so no fp32 exact-libm)
+  const int kind = variant_kind(variant);
+  const int rc = validate_shape_args(precision, kind, ngptot, nproma, klev);
+  if (rc) return rc;
+  if (!form_exists(kind, precision, /*exact_libm=*/false, kFormTb | kFormProg)) return CLOUDSC_EINVAL;   // no SCC form
+  if (!f || !fields_complete(f, outputs) || (kind == CLOUDSC_VARIANT_KSEG && !scratch)) return CLOUDSC_EINVAL;
+  return gpu_run_impl(device, stream, precision, variant, ngptot, nproma, klev, f, scratch, nullptr, nullptr, nullptr,
+                      nullptr, tend_planes, outputs);
 }
 
 int cloudsc_gpu_check(int device, void* stream, int variant, void* scratch) {

@@ -49,6 +49,7 @@
 #include <unistd.h>
 
 #include "cloudsc_amd.h"
+#include "cloudsc_fields.def"
 #include "cloudsc_io.h"
 
 #define ZHPM 12482329.0   /* HPM flop count for 100 columns (cloudsc_driver.c:101) */
@@ -57,8 +58,9 @@
 typedef struct {
   int numomp, ngptot, nproma, ngpus, precision, variant, reps, warmup;
   int transfer, chunk_blocks, nstreams, exact_libm;
-  int fields_caller;              /* --fields caller | tendbuf: caller-owned field sets instead of a state */
+  int fields_caller;              /* --fields caller | tendbuf | tendbuf-inplace (1 | 2 | 3): caller-owned field sets */
   int tend_planes;                /* --fields tendbuf: planes per block of the two tendency buffers (0: not tendbuf) */
+  int outputs, outputs_given;     /* --outputs all|prognostic: CLOUDSC_OUTPUTS_* */
   int place;                      /* placement search: 1 on, 0 off, -1 auto (on when reps > 1) */
   int narrow_pack;                /* NPROMA <= 32 packed into full waves: 1 on, 0 off, -1 the library's default */
   double energy_s;                /* --energy: seconds of back-to-back launches sampled for board power */
@@ -72,6 +74,8 @@ typedef struct {
   int libm_bit;                   /* CLOUDSC_FP32_EXACT_LIBM or 0 */
   int caller, place_on, aerosols; /* --fields caller; its placement search; aerosol inputs allocated */
   int tend_planes;                /* --fields tendbuf: the step runs on two packed tendency buffers of that many planes */
+  int inplace;                    /* --fields tendbuf-inplace: fill, step and validation on the buffers themselves */
+  int outputs;                    /* --outputs: CLOUDSC_OUTPUTS_* */
   double energy_s;
   long long col_offset;
   const cloudsc_template_t *tmpl;
@@ -88,6 +92,7 @@ typedef struct {
   double board_w, energy_ms_per_step;   /* mean board power over the energy window, and its time per launch */
   int power_samples, energy_steps;
   cloudsc_stats_t stats[CLOUDSC_NVALID];
+  int skipped[CLOUDSC_NVALID];    /* --outputs: validated fields the set does not hold (no row, not gated) */
 } shard_t;
 
 static const char *variant_name(int v) {
@@ -137,7 +142,12 @@ static void usage(const char *prog) {
           "  --fields tendbuf      caller, with the tendencies in the reference Fortran drivers' two packed\n"
           "                        buffers: tendency_tmp_* packed into a BUFFER_TMP, cloudsc_gpu_run_tendbuf,\n"
           "                        BUFFER_LOC unpacked before the validation (kseg and kcache only)\n"
-          "  --tend-planes N       --fields tendbuf: planes per block of the two buffers, 8..64 (default 8)\n"
+          "  --fields tendbuf-inplace  tendbuf without the two conversions: cloudsc_fields_expand_tendbuf,\n"
+          "                        cloudsc_gpu_run_tendbuf_outputs, cloudsc_fields_validate_tendbuf on BUFFER_LOC (the\n"
+          "                        separate tendency arrays cloudsc_fields_alloc makes are never read or written)\n"
+          "  --tend-planes N       --fields tendbuf[-inplace]: planes per block of the two buffers, 8..64 (default 8)\n"
+          "  --outputs all|prognostic  --fields caller|tendbuf|tendbuf-inplace: prognostic = a step without the ten\n"
+          "                        diagnostic fluxes, which are not allocated, validated or printed (kseg, kcache)\n"
           "  --transfer            host-buffer path: block-layout arrays in host memory,\n"
           "                        H2D -> kernel -> D2H per chunk, overlapped on streams\n"
           "                        (TOTAL includes the transfers, like cloudsc_driver.cu)\n"
@@ -207,6 +217,7 @@ static int parse(int argc, char **argv, options_t *o) {
       if (!strcmp(v, "state")) o->fields_caller = 0;
       else if (!strcmp(v, "caller")) o->fields_caller = 1;
       else if (!strcmp(v, "tendbuf")) o->fields_caller = 2;
+      else if (!strcmp(v, "tendbuf-inplace")) o->fields_caller = 3;
       else { fprintf(stderr, "bad --fields %s\n", v); return -1; }
     }
     else if (!strcmp(a, "--tend-planes")) {
@@ -216,6 +227,13 @@ static int parse(int argc, char **argv, options_t *o) {
         fprintf(stderr, "bad --tend-planes %s\n", v);
         return -1;
       }
+    }
+    else if (!strcmp(a, "--outputs")) {
+      NEEDV();
+      o->outputs_given = 1;
+      if (!strcmp(v, "all")) o->outputs = CLOUDSC_OUTPUTS_ALL;
+      else if (!strcmp(v, "prognostic")) o->outputs = CLOUDSC_OUTPUTS_PROGNOSTIC;
+      else { fprintf(stderr, "bad --outputs %s\n", v); return -1; }
     }
     else if (!strcmp(a, "--fp32-exact-libm")) o->exact_libm = 1;
     else if (!strcmp(a, "--chunk")) { NEEDV(); o->chunk_blocks = atoi(v); }
@@ -361,6 +379,12 @@ static void *hip_sym(const char *name) {
 
 /* one step of a --fields caller | tendbuf shard on the field set f (tendbuf: its tendencies in the buffers) */
 static int caller_step(const shard_t *s, int variant, int klev, const cloudsc_fields_t *f, void *ws) {
+  if (s->outputs != CLOUDSC_OUTPUTS_ALL || s->inplace)   /* --outputs prognostic, --fields tendbuf-inplace */
+    return s->tend_planes
+               ? cloudsc_gpu_run_tendbuf_outputs(s->device, NULL, s->precision, variant, s->outputs, s->ngptot,
+                                                 s->nproma, klev, s->tend_planes, f, ws)
+               : cloudsc_gpu_run_outputs(s->device, NULL, s->precision, variant, s->outputs, s->ngptot, s->nproma,
+                                         klev, f, ws);
   if (s->tend_planes)
     return cloudsc_gpu_run_tendbuf(s->device, NULL, s->precision, variant, s->ngptot, s->nproma, klev, s->tend_planes, f,
                                    ws);
@@ -379,17 +403,20 @@ static void shard_caller(shard_t *s) {
   void *ws = NULL;
   /* --fields tendbuf: g is f with the eight tendency members bound to the two buffers; tmp_* / loc_* hold
    * the tendency_tmp_* / tendency_loc_* members alone, of the separate arrays (sep) and of the buffers (buf) */
-  const int tp = s->tend_planes;
+  const int tp = s->tend_planes, inplace = s->inplace, alloc_flags =
+      (s->place_on ? 0 : CLOUDSC_PLACE_NONE) | (s->aerosols ? CLOUDSC_ALLOC_AEROSOLS : 0);
   void *buf_tmp = NULL, *buf_loc = NULL;
   cloudsc_fields_t g, tmp_sep, tmp_buf, loc_sep, loc_buf;
   memset(&tmp_sep, 0, sizeof(tmp_sep)); memset(&tmp_buf, 0, sizeof(tmp_buf));
   memset(&loc_sep, 0, sizeof(loc_sep)); memset(&loc_buf, 0, sizeof(loc_buf));
   s->rc = set_device && dmalloc && dmemset && dfree ? CLOUDSC_OK : CLOUDSC_EHIP;
-  if (!s->rc)
-    s->rc = cloudsc_fields_alloc(s->device, s->precision, s->ngptot, s->nproma, klev,
-                                 (s->place_on ? 0 : CLOUDSC_PLACE_NONE) | (s->aerosols ? CLOUDSC_ALLOC_AEROSOLS : 0), &f,
-                                 &s->place);
-  if (!s->rc) s->rc = cloudsc_fields_expand(s->device, NULL, s->precision, s->ngptot, s->nproma, s->col_offset, s->tmpl, &f);
+  if (!s->rc && s->outputs != CLOUDSC_OUTPUTS_ALL)
+    s->rc = cloudsc_fields_alloc_outputs(s->device, s->precision, s->ngptot, s->nproma, klev, alloc_flags, s->outputs,
+                                         &f, &s->place);
+  else if (!s->rc)
+    s->rc = cloudsc_fields_alloc(s->device, s->precision, s->ngptot, s->nproma, klev, alloc_flags, &f, &s->place);
+  /* (tendbuf-inplace fills g below, once the tendency members are bound to the buffers) */
+  if (!s->rc && !inplace) s->rc = cloudsc_fields_expand(s->device, NULL, s->precision, s->ngptot, s->nproma, s->col_offset, s->tmpl, &f);
   const long long wsb = cloudsc_gpu_scratch_bytes(s->precision, s->variant, s->ngptot, s->nproma, klev);
   if (!s->rc && wsb < 0) s->rc = CLOUDSC_EINVAL;
   if (!s->rc && wsb > 0 && (set_device(s->device) || dmalloc(&ws, (size_t)wsb) || dmemset(ws, 0, 256))) s->rc = CLOUDSC_ENOMEM;
@@ -408,8 +435,12 @@ static void shard_caller(shard_t *s) {
     loc_sep.tendency_loc_q = f.tendency_loc_q; loc_sep.tendency_loc_cld = f.tendency_loc_cld;
     loc_buf.tendency_loc_t = g.tendency_loc_t; loc_buf.tendency_loc_a = g.tendency_loc_a;
     loc_buf.tendency_loc_q = g.tendency_loc_q; loc_buf.tendency_loc_cld = g.tendency_loc_cld;
+    /* tendbuf-inplace: every input from the template, tendency_tmp_* straight into their planes of BUFFER_TMP */
+    if (!s->rc && inplace)
+      s->rc = cloudsc_fields_expand_tendbuf(s->device, NULL, s->precision, s->ngptot, s->nproma, tp, s->col_offset,
+                                            s->tmpl, &g);
     /* pack the expanded tendency_tmp_* into BUFFER_TMP (stream order: before the first step) */
-    if (!s->rc)
+    if (!s->rc && !inplace)
       s->rc = cloudsc_fields_convert_tendbuf(s->device, NULL, s->ngptot, klev, s->precision, s->nproma, 0, &tmp_sep,
                                              s->precision, s->nproma, tp, &tmp_buf);
   }
@@ -435,10 +466,22 @@ static void shard_caller(shard_t *s) {
   }
   s->t_end = s->t_start + timed;
   pthread_barrier_wait(s->barrier);
-  if (!s->rc && tp)   /* unpack BUFFER_LOC into the separate tendency_loc_* arrays the validation reads */
+  if (!s->rc && tp && !inplace)   /* unpack BUFFER_LOC into the separate tendency_loc_* arrays the validation reads */
     s->rc = cloudsc_fields_convert_tendbuf(s->device, NULL, s->ngptot, klev, s->precision, s->nproma, tp, &loc_buf,
                                            s->precision, s->nproma, 0, &loc_sep);
-  if (!s->rc && s->ref)
+  if (!s->rc && s->ref && (inplace || s->outputs != CLOUDSC_OUTPUTS_ALL)) {
+    /* in place: BUFFER_LOC itself.  A prognostic set: the fields cloudsc_fields_alloc_outputs allocated -- the
+     * library's selection, read off the set: a validated member it left NULL has no reference array either */
+    int member[CLOUDSC_NVALID];
+#define VALID_MEMBER(n, N, k, d, i) CLOUDSC_IF_VALIDATED_##d(member[CLOUDSC_F_##N] = CLOUDSC_M_##n;)
+    CLOUDSC_FIELDS(VALID_MEMBER)
+#undef VALID_MEMBER
+    cloudsc_reference_t ref = *s->ref;
+    for (int id = 0; id < CLOUDSC_NVALID; id++)
+      if (!((const void *const *)&f)[member[id]]) { ref.field[id] = NULL; s->skipped[id] = 1; }
+    s->rc = cloudsc_fields_validate_tendbuf(s->device, NULL, s->precision, s->ngptot, s->nproma, klev, inplace ? tp : 0,
+                                            s->outputs, s->col_offset, inplace ? &g : &f, &ref, s->stats);
+  } else if (!s->rc && s->ref)
     s->rc = cloudsc_fields_validate(s->device, NULL, s->precision, s->ngptot, s->nproma, klev, s->col_offset, &f, s->ref,
                                     s->stats);
   if (s->rc) snprintf(s->err, sizeof(s->err), "%s", cloudsc_last_hip_error());
@@ -678,18 +721,30 @@ int main(int argc, char **argv) {
     return rc ? EXIT_FAILURE : EXIT_SUCCESS;
   }
 
-  if (o.tend_planes && o.fields_caller != 2) {
+  if (o.tend_planes && o.fields_caller != 2 && o.fields_caller != 3) {
     fprintf(stderr, "dwarf-cloudsc-amd: --tend-planes goes with --fields tendbuf\n");
     cloudsc_io_free(&ds);
     return EXIT_FAILURE;
   }
-  if (o.fields_caller == 2 && (o.transfer || (o.variant != CLOUDSC_VARIANT_KSEG && o.variant != CLOUDSC_VARIANT_KCACHE))) {
+  if (o.outputs_given && (!o.fields_caller || o.transfer || o.exact_libm ||
+                          (o.variant != CLOUDSC_VARIANT_KSEG && o.variant != CLOUDSC_VARIANT_KCACHE))) {
+    fprintf(stderr, "dwarf-cloudsc-amd: --outputs goes with --fields caller|tendbuf|tendbuf-inplace and --variant "
+                    "kseg|kcache (no --transfer, no --fp32-exact-libm)\n");
+    cloudsc_io_free(&ds);
+    return EXIT_FAILURE;
+  }
+  if (o.fields_caller == 3 && o.exact_libm) {
+    fprintf(stderr, "dwarf-cloudsc-amd: --fields tendbuf-inplace has no --fp32-exact-libm form\n");
+    cloudsc_io_free(&ds);
+    return EXIT_FAILURE;
+  }
+  if (o.fields_caller >= 2 && (o.transfer || (o.variant != CLOUDSC_VARIANT_KSEG && o.variant != CLOUDSC_VARIANT_KCACHE))) {
     fprintf(stderr, "dwarf-cloudsc-amd: --fields tendbuf runs --variant kseg|kcache on device fields (no --transfer, "
                     "no cpu, scc or scc-private)\n");
     cloudsc_io_free(&ds);
     return EXIT_FAILURE;
   }
-  if (o.fields_caller == 2 && !o.tend_planes) o.tend_planes = CLOUDSC_TENDBUF_PLANES_MIN;
+  if (o.fields_caller >= 2 && !o.tend_planes) o.tend_planes = CLOUDSC_TENDBUF_PLANES_MIN;
   if (o.fields_caller && (o.transfer || o.variant == VARIANT_CPU)) {
     fprintf(stderr, "dwarf-cloudsc-amd: --fields caller runs the GPU variants on device fields (no --transfer, no "
                     "--variant cpu)\n");
@@ -777,7 +832,9 @@ int main(int argc, char **argv) {
     s->libm_bit = o.exact_libm ? CLOUDSC_FP32_EXACT_LIBM : 0;
     s->energy_s = o.energy_s;
     s->caller = o.fields_caller; s->place_on = place;
-    s->tend_planes = o.fields_caller == 2 ? o.tend_planes : 0;
+    s->tend_planes = o.fields_caller >= 2 ? o.tend_planes : 0;
+    s->inplace = o.fields_caller == 3;
+    s->outputs = o.outputs;
     s->aerosols = ds.params.laericesed || ds.params.laericeauto;
     s->tmpl = &tmpl; s->params = &ds.params; s->ref = ds.has_reference ? &ref : NULL; s->barrier = &bar;
     s->kernel_ms = (float *)calloc((size_t)o.reps, sizeof(float));
@@ -888,6 +945,7 @@ int main(int argc, char **argv) {
     const int gate = o.precision == CLOUDSC_FP64 || o.tol_given;
     double worst = 0.0;
     for (int f = 0; f < CLOUDSC_NVALID; f++) {
+      if (sh[0].skipped[f]) continue;   /* --outputs prognostic: not allocated, not computed: no row */
       cloudsc_stats_t s = sh[0].stats[f];
       for (int d = 1; d < nused; d++) cloudsc_stats_combine(&s, &sh[d].stats[f]);   /* double-double sums */
       const int kind = cloudsc_io_ref_kind[f];

@@ -367,7 +367,9 @@ int cloudsc_cpu_run_tendbuf(int nthreads, int precision, int ngptot, int nproma,
  * and re-typing; with 0 and 0 it is cloudsc_fields_convert.  Planes no member
  * points at and padding lanes are never written.  CLOUDSC_EINVAL as
  * cloudsc_fields_convert, and for a non-zero *_tend_planes outside 8..64.
- * (Comparison, validation and expansion have no packed form: unpack first.) */
+ * (Comparison, validation and expansion read and write the buffers in place:
+ * cloudsc_fields_compare_tendbuf, cloudsc_fields_validate_tendbuf and
+ * cloudsc_fields_expand_tendbuf, below.) */
 int cloudsc_fields_convert_tendbuf(int device, void *stream, int ngptot, int klev,
                                    int src_precision, int src_nproma, int src_tend_planes,
                                    const cloudsc_fields_t *src,
@@ -410,9 +412,11 @@ int cloudsc_cpu_fields_convert_tendbuf(int nthreads, int ngptot, int klev,
  * and the option bit CLOUDSC_FP32_EXACT_LIBM have no such form: CLOUDSC_EINVAL,
  * like an unknown `outputs` value and every argument error of cloudsc_gpu_run
  * -- with PROGNOSTIC all of these are checked before the first HIP call.
- * There is no combined form with the tendency buffers.
- * cloudsc_fields_validate needs all 21 members: to check a prognostic set use
- * cloudsc_fields_compare, which skips members that are NULL in both sets. */
+ * The combined form with the tendency buffers is cloudsc_gpu_run_tendbuf_outputs.
+ * cloudsc_fields_validate needs all 21 members: a prognostic set is validated
+ * with cloudsc_fields_validate_tendbuf (tend_planes 0 for separate arrays), or
+ * compared with cloudsc_fields_compare, which skips members that are NULL in
+ * both sets. */
 int cloudsc_gpu_run_outputs(int device, void *stream, int precision, int variant, int outputs,
                             int ngptot, int nproma, int klev,
                             const cloudsc_fields_t *device_fields, void *scratch);
@@ -424,6 +428,34 @@ int cloudsc_gpu_run_outputs(int device, void *stream, int precision, int variant
  * value and every argument error of cloudsc_cpu_run_precision.  Needs no GPU. */
 int cloudsc_cpu_run_outputs(int nthreads, int precision, int outputs, int ngptot, int nproma, int klev,
                             const cloudsc_params_t *params, const cloudsc_fields_t *host_fields);
+
+/* cloudsc_gpu_run_tendbuf with an output selection: the prognostic step on the
+ * packed tendency buffers, for a host model that only advances its state and
+ * keeps its tendencies in BUFFER_TMP / BUFFER_LOC.  With CLOUDSC_OUTPUTS_ALL it
+ * IS cloudsc_gpu_run_tendbuf: the same kernels, the same rules.  With
+ * CLOUDSC_OUTPUTS_PROGNOSTIC the contract of cloudsc_gpu_run_outputs applies --
+ * the ten diagnostic members may be NULL, a non-NULL one keeps every byte, the
+ * eleven kept outputs have the bits of cloudsc_gpu_run on the same values in
+ * separate arrays -- together with the touch rule of the buffers: only the
+ * planes the members point at, only the lanes of real columns.  All eight
+ * tendency planes are still read and written: the tendencies are prognostic.
+ * KCACHE and KSEG, every precision, with and without aerosols, packed and
+ * unpacked; one KSEG workspace serves every form in any order.
+ * CLOUDSC_EINVAL: an unknown `outputs` value, tend_planes outside 8..64,
+ * CLOUDSC_VARIANT_SCC, CLOUDSC_VARIANT_SCC_PRIVATE, the option bit
+ * CLOUDSC_FP32_EXACT_LIBM, a NULL kept member and every argument error of
+ * cloudsc_gpu_run; all checked before the first HIP call. */
+int cloudsc_gpu_run_tendbuf_outputs(int device, void *stream, int precision, int variant, int outputs,
+                                    int ngptot, int nproma, int klev, int tend_planes,
+                                    const cloudsc_fields_t *device_fields, void *scratch);
+
+/* The host twin, on HOST memory through the same phase functions: the bits of
+ * cloudsc_cpu_run_precision on separate arrays for the eleven kept outputs.
+ * CLOUDSC_EINVAL: an unknown `outputs` value, tend_planes outside 8..64 and
+ * every argument error of cloudsc_cpu_run_precision.  Needs no GPU. */
+int cloudsc_cpu_run_tendbuf_outputs(int nthreads, int precision, int outputs, int ngptot, int nproma, int klev,
+                                    int tend_planes, const cloudsc_params_t *params,
+                                    const cloudsc_fields_t *host_fields);
 
 /* cloudsc_fields_alloc for an output selection.  With CLOUDSC_OUTPUTS_ALL it is
  * cloudsc_fields_alloc.  With CLOUDSC_OUTPUTS_PROGNOSTIC the ten diagnostic
@@ -861,10 +893,31 @@ int cloudsc_cpu_fields_compare(int nthreads, int ngptot, int klev,
                                int b_precision, int b_nproma, const cloudsc_fields_t *b,
                                cloudsc_field_diff_t *diff);
 
+/* cloudsc_fields_compare with the eight tendency members of either side in a
+ * packed tendency buffer (above, "Packed tendency buffers"): where
+ * a_tend_planes (b_tend_planes) is non-zero, the tendency members of a (b) have
+ * the block stride *_tend_planes * klev * *_nproma elements; 0 means separate
+ * arrays, and 0 and 0 is cloudsc_fields_compare.  Nothing is written; padding
+ * lanes and planes no member points at are never read.  diff[] is as there:
+ * compared, first_column and first_row count in the member's own rows, and
+ * min, max, the counts and the first mismatch do not depend on the grid or on
+ * either blocking.  CLOUDSC_EINVAL as cloudsc_fields_compare, and for a
+ * non-zero *_tend_planes outside 8..64; checked before the first HIP call. */
+int cloudsc_fields_compare_tendbuf(int device, void *stream, int ngptot, int klev,
+                                   int a_precision, int a_nproma, int a_tend_planes, const cloudsc_fields_t *a,
+                                   int b_precision, int b_nproma, int b_tend_planes, const cloudsc_fields_t *b,
+                                   cloudsc_field_diff_t *diff);
+
+/* The same on HOST arrays, as cloudsc_cpu_fields_compare.  Needs no GPU. */
+int cloudsc_cpu_fields_compare_tendbuf(int nthreads, int ngptot, int klev,
+                                       int a_precision, int a_nproma, int a_tend_planes, const cloudsc_fields_t *a,
+                                       int b_precision, int b_nproma, int b_tend_planes, const cloudsc_fields_t *b,
+                                       cloudsc_field_diff_t *diff);
+
 /* cloudsc_state_validate for a caller-owned set: the 21 validated members of
  * `fields` (all must be set: a set of CLOUDSC_OUTPUTS_PROGNOSTIC, whose ten
- * diagnostic fluxes are NULL, is checked with cloudsc_fields_compare instead,
- * which skips members that are NULL in both sets) against the KLON-column reference, read as
+ * diagnostic fluxes are NULL, is validated with cloudsc_fields_validate_tendbuf
+ * below) against the KLON-column reference, read as
  * ref[row][(col_offset + g) % klon] -- the comparison kernel with the
  * reference as its second operand.  The reference arrays are uploaded on
  * `stream`, ordered before the one launch; the call waits for that stream only
@@ -875,6 +928,23 @@ int cloudsc_cpu_fields_compare(int nthreads, int ngptot, int klev,
 int cloudsc_fields_validate(int device, void *stream, int precision, int ngptot, int nproma, int klev,
                             long long col_offset, const cloudsc_fields_t *fields,
                             const cloudsc_reference_t *ref, cloudsc_stats_t *stats);
+
+/* cloudsc_fields_validate reading the eight tendency members in place from
+ * packed tendency buffers (tend_planes planes per block, 8..64; 0: separate
+ * arrays), with an output selection.  With CLOUDSC_OUTPUTS_PROGNOSTIC each of
+ * the ten diagnostic members may be NULL together with its reference array;
+ * its stats[] record is then the "skipped" record of cloudsc_fields_compare,
+ * {DBL_MAX, -DBL_MAX, 0, ...}.  A diagnostic member that is non-NULL while its
+ * reference array is NULL, or the reverse, is CLOUDSC_EINVAL; one present on
+ * both sides is validated.  tend_planes 0 with CLOUDSC_OUTPUTS_ALL is
+ * cloudsc_fields_validate.  Nothing is written to the fields; padding lanes and
+ * planes no member points at are never read.  CLOUDSC_EINVAL also: an unknown
+ * `outputs` value, a non-zero tend_planes outside 8..64 and every argument
+ * error of cloudsc_fields_validate (checked before the first HIP call). */
+int cloudsc_fields_validate_tendbuf(int device, void *stream, int precision, int ngptot, int nproma, int klev,
+                                    int tend_planes, int outputs, long long col_offset,
+                                    const cloudsc_fields_t *fields, const cloudsc_reference_t *ref,
+                                    cloudsc_stats_t *stats);
 
 /* cloudsc_state_create's expansion for a caller-owned set: fills every
  * non-NULL INPUT member of `fields` (aerosol inputs and plude included; the
@@ -892,6 +962,16 @@ int cloudsc_fields_validate(int device, void *stream, int precision, int ngptot,
  * waits for this expansion's kernel, which still reads the staged template. */
 int cloudsc_fields_expand(int device, void *stream, int precision, int ngptot, int nproma,
                           long long col_offset, const cloudsc_template_t *tmpl, const cloudsc_fields_t *fields);
+
+/* cloudsc_fields_expand writing the tendency members (tendency_tmp_*; the
+ * tendency_loc_* are outputs and left alone) straight into their planes of a
+ * packed tendency buffer with tend_planes planes per block (8..64): only the
+ * planes the members point at and the lanes of real columns are written.  The
+ * same asynchrony and staging rules.  CLOUDSC_EINVAL: tend_planes outside 8..64
+ * and every argument error of cloudsc_fields_expand, before the first HIP call. */
+int cloudsc_fields_expand_tendbuf(int device, void *stream, int precision, int ngptot, int nproma,
+                                  int tend_planes, long long col_offset, const cloudsc_template_t *tmpl,
+                                  const cloudsc_fields_t *fields);
 
 /* Free the device's compare / validate / expand workspace (after waiting for a
  * pending expansion); the next such call allocates it again. */
