@@ -147,19 +147,35 @@ class Placement(C.Structure):
 PLACE_NONE = 1
 ALLOC_AEROSOLS = 2
 # output selection (cloudsc_gpu_run_outputs, cloudsc_cpu_run_outputs, cloudsc_fields_alloc_outputs)
-OUTPUTS_ALL, OUTPUTS_PROGNOSTIC = 0, 1
+# (a bit set: bit 0 = no diagnostic flux profiles, bit 2 = the four precipitation / enthalpy fluxes at the
+# surface only, valid with bit 0 alone; 2, 4 and every other value are unknown)
+OUTPUTS_ALL, OUTPUTS_PROGNOSTIC, OUTPUTS_SURFACE = 0, 1, 5
 # the ten diagnostic flux outputs OUTPUTS_PROGNOSTIC leaves out: the running sums of section 8
 DIAGNOSTIC_FLUX_FIELDS = ("pfsqlf", "pfsqif", "pfcqnng", "pfcqlng", "pfsqrf", "pfsqsf", "pfcqrng", "pfcqsng",
                           "pfsqltur", "pfsqitur")
+# the four flux outputs OUTPUTS_SURFACE keeps as surface fields [nblocks][nproma]: row klev of their profiles
+SURFACE_FLUX_FIELDS = ("pfplsl", "pfplsn", "pfhpsl", "pfhpsn")
 
 
 def selected_outputs(outputs: int = OUTPUTS_ALL) -> tuple:
     """The output members (plude included) an output selection writes, in member order: all 21, or the
-    eleven OUTPUTS_PROGNOSTIC keeps."""
-    if outputs not in (OUTPUTS_ALL, OUTPUTS_PROGNOSTIC):
+    eleven OUTPUTS_PROGNOSTIC and OUTPUTS_SURFACE keep (selected_field_shape has their shapes)."""
+    if outputs not in (OUTPUTS_ALL, OUTPUTS_PROGNOSTIC, OUTPUTS_SURFACE):
         raise ValueError("unknown output selection: %r" % (outputs,))
     return tuple(n for n in list(INOUT_FIELDS) + list(OUTPUT_FIELDS)
                  if outputs == OUTPUTS_ALL or n not in DIAGNOSTIC_FLUX_FIELDS)
+
+
+def selected_field_shape(name: str, klev: int, klon: int, outputs: int = OUTPUTS_ALL) -> tuple:
+    """The per-block shape of member `name` under an output selection: field_shape of its kind, except that
+    OUTPUTS_SURFACE holds the SURFACE_FLUX_FIELDS as surface fields, (klon,)."""
+    if outputs not in (OUTPUTS_ALL, OUTPUTS_PROGNOSTIC, OUTPUTS_SURFACE):
+        raise ValueError("unknown output selection: %r" % (outputs,))
+    if name not in ALL_FIELDS:
+        raise KeyError("no such field: %s" % name)
+    if outputs == OUTPUTS_SURFACE and name in SURFACE_FLUX_FIELDS:
+        return (klon,)
+    return field_shape(ALL_FIELDS[name], klev, klon)
 
 
 class LaunchGeometry(C.Structure):
@@ -521,6 +537,11 @@ def gpu_lib(path: Optional[str] = None):
             C.c_longlong, C.POINTER(Fields), C.POINTER(Reference), C.POINTER(Stats)]
         lib.cloudsc_fields_expand_tendbuf.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                                       C.c_longlong, C.POINTER(Template), C.POINTER(Fields)]
+    if hasattr(lib, "cloudsc_fields_compare_outputs"):   # (likewise: the forms for a set of one output selection)
+        lib.cloudsc_fields_convert_outputs.argtypes = [C.c_int, C.c_void_p] + [C.c_int] * 5 + [
+            C.POINTER(Fields), C.c_int, C.c_int, C.POINTER(Fields)]
+        lib.cloudsc_fields_compare_outputs.argtypes = lib.cloudsc_fields_convert_outputs.argtypes + \
+            [C.POINTER(FieldDiff)]
     lib.cloudsc_fields_diff_sizeof.restype = C.c_longlong
     lib.cloudsc_fields_compare_release.argtypes = [C.c_int]
     lib.cloudsc_debug_set_compare_grid.argtypes = [C.c_int]
@@ -612,6 +633,15 @@ def convert_fields(src: "Fields", dst: "Fields", ngptot: int, klev: int, src_pre
     Asynchronous: synchronise the stream before reading dst from the host."""
     check(gpu_lib().cloudsc_fields_convert(device, stream, ngptot, klev, src_precision, src_nproma, C.byref(src),
                                            dst_precision, dst_nproma, C.byref(dst)))
+
+
+def convert_fields_outputs(src: "Fields", dst: "Fields", ngptot: int, klev: int, outputs: int, src_precision: int,
+                           src_nproma: int, dst_precision: int, dst_nproma: int, device: int = 0,
+                           stream=None) -> None:
+    """cloudsc_fields_convert_outputs: convert_fields for two sets of one output selection -- with
+    OUTPUTS_SURFACE the SURFACE_FLUX_FIELDS members of both are surface fields."""
+    check(gpu_lib().cloudsc_fields_convert_outputs(device, stream, ngptot, klev, outputs, src_precision, src_nproma,
+                                                   C.byref(src), dst_precision, dst_nproma, C.byref(dst)))
 
 
 def cpu_convert_fields(src, dst, ngptot: Optional[int] = None, klev: Optional[int] = None,
@@ -738,6 +768,17 @@ def compare_fields(a: "Fields", b: "Fields", ngptot: int, klev: int, a_precision
     return _diffs_to_dict(diffs)
 
 
+def compare_fields_outputs(a: "Fields", b: "Fields", ngptot: int, klev: int, outputs: int, a_precision: int,
+                           a_nproma: int, b_precision: int, b_nproma: int, device: int = 0,
+                           stream=None) -> Dict[str, dict]:
+    """cloudsc_fields_compare_outputs: compare_fields for two sets of one output selection -- with
+    OUTPUTS_SURFACE the SURFACE_FLUX_FIELDS members of both are surface fields (one row)."""
+    diffs = (FieldDiff * len(ALL_FIELDS))()
+    check(gpu_lib().cloudsc_fields_compare_outputs(device, stream, ngptot, klev, outputs, a_precision, a_nproma,
+                                                   C.byref(a), b_precision, b_nproma, C.byref(b), diffs))
+    return _diffs_to_dict(diffs)
+
+
 def cpu_compare_fields(a: "HostState", b: "HostState", names=None, nthreads: int = 0) -> Dict[str, dict]:
     """cloudsc_cpu_fields_compare on two HostStates of the same ngptot and klev (any two blockings and
     precisions): the members in `names`, or every array both hold.  Same result shape as compare_fields."""
@@ -780,7 +821,8 @@ def validate_fields_tendbuf(f: "Fields", ref: "Reference", precision: int, ngpto
     """cloudsc_fields_validate_tendbuf: the validated members of DEVICE fields against the KLON-column
     reference, the tendency members read in place from packed buffers (tend_planes 0 = separate arrays).  With
     OUTPUTS_PROGNOSTIC the DIAGNOSTIC_FLUX_FIELDS members and their reference arrays may be None: their
-    records are the skipped record.  Returns the Stats array in VALIDATED order (waits for `stream`)."""
+    records are the skipped record; with OUTPUTS_SURFACE the SURFACE_FLUX_FIELDS members are surface fields
+    held against row klev of their reference profiles.  Returns the Stats array in VALIDATED order (waits for `stream`)."""
     stats = (Stats * len(VALIDATED))()
     check(gpu_lib().cloudsc_fields_validate_tendbuf(device, stream, precision, ngptot, nproma, klev, tend_planes,
                                                     outputs, col_offset, C.byref(f), C.byref(ref), stats))
@@ -1097,7 +1139,10 @@ class DeviceFields:
     them in the reference's plane order -- the set then runs with gpu_run_tendbuf; self.separate keeps the
     set with the tendency members as the separate arrays cloudsc_fields_alloc made.
     outputs=OUTPUTS_PROGNOSTIC: cloudsc_fields_alloc_outputs -- the DIAGNOSTIC_FLUX_FIELDS members stay None and
-    the placement search runs over the eleven other outputs; the set runs with gpu_run_outputs."""
+    the placement search runs over the eleven other outputs; the set runs with gpu_run_outputs.
+    outputs=OUTPUTS_SURFACE: likewise, and the SURFACE_FLUX_FIELDS members are surface fields [nblocks][nproma]
+    (selected_field_shape): upload, download, copy_from, convert_to and compare take them as such, between
+    sets of the same selection."""
 
     def __init__(self, ngptot: int, nproma: int, klev: int, precision: int = FP64, device: int = 0,
                  place: bool = True, aerosols: bool = False, tend_planes: int = 0, outputs: int = OUTPUTS_ALL):
@@ -1143,8 +1188,20 @@ class DeviceFields:
 
     def nbytes(self, name: str) -> int:
         es = 4 if name == "ktype" else np.dtype(storage_dtype(self.precision)).itemsize
-        return nblocks_of(self.ngptot, self.nproma) * int(np.prod(field_shape(ALL_FIELDS[name], self.klev,
-                                                                             self.nproma))) * es
+        return nblocks_of(self.ngptot, self.nproma) * int(np.prod(self.shape(name))) * es
+
+    def shape(self, name: str) -> tuple:
+        """The per-block shape of a member of this set (selected_field_shape of its output selection)."""
+        return selected_field_shape(name, self.klev, self.nproma, self._selection())
+
+    def _selection(self) -> int:
+        """This set's output selection (OUTPUTS_ALL for a set put together without one)."""
+        return getattr(self, "outputs", OUTPUTS_ALL)
+
+    def _same_selection(self, other: "DeviceFields", what: str) -> None:
+        if (self._selection() == OUTPUTS_SURFACE) != (other._selection() == OUTPUTS_SURFACE):
+            raise ValueError("%s: one set holds the surface fluxes as surface fields, the other as profiles "
+                             "(pass names without SURFACE_FLUX_FIELDS)" % what)
 
     def copy_from(self, src: "Fields", names) -> None:
         """Device-to-device copy of the named fields from another field set of
@@ -1173,8 +1230,14 @@ class DeviceFields:
         Asynchronous on `stream` (None = the default stream)."""
         if (other.ngptot, other.klev, other.device) != (self.ngptot, self.klev, self.device):
             raise ValueError("convert_to: ngptot, klev and device must be the same")
-        convert_fields(fields_subset(self.f, names, other.f), fields_subset(other.f, names, self.f), self.ngptot,
-                       self.klev, self.precision, self.nproma, other.precision, other.nproma, self.device, stream)
+        a, b = fields_subset(self.f, names, other.f), fields_subset(other.f, names, self.f)
+        if OUTPUTS_SURFACE in (self._selection(), other._selection()) and any(getattr(a, n) for n in SURFACE_FLUX_FIELDS):
+            self._same_selection(other, "convert_to")
+            convert_fields_outputs(a, b, self.ngptot, self.klev, OUTPUTS_SURFACE, self.precision, self.nproma,
+                                   other.precision, other.nproma, self.device, stream)
+            return
+        convert_fields(a, b, self.ngptot, self.klev, self.precision, self.nproma, other.precision, other.nproma,
+                       self.device, stream)
 
     def compare(self, other: "DeviceFields", names=None, stream=None) -> Dict[str, dict]:
         """cloudsc_fields_compare of this set against `other` as the reference (another blocking and / or
@@ -1182,9 +1245,13 @@ class DeviceFields:
         sets hold.  See compare_fields for the result."""
         if (other.ngptot, other.klev, other.device) != (self.ngptot, self.klev, self.device):
             raise ValueError("compare: ngptot, klev and device must be the same")
-        return compare_fields(fields_subset(self.f, names, other.f), fields_subset(other.f, names, self.f),
-                              self.ngptot, self.klev, self.precision, self.nproma, other.precision, other.nproma,
-                              self.device, stream)
+        a, b = fields_subset(self.f, names, other.f), fields_subset(other.f, names, self.f)
+        if OUTPUTS_SURFACE in (self._selection(), other._selection()) and any(getattr(a, n) for n in SURFACE_FLUX_FIELDS):
+            self._same_selection(other, "compare")
+            return compare_fields_outputs(a, b, self.ngptot, self.klev, OUTPUTS_SURFACE, self.precision, self.nproma,
+                                          other.precision, other.nproma, self.device, stream)
+        return compare_fields(a, b, self.ngptot, self.klev, self.precision, self.nproma, other.precision,
+                              other.nproma, self.device, stream)
 
     def validate(self, ds: "Dataset", col_offset: int = 0, stream=None) -> list:
         """cloudsc_fields_validate: the 21 validated fields against ds.reference on the device; the list
@@ -1216,7 +1283,7 @@ class DeviceFields:
         self.hip.hipDeviceSynchronize()
         dt = np.int32 if name == "ktype" else storage_dtype(self.precision)
         nb = nblocks_of(self.ngptot, self.nproma)
-        out = np.empty((nb,) + field_shape(ALL_FIELDS[name], self.klev, self.nproma), dtype=dt)
+        out = np.empty((nb,) + self.shape(name), dtype=dt)
         rc = self.hip.hipMemcpy(out.ctypes.data, getattr(self.f, name), out.nbytes, 2)
         if rc != 0:
             raise CloudscError("hipMemcpy %s failed (%d)" % (name, rc))

@@ -445,13 +445,14 @@ extern "C" int cloudsc_debug_set_compare_grid(int workgroups) {
   return CLOUDSC_OK;
 }
 
-extern "C" int cloudsc_fields_compare(int device, void* stream, int ngptot, int klev, int a_precision, int a_nproma,
-                                      const cloudsc_fields_t* fa, int b_precision, int b_nproma,
-                                      const cloudsc_fields_t* fb, cloudsc_field_diff_t* diff) {
+// outputs: the selection both sets were allocated for (the shape of the four surface flux members)
+static int compare_impl(int device, void* stream, int ngptot, int klev, int a_precision, int a_nproma,
+                        const cloudsc_fields_t* fa, int b_precision, int b_nproma, const cloudsc_fields_t* fb,
+                        int outputs, cloudsc_field_diff_t* diff) {
   CmpArgs a = {};
   int member[kFsMaxEntries], ncu = 0;
   if (!diff) return CLOUDSC_EINVAL;
-  int rc = fs_build(ngptot, klev, a_precision, a_nproma, fa, b_precision, b_nproma, fb, &a, member);
+  int rc = fs_build(ngptot, klev, a_precision, a_nproma, fa, b_precision, b_nproma, fb, &a, member, outputs);
   if (rc) return rc;
   CmpWorkspace* ws = nullptr;
   std::unique_lock<std::mutex> lock;
@@ -462,6 +463,25 @@ extern "C" int cloudsc_fields_compare(int device, void* stream, int ngptot, int 
   for (int m = 0; m < kNumFields; m++) diff_skipped(&diff[m]);
   for (int i = 0; i < a.n; i++) diff_from(&diff[member[i]], ws->hres[i], a.e[i].rows, ngptot);
   return CLOUDSC_OK;
+}
+
+extern "C" int cloudsc_fields_compare(int device, void* stream, int ngptot, int klev, int a_precision, int a_nproma,
+                                      const cloudsc_fields_t* fa, int b_precision, int b_nproma,
+                                      const cloudsc_fields_t* fb, cloudsc_field_diff_t* diff) {
+  return compare_impl(device, stream, ngptot, klev, a_precision, a_nproma, fa, b_precision, b_nproma, fb,
+                      CLOUDSC_OUTPUTS_ALL, diff);
+}
+
+extern "C" int cloudsc_fields_compare_outputs(int device, void* stream, int ngptot, int klev, int outputs,
+                                              int a_precision, int a_nproma, const cloudsc_fields_t* fa,
+                                              int b_precision, int b_nproma, const cloudsc_fields_t* fb,
+                                              cloudsc_field_diff_t* diff) {
+  if (!outputs_known(outputs)) return CLOUDSC_EINVAL;
+  if (!outputs_surface(outputs))   // cloudsc_fields_compare itself
+    return cloudsc_fields_compare(device, stream, ngptot, klev, a_precision, a_nproma, fa, b_precision, b_nproma, fb,
+                                  diff);
+  return compare_impl(device, stream, ngptot, klev, a_precision, a_nproma, fa, b_precision, b_nproma, fb, outputs,
+                      diff);
 }
 
 // the host comparison; a_planes / b_planes: the tendency members of that side are planes of a packed buffer
@@ -543,7 +563,7 @@ extern "C" int cloudsc_fields_validate_tendbuf(int device, void* stream, int pre
                                                const cloudsc_fields_t* fields, const cloudsc_reference_t* ref,
                                                cloudsc_stats_t* stats) {
   if (!fs_tend_planes_ok(tend_planes)) return CLOUDSC_EINVAL;
-  if (outputs != CLOUDSC_OUTPUTS_ALL && outputs != CLOUDSC_OUTPUTS_PROGNOSTIC) return CLOUDSC_EINVAL;
+  if (!outputs_known(outputs)) return CLOUDSC_EINVAL;
   if (!tend_planes && outputs == CLOUDSC_OUTPUTS_ALL)   // cloudsc_fields_validate itself
     return cloudsc_fields_validate(device, stream, precision, ngptot, nproma, klev, col_offset, fields, ref, stats);
   if (!fields || !ref || !stats || col_offset < 0) return CLOUDSC_EINVAL;
@@ -555,14 +575,17 @@ extern "C" int cloudsc_fields_validate_tendbuf(int device, void* stream, int pre
   CmpTendArgs a = {};
   int id_of[CLOUDSC_NVALID];               // the validated field of each entry
   size_t off[CLOUDSC_NVALID], total = 0;   // bytes of each entry's reference array in the stage
+  size_t ref_row0[CLOUDSC_NVALID];         // the first reference row of each entry
   for (int id = 0; id < CLOUDSC_NVALID; id++) {
     const void* p = ((const void* const*)fields)[member[id]];
     const bool optional = !output_selected(member[id], outputs);
     if (optional && !p && !ref->field[id]) continue;   // skipped: absent on both sides
     if (!p || !ref->field[id]) return CLOUDSC_EINVAL;
     const int i = a.n;
-    fs_add<const void>(&a, member[id], klev, p, nullptr);   // b: the staged reference, below
+    fs_add<const void>(&a, member[id], klev, p, nullptr, outputs);   // b: the staged reference, below
     a.abrows[i] = a.bbrows[i] = fs_tend_brows(a, i, member[id], klev, tend_planes);
+    // CLOUDSC_OUTPUTS_SURFACE: a surface flux member is one row, held against row klev of its reference profile
+    ref_row0[i] = outputs_surface(outputs) && is_surface_flux(member[id]) ? (size_t)klev : 0;
     id_of[i] = id;
     off[i] = total;
     total += (size_t)a.e[i].rows * ref->klon * sizeof(double);
@@ -577,8 +600,8 @@ extern "C" int cloudsc_fields_validate_tendbuf(int device, void* stream, int pre
   hipStream_t st = (hipStream_t)stream;
   for (int i = 0; i < a.n; i++) {
     // on `stream`, ordered before the kernel that reads it
-    HIPCHK(hipMemcpyAsync(ws->stage + off[i], ref->field[id_of[i]], (size_t)a.e[i].rows * ref->klon * sizeof(double),
-                          hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(ws->stage + off[i], ref->field[id_of[i]] + ref_row0[i] * (size_t)ref->klon,
+                          (size_t)a.e[i].rows * ref->klon * sizeof(double), hipMemcpyHostToDevice, st));
     a.e[i].b = ws->stage + off[i];
   }
   rc = cmp_launch<true, CmpTendItem>(*ws, ncu, st, a, precision_storage_bytes(precision) == 8, true);

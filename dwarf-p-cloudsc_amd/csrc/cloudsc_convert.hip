@@ -115,12 +115,13 @@ void conv_block(const ConvTable& a, long long db, const long long* sbrows, const
 
 }  // namespace
 
-extern "C" int cloudsc_fields_convert(int device, void* stream, int ngptot, int klev, int src_precision,
-                                      int src_nproma, const cloudsc_fields_t* src, int dst_precision,
-                                      int dst_nproma, const cloudsc_fields_t* dst) {
+// outputs: the selection both sets were allocated for (the shape of the four surface flux members)
+static int convert_impl(int device, void* stream, int ngptot, int klev, int src_precision, int src_nproma,
+                        const cloudsc_fields_t* src, int dst_precision, int dst_nproma, const cloudsc_fields_t* dst,
+                        int outputs) {
   ConvTable a = {};
   int ncu = 0;
-  int rc = fs_build(ngptot, klev, src_precision, src_nproma, src, dst_precision, dst_nproma, dst, &a);
+  int rc = fs_build(ngptot, klev, src_precision, src_nproma, src, dst_precision, dst_nproma, dst, &a, nullptr, outputs);
   if (rc || (rc = fs_device(device, &ncu))) return rc;
   HIPCHK(hipSetDevice(device));
   const dim3 grid(fs_grid(a, ncu)), wg(kFsThreads);
@@ -132,6 +133,24 @@ extern "C" int cloudsc_fields_convert(int device, void* stream, int ngptot, int 
   else hipLaunchKernelGGL((fs_kernel<ConvItem<4, 4>>), grid, wg, 0, st, a);
   HIPCHK(hipGetLastError());
   return CLOUDSC_OK;
+}
+
+extern "C" int cloudsc_fields_convert(int device, void* stream, int ngptot, int klev, int src_precision,
+                                      int src_nproma, const cloudsc_fields_t* src, int dst_precision,
+                                      int dst_nproma, const cloudsc_fields_t* dst) {
+  return convert_impl(device, stream, ngptot, klev, src_precision, src_nproma, src, dst_precision, dst_nproma, dst,
+                      CLOUDSC_OUTPUTS_ALL);
+}
+
+extern "C" int cloudsc_fields_convert_outputs(int device, void* stream, int ngptot, int klev, int outputs,
+                                              int src_precision, int src_nproma, const cloudsc_fields_t* src,
+                                              int dst_precision, int dst_nproma, const cloudsc_fields_t* dst) {
+  if (!outputs_known(outputs)) return CLOUDSC_EINVAL;
+  if (!outputs_surface(outputs))   // cloudsc_fields_convert itself
+    return cloudsc_fields_convert(device, stream, ngptot, klev, src_precision, src_nproma, src, dst_precision,
+                                  dst_nproma, dst);
+  return convert_impl(device, stream, ngptot, klev, src_precision, src_nproma, src, dst_precision, dst_nproma, dst,
+                      outputs);
 }
 
 extern "C" int cloudsc_cpu_fields_convert(int nthreads, int ngptot, int klev, int src_precision, int src_nproma,

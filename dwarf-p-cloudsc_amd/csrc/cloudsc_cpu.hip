@@ -39,8 +39,9 @@ struct HostColumn {
 
 // real: the compute type, S: the fields' element type (float under double = CLOUDSC_MIXED);
 // TB: the tendency members are planes of packed buffers and A is a KArgsTB (cloudsc_kcache.h);
-// PROG: the prognostic-outputs form, the ten diagnostic flux members of A never touched (flux_level)
-template <typename real, bool AER, bool TB, bool PROG = false, typename S>
+// PROG: the prognostic-outputs form, the ten diagnostic flux members of A never touched (flux_level);
+// SURF: the surface-fluxes form, the other four flux members surface fields written after the last level
+template <typename real, bool AER, bool TB, bool PROG = false, bool SURF = false, typename S>
 void run_block(const DevParams<real>& c, const KArgs<real, S>& A, int b, std::vector<HostColumn<real>>& col) {
   const int nproma = A.nproma, klev = A.klev;
   const int bsize = std::min(nproma, A.ngptot - b * nproma);
@@ -54,7 +55,7 @@ void run_block(const DevParams<real>& c, const KArgs<real, S>& A, int b, std::ve
     const unsigned lo = (unsigned)jl * (unsigned)sizeof(S);
     HostColumn<real>& h = col[jl];
     init_carry<real, PROG>(h.cs);
-    flux_top<PROG>(c, A, uh, lo);
+    flux_top<PROG, SURF>(c, A, uh, lo);
     h.cc = column_constants(c, A, u1, uh, lo);
     h.nb.paph_k = ldg(A.paph, uh, lo);
     h.nb.paph_n = ldg(A.paph, uh + (size_t)nproma, lo);
@@ -82,7 +83,7 @@ void run_block(const DevParams<real>& c, const KArgs<real, S>& A, int b, std::ve
       po.zcovptot_out = R(0.0);
       if (physics) physics_level(c, k, klev, ncldtop0, cur, h.nb, h.cc, ls, h.cs, po);
       store_level<TB>(A, u2, u3, k, klev, nproma, lo, physics, ls, po);
-      flux_level<PROG>(c, A, uh + (size_t)(k + 1) * nproma, lo, cur, ls, po, h.nb.paph_k, h.nb.paph_n, h.cs);
+      flux_level<PROG, SURF>(c, A, uh + (size_t)(k + 1) * nproma, lo, cur, ls, po, h.nb.paph_k, h.nb.paph_n, h.cs);
       h.cs.t_prev = ls.ztp1;
       h.cs.a_prev = ls.za;
       h.cs.pap_prev = cur.pap;
@@ -96,6 +97,8 @@ void run_block(const DevParams<real>& c, const KArgs<real, S>& A, int b, std::ve
     }
   }
   for (int jl = 0; jl < bsize; jl++) stg(A.prainfrac, u1, (unsigned)jl * (unsigned)sizeof(S), col[jl].cs.rainfrac);
+  if constexpr (SURF)
+    for (int jl = 0; jl < bsize; jl++) flux_surface(c, A, u1, (unsigned)jl * (unsigned)sizeof(S), col[jl].cs);
 }
 
 // the block loop over fields of element type S, computed in double
@@ -130,7 +133,13 @@ int cpu_run(int nthreads, int ngptot, int nproma, int klev, const cloudsc_params
     std::vector<HostColumn<double>> col((size_t)nproma);
     int icalls = 0, igpc = 0;
     for (int b = next.fetch_add(1); b < nblocks; b = next.fetch_add(1)) {
-      if (outputs == CLOUDSC_OUTPUTS_PROGNOSTIC && tend_planes) {
+      if (outputs == CLOUDSC_OUTPUTS_SURFACE && tend_planes) {
+        if (aer) run_block<double, true, true, true, true>(c, A, b, col);
+        else run_block<double, false, true, true, true>(c, A, b, col);
+      } else if (outputs == CLOUDSC_OUTPUTS_SURFACE) {
+        if (aer) run_block<double, true, false, true, true>(c, A, b, col);
+        else run_block<double, false, false, true, true>(c, A, b, col);
+      } else if (outputs == CLOUDSC_OUTPUTS_PROGNOSTIC && tend_planes) {
         if (aer) run_block<double, true, true, true>(c, A, b, col);
         else run_block<double, false, true, true>(c, A, b, col);
       } else if (outputs == CLOUDSC_OUTPUTS_PROGNOSTIC) {
@@ -212,7 +221,7 @@ extern "C" int cloudsc_cpu_run_tendbuf(int nthreads, int precision, int ngptot, 
 
 extern "C" int cloudsc_cpu_run_outputs(int nthreads, int precision, int outputs, int ngptot, int nproma, int klev,
                                        const cloudsc_params_t* params, const cloudsc_fields_t* f) {
-  if (outputs != CLOUDSC_OUTPUTS_ALL && outputs != CLOUDSC_OUTPUTS_PROGNOSTIC) return CLOUDSC_EINVAL;
+  if (!cloudsc_impl::outputs_known(outputs)) return CLOUDSC_EINVAL;
   if (!cloudsc_impl::precision_computes_double(precision)) return CLOUDSC_EINVAL;   // as cloudsc_cpu_run_precision
   switch (cloudsc_impl::precision_storage_bytes(precision)) {
     case sizeof(double):
@@ -226,7 +235,7 @@ extern "C" int cloudsc_cpu_run_outputs(int nthreads, int precision, int outputs,
 extern "C" int cloudsc_cpu_run_tendbuf_outputs(int nthreads, int precision, int outputs, int ngptot, int nproma,
                                                int klev, int tend_planes, const cloudsc_params_t* params,
                                                const cloudsc_fields_t* f) {
-  if (outputs != CLOUDSC_OUTPUTS_ALL && outputs != CLOUDSC_OUTPUTS_PROGNOSTIC) return CLOUDSC_EINVAL;
+  if (!cloudsc_impl::outputs_known(outputs)) return CLOUDSC_EINVAL;
   if (tend_planes < CLOUDSC_TENDBUF_PLANES_MIN || tend_planes > CLOUDSC_TENDBUF_PLANES_MAX) return CLOUDSC_EINVAL;
   if (!cloudsc_impl::precision_computes_double(precision)) return CLOUDSC_EINVAL;   // as cloudsc_cpu_run_precision
   switch (cloudsc_impl::precision_storage_bytes(precision)) {

@@ -123,10 +123,12 @@ __device__ __forceinline__ size_t fs_wrapped(unsigned g, long long col_offset, i
 // ---------------------------------------------------------------------------
 // host side; no HIP call up to fs_device
 // ---------------------------------------------------------------------------
-// entry a->n++ for cloudsc_fields_t member m
+// entry a->n++ for cloudsc_fields_t member m; outputs: the selection of the sets, which overrides the
+// inventory's kind for the four surface flux members (field_kind_of) -- here in the walker's table, not in
+// the inventory
 template <typename B>
-inline void fs_add(FsTable<B>* a, int m, int klev, const void* pa, B* pb) {
-  a->e[a->n] = {pa, pb, (long long)per_block_elems(kFieldTable[m].kind, 1, klev)};
+inline void fs_add(FsTable<B>* a, int m, int klev, const void* pa, B* pb, int outputs = CLOUDSC_OUTPUTS_ALL) {
+  a->e[a->n] = {pa, pb, (long long)per_block_elems(field_kind_of(m, outputs), 1, klev)};
   if (kFieldTable[m].is_int) a->int_mask |= 1ull << a->n;
   a->n++;
 }
@@ -142,7 +144,8 @@ inline void fs_shape(FsTable<B>* a, int ngptot, int anp, int bnp) {
 // written (convert) refuses a member that is the same array in both
 template <typename B>
 inline int fs_build(int ngptot, int klev, int a_precision, int a_nproma, const cloudsc_fields_t* fa, int b_precision,
-                    int b_nproma, const cloudsc_fields_t* fb, FsTable<B>* a, int* member = nullptr) {
+                    int b_nproma, const cloudsc_fields_t* fb, FsTable<B>* a, int* member = nullptr,
+                    int outputs = CLOUDSC_OUTPUTS_ALL) {
   if (!fa || !fb) return CLOUDSC_EINVAL;
   if (!precision_storage_bytes(a_precision) || !precision_storage_bytes(b_precision)) return CLOUDSC_EINVAL;
   if (ngptot < 1 || klev < 1 || a_nproma < 1 || b_nproma < 1) return CLOUDSC_EINVAL;
@@ -153,7 +156,7 @@ inline int fs_build(int ngptot, int klev, int a_precision, int a_nproma, const c
     if (!pa && !pb) continue;
     if (!pa || !pb || (!std::is_const<B>::value && pa == pb)) return CLOUDSC_EINVAL;
     if (member) member[a->n] = m;
-    fs_add(a, m, klev, pa, pb);
+    fs_add(a, m, klev, pa, pb, outputs);
   }
   if (!a->n) return CLOUDSC_EINVAL;
   fs_shape(a, ngptot, a_nproma, b_nproma);

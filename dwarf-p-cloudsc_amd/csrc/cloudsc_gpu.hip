@@ -173,6 +173,9 @@ __device__ __forceinline__ cptr<typename F::params> params_of(cptr<typename F::f
 //            argument is a KArgsTB, tend_planes directly behind the KArgs;
 //   F::prog  the prognostic-outputs form (CLOUDSC_OUTPUTS_PROGNOSTIC): the
 //            plain KArgs, whose ten diagnostic flux members are never read;
+//   F::surf  the surface-fluxes form (CLOUDSC_OUTPUTS_SURFACE): F::prog, and the
+//            members pfplsl, pfplsn, pfhpsl, pfhpsn point at [nblocks][nproma]
+//            surface fields, written once after the last level;
 //   F::pack  narrow blocks (NPROMA <= 32) packed into full waves: a workgroup
 //            is one wave that walks PackArgs::pack consecutive blocks.
 // A kernel has exactly the arguments its form needs: Pack is PackArgs for
@@ -272,17 +275,19 @@ int dispatch_bools(Fn&& f, bool c, Rest... rest) {
   return c ? dispatch_bools<Bs..., true>(f, rest...) : dispatch_bools<Bs..., false>(f, rest...);
 }
 
-// The support matrix: whether (variant kind, precision, fp32 exact-libm, form bits kFormTb and
-// kFormProg) has a kernel.  MIXED runs on the k-caching variants only; so do the tendency buffer
+// The support matrix: whether (variant kind, precision, fp32 exact-libm, form bits kFormTb,
+// kFormProg and kFormSurf) has a kernel.  MIXED runs on the k-caching variants only; so do the tendency buffer
 // and the prognostic-outputs forms, alone or combined, which fp32 has with its default
-// exp/pow only; the SCC variants are plain.  (The exact-libm bit means nothing outside fp32;
+// exp/pow only; the surface-fluxes form is a prognostic-outputs form (kFormSurf without kFormProg
+// does not exist); the SCC variants are plain.  (The exact-libm bit means nothing outside fp32;
 // every k-caching kernel has its packed twin, so kFormPack is not asked about.)
 constexpr bool form_exists(int kind, int precision, bool exact_libm, unsigned form) {
-  const bool tb = (form & kFormTb) != 0, prog = (form & kFormProg) != 0;
+  const bool tb = (form & kFormTb) != 0, prog = (form & kFormProg) != 0, surf = (form & kFormSurf) != 0;
   const bool kcaching = kind == CLOUDSC_VARIANT_KCACHE || kind == CLOUDSC_VARIANT_KSEG;
   if (!kcaching && kind != CLOUDSC_VARIANT_SCC && kind != CLOUDSC_VARIANT_SCC_PRIVATE) return false;
   if (precision != CLOUDSC_FP64 && precision != CLOUDSC_FP32 && precision != CLOUDSC_MIXED) return false;
   if (precision == CLOUDSC_MIXED && !kcaching) return false;
+  if (surf && !prog) return false;
   if (tb || prog) return kcaching && !(precision == CLOUDSC_FP32 && exact_libm);
   return true;
 }
@@ -297,7 +302,7 @@ constexpr int kPrecisionOf = !std::is_same<real, S>::value ? CLOUDSC_MIXED : siz
 template <typename real, typename S, bool FAST>
 constexpr bool kernel_kept(int kind, bool aer, unsigned form = 0u) {
 #ifdef CLOUDSC_ONLY_KSEG
-  if (kind != CLOUDSC_VARIANT_KSEG || aer || (form & (kFormTb | kFormProg)) || sizeof(real) != CLOUDSC_ONLY_KSEG ||
+  if (kind != CLOUDSC_VARIANT_KSEG || aer || (form & (kFormTb | kFormProg | kFormSurf)) || sizeof(real) != CLOUDSC_ONLY_KSEG ||
       sizeof(S) != CLOUDSC_ONLY_KSEG)
     return false;
 #endif
@@ -318,7 +323,7 @@ struct LaunchForm {
   using product = cfg<DefaultCfg<real>::waves, DefaultCfg<real>::pf, false>;
 };
 constexpr bool cfg_table_applies(int kind, unsigned form) {
-  return !(form & (kFormTb | kFormProg)) && (kind == CLOUDSC_VARIANT_KSEG || !(form & kFormPack));
+  return !(form & (kFormTb | kFormProg | kFormSurf)) && (kind == CLOUDSC_VARIANT_KSEG || !(form & kFormPack));
 }
 template <typename LF, bool TABLE, typename Fn>
 int with_cfg(Fn&& f) {
@@ -544,9 +549,10 @@ template <typename real, bool FAST, typename ST = real>
 int launch_v(hipStream_t st, int variant, const cloudsc_fields_t* f, int ngptot, int nproma, int klev,
              void* scratch, const void* plude_in, const ParamSet& ps, KsegEpoch* ep, const LaunchEvents* ev,
              int tend_planes, int outputs) {
-  // tend_planes != 0: the tendency buffer form; outputs == CLOUDSC_OUTPUTS_PROGNOSTIC: the prognostic-outputs form
-  const bool aer = ps.aer, tb = tend_planes != 0, prog = outputs == CLOUDSC_OUTPUTS_PROGNOSTIC;
-  if (!kernel_kept<real, ST, FAST>(variant, aer, (tb ? kFormTb : 0u) | (prog ? kFormProg : 0u))) return CLOUDSC_EINVAL;
+  // tend_planes != 0: the tendency buffer form; the selection's bits: the prognostic-outputs and surface-fluxes forms
+  const bool aer = ps.aer, tb = tend_planes != 0, prog = outputs_prognostic(outputs), surf = outputs_surface(outputs);
+  if (!kernel_kept<real, ST, FAST>(variant, aer, (tb ? kFormTb : 0u) | (prog ? kFormProg : 0u) | (surf ? kFormSurf : 0u)))
+    return CLOUDSC_EINVAL;
   KArgs<real, ST> a = make_kargs<real, ST>(
       f, ngptot, nproma, klev, (const DevParams<real>*)((const char*)ps.dev + (sizeof(real) == 8 ? 0 : kSpOffset)));
   if (plude_in) a.plude_in = (const ST*)plude_in;
@@ -563,14 +569,15 @@ int launch_v(hipStream_t st, int variant, const cloudsc_fields_t* f, int ngptot,
   // conditions become F's members here, and only kernels that exist are instantiated
   const auto with_form = [&](auto kind, auto&& go) {
     return dispatch_bools(
-        [&](auto AER, auto PACK, auto TB, auto PROG) {
-          constexpr unsigned form = (PACK ? kFormPack : 0u) | (TB ? kFormTb : 0u) | (PROG ? kFormProg : 0u);
+        [&](auto AER, auto PACK, auto TB, auto PROG, auto SURF) {
+          constexpr unsigned form =
+              (PACK ? kFormPack : 0u) | (TB ? kFormTb : 0u) | (PROG ? kFormProg : 0u) | (SURF ? kFormSurf : 0u);
           if constexpr (kernel_kept<real, ST, FAST>(kind, AER, form))
             return with_cfg<LaunchForm<real, ST, AER, FAST, form>, cfg_table_applies(kind, form)>(go);
           else
             return (int)CLOUDSC_EINVAL;
         },
-        aer, pack > 1, tb, prog);
+        aer, pack > 1, tb, prog, surf);
   };
   if (variant == CLOUDSC_VARIANT_KCACHE) {
     rc = with_form(std::integral_constant<int, CLOUDSC_VARIANT_KCACHE>{}, [&](auto form) {
@@ -783,6 +790,9 @@ int validate_run_args(int device, int precision, int variant, int ngptot, int np
 int gpu_run_impl(int device, void* stream, int precision, int variant, int ngptot, int nproma, int klev,
                  const cloudsc_fields_t* f, void* scratch, const void* plude_in, const ParamSet* ps,
                  KsegEpoch* ep, const LaunchEvents* lev, int tend_planes, int outputs) {
+  // unknown option bits are an argument error here, before they are stripped (validate_run_args below sees
+  // the variant's kind only): such a call must never launch
+  if (variant & ~(0xff | CLOUDSC_FP32_EXACT_LIBM)) return CLOUDSC_EINVAL;
   const bool exact_libm = (variant & CLOUDSC_FP32_EXACT_LIBM) != 0;
   variant = variant_kind(variant);
   int rc = validate_run_args(device, precision, variant, ngptot, nproma, klev);
@@ -873,7 +883,7 @@ int cloudsc_gpu_run_tendbuf(int device, void* stream, int precision, int variant
 
 int cloudsc_gpu_run_outputs(int device, void* stream, int precision, int variant, int outputs, int ngptot, int nproma,
                             int klev, const cloudsc_fields_t* f, void* scratch) {
-  if (outputs != CLOUDSC_OUTPUTS_ALL && outputs != CLOUDSC_OUTPUTS_PROGNOSTIC) return CLOUDSC_EINVAL;
+  if (!outputs_known(outputs)) return CLOUDSC_EINVAL;
   if (outputs == CLOUDSC_OUTPUTS_ALL)   // cloudsc_gpu_run itself
     return gpu_run_impl(device, stream, precision, variant, ngptot, nproma, klev, f, scratch, nullptr, nullptr);
   // every argument rule first, the device's among them last: no HIP call before an argument error
@@ -881,7 +891,8 @@ int cloudsc_gpu_run_outputs(int device, void* stream, int precision, int variant
   const int kind = variant_kind(variant);
   const int rc = validate_shape_args(precision, kind, ngptot, nproma, klev);
   if (rc) return rc;
-  if (!form_exists(kind, precision, /*exact_libm=*/false, kFormProg)) return CLOUDSC_EINVAL;   // no SCC form
+  const unsigned form = kFormProg | (outputs_surface(outputs) ? kFormSurf : 0u);
+  if (!form_exists(kind, precision, /*exact_libm=*/false, form)) return CLOUDSC_EINVAL;   // no SCC form
   if (!f || !fields_complete(f, outputs) || (kind == CLOUDSC_VARIANT_KSEG && !scratch)) return CLOUDSC_EINVAL;
   return gpu_run_impl(device, stream, precision, variant, ngptot, nproma, klev, f, scratch, nullptr, nullptr, nullptr,
                       nullptr, 0, outputs);
@@ -889,7 +900,7 @@ int cloudsc_gpu_run_outputs(int device, void* stream, int precision, int variant
 
 int cloudsc_gpu_run_tendbuf_outputs(int device, void* stream, int precision, int variant, int outputs, int ngptot,
                                     int nproma, int klev, int tend_planes, const cloudsc_fields_t* f, void* scratch) {
-  if (outputs != CLOUDSC_OUTPUTS_ALL && outputs != CLOUDSC_OUTPUTS_PROGNOSTIC) return CLOUDSC_EINVAL;
+  if (!outputs_known(outputs)) return CLOUDSC_EINVAL;
   if (outputs == CLOUDSC_OUTPUTS_ALL)   // cloudsc_gpu_run_tendbuf itself
     return cloudsc_gpu_run_tendbuf(device, stream, precision, variant, ngptot, nproma, klev, tend_planes, f, scratch);
   // every argument rule first, the device's among them last: no HIP call before an argument error
@@ -898,7 +909,8 @@ int cloudsc_gpu_run_tendbuf_outputs(int device, void* stream, int precision, int
   const int kind = variant_kind(variant);
   const int rc = validate_shape_args(precision, kind, ngptot, nproma, klev);
   if (rc) return rc;
-  if (!form_exists(kind, precision, /*exact_libm=*/false, kFormTb | kFormProg)) return CLOUDSC_EINVAL;   // no SCC form
+  const unsigned form = kFormTb | kFormProg | (outputs_surface(outputs) ? kFormSurf : 0u);
+  if (!form_exists(kind, precision, /*exact_libm=*/false, form)) return CLOUDSC_EINVAL;   // no SCC form
   if (!f || !fields_complete(f, outputs) || (kind == CLOUDSC_VARIANT_KSEG && !scratch)) return CLOUDSC_EINVAL;
   return gpu_run_impl(device, stream, precision, variant, ngptot, nproma, klev, f, scratch, nullptr, nullptr, nullptr,
                       nullptr, tend_planes, outputs);

@@ -79,9 +79,24 @@ int validate_run_args(int device, int precision, int variant, int ngptot, int np
 constexpr bool is_flux_diagnostic(int member) { return member >= CLOUDSC_M_pfsqlf && member <= CLOUDSC_M_pfsqitur; }
 static_assert(CLOUDSC_M_pfsqitur - CLOUDSC_M_pfsqlf + 1 == 10 && CLOUDSC_M_pfplsl == CLOUDSC_M_pfsqitur + 1,
               "the diagnostic flux members");
+// The output selections are bit sets (cloudsc_amd.h): the three known values, and their two bits
+constexpr bool outputs_known(int outputs) {
+  return outputs == CLOUDSC_OUTPUTS_ALL || outputs == CLOUDSC_OUTPUTS_PROGNOSTIC || outputs == CLOUDSC_OUTPUTS_SURFACE;
+}
+constexpr bool outputs_prognostic(int outputs) { return (outputs & CLOUDSC_OUTPUTS_PROGNOSTIC) != 0; }
+constexpr bool outputs_surface(int outputs) { return (outputs & CLOUDSC_OUTPUTS_SURFACE_BIT) != 0; }
+static_assert(CLOUDSC_OUTPUTS_SURFACE == (CLOUDSC_OUTPUTS_PROGNOSTIC | CLOUDSC_OUTPUTS_SURFACE_BIT), "the selection bits");
+// The four precipitation / enthalpy flux members (consecutive): half-level profiles, or, with
+// CLOUDSC_OUTPUTS_SURFACE, surface fields that hold the profiles' last row
+constexpr bool is_surface_flux(int member) { return member >= CLOUDSC_M_pfplsl && member <= CLOUDSC_M_pfhpsn; }
+static_assert(CLOUDSC_M_pfhpsn - CLOUDSC_M_pfplsl + 1 == 4, "the surface flux members");
+// the shape kind of member m under a selection: the inventory's, overridden for the four members above
+constexpr int field_kind_of(int member, int outputs) {
+  return outputs_surface(outputs) && is_surface_flux(member) ? (int)CLOUDSC_FK_SURFACE : kFieldTable[member].kind;
+}
 // whether an output selection (CLOUDSC_OUTPUTS_*) touches member m
 constexpr bool output_selected(int member, int outputs) {
-  return outputs != CLOUDSC_OUTPUTS_PROGNOSTIC || !is_flux_diagnostic(member);
+  return !outputs_prognostic(outputs) || !is_flux_diagnostic(member);
 }
 // every pointer the kernel reads or writes (aerosol inputs and, with CLOUDSC_OUTPUTS_PROGNOSTIC, the ten
 // diagnostic fluxes excepted) is set

@@ -67,9 +67,11 @@ struct KArgsTB : KArgs<real, store> {
 //   kFormPack  narrow blocks packed into full waves (PackArgs, below)
 //   kFormTb    the tendency buffer form (KArgsTB)
 //   kFormProg  the prognostic-outputs form (flux_level)
+//   kFormSurf  the surface-fluxes form (flux_surface): kFormProg, and pfplsl, pfplsn, pfhpsl, pfhpsn
+//              stored once, after the last level, as surface fields
 // The kernel entries, the bodies below and the host's launch path all take the
 // descriptor and read its members by name.
-enum : unsigned { kFormPack = 1u, kFormTb = 2u, kFormProg = 4u };
+enum : unsigned { kFormPack = 1u, kFormTb = 2u, kFormProg = 4u, kFormSurf = 8u };
 template <typename Real, typename Store, int WAVES, int PF, bool AER, bool LDSC, bool FAST, unsigned FORM = 0u>
 struct KForm {
   using real = Real;
@@ -77,6 +79,8 @@ struct KForm {
   static constexpr int waves = WAVES, pf = PF;
   static constexpr bool aer = AER, ldsc = LDSC, fast = FAST;
   static constexpr bool pack = (FORM & kFormPack) != 0, tb = (FORM & kFormTb) != 0, prog = (FORM & kFormProg) != 0;
+  static constexpr bool surf = (FORM & kFormSurf) != 0;
+  static_assert(!surf || prog, "the surface-fluxes form is a prognostic-outputs form");
   using fields = KArgs<real, store>;   // what the bodies read: the kernel arguments, or their base in the TB form
   using kargs = typename std::conditional<tb, KArgsTB<real, store>, fields>::type;   // the kernel's first argument
   using params = DevParamsT<real, fast>;                                              // the parameter block
@@ -1163,7 +1167,10 @@ CLOUDSC_HD void physics_level(const P& c, const int k, const int klev,
 // are never touched -- not initialised, not carried, not handed over between KSEG segments -- and
 // their members of the kernel arguments are never read (they may be NULL).  What stays is what
 // pfplsl, pfplsn, pfhpsl and pfhpsn need.  With PROG off the functions are the ones they were.
-template <bool PROG = false, typename real, typename P, typename CS, typename S, typename LO>
+// SURF (with PROG): the surface-fluxes form (CLOUDSC_OUTPUTS_SURFACE).  The four remaining profiles are
+// not stored per level either -- flux_level and flux_top are empty -- and their last row is stored once,
+// after the last level, from the carried precipitation fluxes (flux_surface).
+template <bool PROG = false, bool SURF = false, typename real, typename P, typename CS, typename S, typename LO>
 CLOUDSC_HD void flux_level(const P& c, const KArgs<real, S>& A, size_t h, LO lane,
                                            const LevelIn<real>& in, const LevelState<real>& ls,
                                            const PhysOut<real>& po, real paph_k, real paph_n,
@@ -1191,15 +1198,30 @@ CLOUDSC_HD void flux_level(const P& c, const KArgs<real, S>& A, size_t h, LO lan
     stg(A.pfsqltur, h, lo, cs.fl_ltur); stg(A.pfsqitur, h, lo, cs.fl_itur);
     stg(A.pfsqrf, h, lo, rf); stg(A.pfcqrng, h, lo, rng); stg(A.pfsqsf, h, lo, sf); stg(A.pfcqsng, h, lo, sng);
   }
-  const unsigned lo = lo_half(lane);
-  const real plsl = cs.pfx_r + R(0.0);      // zpfplsx[qr] + zpfplsx[ql] (ql flux is +0)
+  if constexpr (!SURF) {
+    const unsigned lo = lo_half(lane);
+    const real plsl = cs.pfx_r + R(0.0);      // zpfplsx[qr] + zpfplsx[ql] (ql flux is +0)
+    const real plsn = cs.pfx_s + cs.pfx_i;
+    stg(A.pfplsl, h, lo, plsl); stg(A.pfplsn, h, lo, plsn);
+    stg(A.pfhpsl, h, lo, -c.rlvtt * plsl); stg(A.pfhpsn, h, lo, -c.rlstt * plsn);
+  }
+}
+
+// SURF: row klev of pfplsl, pfplsn, pfhpsl, pfhpsn -- what flux_level stores at half level klev, from the
+// precipitation fluxes the last level left in the carried state -- into the members as surface fields
+// ([nblocks][nproma], u1 the block's base as for prainfrac).  Called once per column after the last
+// level, outside the level loop: it reads only what the carried state holds there anyway.
+template <typename real, typename P, typename CS, typename S, typename LO>
+CLOUDSC_HD void flux_surface(const P& c, const KArgs<real, S>& A, size_t u1, LO lane, const CS& cs) {
+  const unsigned lo = lo_surf(lane);
+  const real plsl = cs.pfx_r + R(0.0);      // as flux_level
   const real plsn = cs.pfx_s + cs.pfx_i;
-  stg(A.pfplsl, h, lo, plsl); stg(A.pfplsn, h, lo, plsn);
-  stg(A.pfhpsl, h, lo, -c.rlvtt * plsl); stg(A.pfhpsn, h, lo, -c.rlstt * plsn);
+  stg(A.pfplsl, u1, lo, plsl); stg(A.pfplsn, u1, lo, plsn);
+  stg(A.pfhpsl, u1, lo, -c.rlvtt * plsl); stg(A.pfhpsn, u1, lo, -c.rlstt * plsn);
 }
 
 // level-0 half-level outputs (cloudsc_c.c:2523-2543, 2578-2579)
-template <bool PROG = false, typename real, typename P, typename S, typename LO>
+template <bool PROG = false, bool SURF = false, typename real, typename P, typename S, typename LO>
 CLOUDSC_HD void flux_top(const P& c, const KArgs<real, S>& A, size_t h0, LO lane) {
   const unsigned lo = lo_half(lane);
   if constexpr (!PROG) {
@@ -1208,9 +1230,11 @@ CLOUDSC_HD void flux_top(const P& c, const KArgs<real, S>& A, size_t h0, LO lane
     stg(A.pfcqrng, h0, lo, R(0.0)); stg(A.pfcqsng, h0, lo, R(0.0));
     stg(A.pfsqltur, h0, lo, R(0.0)); stg(A.pfsqitur, h0, lo, R(0.0));
   }
-  const real plsl = R(0.0) + R(0.0), plsn = R(0.0) + R(0.0);
-  stg(A.pfplsl, h0, lo, plsl); stg(A.pfplsn, h0, lo, plsn);
-  stg(A.pfhpsl, h0, lo, -c.rlvtt * plsl); stg(A.pfhpsn, h0, lo, -c.rlstt * plsn);
+  if constexpr (!SURF) {
+    const real plsl = R(0.0) + R(0.0), plsn = R(0.0) + R(0.0);
+    stg(A.pfplsl, h0, lo, plsl); stg(A.pfplsn, h0, lo, plsn);
+    stg(A.pfhpsl, h0, lo, -c.rlvtt * plsl); stg(A.pfhpsn, h0, lo, -c.rlstt * plsn);
+  }
 }
 
 template <typename real, typename P, typename S, typename LO>
@@ -1283,7 +1307,8 @@ __device__ __forceinline__ const auto& params_here(const PV& pv, cptr<PT> cpar) 
 // persistent kernel (below) runs a column in level segments.
 //
 // F: the kernel's descriptor (KForm).  F::tb: the tendency buffer form (`ka`
-// then points at a KArgsTB); F::prog: the prognostic-outputs form (flux_level).
+// then points at a KArgsTB); F::prog: the prognostic-outputs form (flux_level); F::surf: the
+// surface-fluxes form (flux_level stores nothing; the caller stores the surface row, flux_surface).
 template <typename F, typename CS, typename LO>
 __device__ __forceinline__ void kcache_levels(cptr<typename F::fields> ka, cptr<typename F::params> cpar, int b,
                                               LO lo0, int lev0, int lev1, CS& cs) {
@@ -1439,7 +1464,7 @@ __device__ __forceinline__ void kcache_levels(cptr<typename F::fields> ka, cptr<
       // offsets formed from it stay live across the physics)
       const LO los = PVR || std::is_same<LO, PackLo>::value ? launder_vgpr(lo0) : lo;
       store_level<F::tb>(A, u2, u3, k, klev, nproma, los, physics, ls, po);
-      flux_level<F::prog>(c, A, uh + (size_t)(k + 1) * nproma, los, cur, ls, po, nb.paph_k, nb.paph_n, cs);
+      flux_level<F::prog, F::surf>(c, A, uh + (size_t)(k + 1) * nproma, los, cur, ls, po, nb.paph_k, nb.paph_n, cs);
     }
 
     // ---- rotate carried state ----
@@ -1514,11 +1539,15 @@ __device__ __forceinline__ void cloudsc_kcache_body(cptr<typename F::fields> ka,
   init_carry<real, F::prog>(cs);
   {
     CLOUDSC_PARAMS_HERE;
-    flux_top<F::prog>(c, A, (size_t)b * (A.klev + 1) * A.nproma, lo);
+    flux_top<F::prog, F::surf>(c, A, (size_t)b * (A.klev + 1) * A.nproma, lo);
   }
   kcache_levels<F>(ka, cpar, b, lo, 0, A.klev, cs);
   stg(((const KArgs<real, S>*)launder_uniform(ka))->prainfrac, (size_t)b * A.nproma, lo_surf(lane_here(lo)),
       cs.rainfrac);
+  if constexpr (F::surf) {
+    CLOUDSC_PARAMS_HERE;
+    flux_surface(c, *(const KArgs<real, S>*)launder_uniform(ka), (size_t)b * A.nproma, lane_here(lo), cs);
+  }
 }
 
 // ===================== persistent (work-queue) SCC-k-caching =====================
@@ -1684,9 +1713,11 @@ __device__ __forceinline__ void cloudsc_kcache_persistent_body(cptr<typename F::
     CarryOf<real, F::ldsc> cs(carry_lds_base<real>());
     if (seg == 0) {
       init_carry<real, F::prog>(cs);
-      if (active) {
-        CLOUDSC_PARAMS_HERE;
-        flux_top<F::prog>(c, A, (size_t)b * (A.klev + 1) * nproma, lo);
+      if constexpr (!F::surf) {   // (the surface-fluxes form stores nothing at the top)
+        if (active) {
+          CLOUDSC_PARAMS_HERE;
+          flux_top<F::prog, F::surf>(c, A, (size_t)b * (A.klev + 1) * nproma, lo);
+        }
       }
     } else {
       // consumer: one relaxed poll (bounded, with s_sleep), one agent acquire,
@@ -1722,6 +1753,10 @@ __device__ __forceinline__ void cloudsc_kcache_persistent_body(cptr<typename F::
       __syncthreads();
       if (wave0) __hip_atomic_store(P.flags + sb, P.stamp + (unsigned)(seg + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     } else if (active) {
+      if constexpr (F::surf) {   // the last segment ends at the last level: the surface row of the four fluxes
+        CLOUDSC_PARAMS_HERE;
+        flux_surface(c, *(const KArgs<real, ST>*)launder_uniform(ka), (size_t)b * nproma, lo_e, cs);
+      }
       stg(((const KArgs<real, ST>*)launder_uniform(ka))->prainfrac, (size_t)b * nproma, lo_surf(lo_e), cs.rainfrac);
     }
 #ifdef CLOUDSC_KSEG_TRACE

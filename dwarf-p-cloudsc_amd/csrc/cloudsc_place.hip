@@ -44,7 +44,9 @@ struct ProbeArgs {
   void* out_level[kProbeOutLevel];
   void* out_species;                  // tendency_loc_cld: species 0..4 written
   void* out_half[kProbeOutHalf];
-  void* out_surf;                     // prainfrac_toprfz
+  // prainfrac_toprfz and, with CLOUDSC_OUTPUTS_SURFACE, pfplsl, pfplsn, pfhpsl, pfhpsn as surface fields
+  // (their out_half slots are then NULL): one store each after the last level, as the kernel's
+  void* out_surf[1 + 4];
   int ngptot, nproma, klev, nsub, nitems;
   // element strides of the inputs [0..2] and the outputs [3..5]: between blocks,
   // between rows (levels), between species planes; 0 = the reference block
@@ -139,18 +141,23 @@ __global__ void __launch_bounds__(64) place_probe_kernel(const ProbeArgs a) {
         for (int q = 0; q < NL; q++) acc += cur[q];
       }
     }
-    if (a.out_surf) st_out<real>(a.out_surf, (size_t)b * np + jl, acc);
+#pragma unroll
+    for (int q = 0; q < 1 + 4; q++)
+      if (a.out_surf[q]) st_out<real>(a.out_surf[q], (size_t)b * np + jl, acc);
   }
 }
 
 // outputs: with CLOUDSC_OUTPUTS_PROGNOSTIC the ten diagnostic flux members are not looked at: their slots
-// stay NULL, which the kernel skips like any other NULL member
+// stay NULL, which the kernel skips like any other NULL member; with CLOUDSC_OUTPUTS_SURFACE the four
+// precipitation / enthalpy flux members are surface fields (field_kind_of) and go to surface slots: the probe
+// writes them once per column after the last level and never as profiles (they hold nproma elements per block)
 ProbeArgs probe_args(const cloudsc_fields_t* f, int ngptot, int nproma, int klev, bool read, int outputs) {
   ProbeArgs a;
   std::memset(&a, 0, sizeof(a));
-  int nil = 0, nis = 0, nol = 0, noh = 0;
+  int nil = 0, nis = 0, nol = 0, noh = 0, nos = 0;
   for (int m = 0; m < kNumFields; m++) {
-    const FieldDesc& d = kFieldTable[m];
+    FieldDesc d = kFieldTable[m];
+    d.kind = field_kind_of(m, outputs);
     void* p = output_selected(m, outputs) ? ((void* const*)f)[m] : nullptr;
     if (d.dir == CLOUDSC_FD_IN && read) {
       if (d.kind == CLOUDSC_FK_LEVEL) a.in_level[nil++] = p;
@@ -160,7 +167,7 @@ ProbeArgs probe_args(const cloudsc_fields_t* f, int ngptot, int nproma, int klev
       if (d.kind == CLOUDSC_FK_LEVEL) a.out_level[nol++] = p;
       else if (d.kind == CLOUDSC_FK_SPECIES) a.out_species = p;
       else if (d.kind == CLOUDSC_FK_HALF) a.out_half[noh++] = p;
-      else a.out_surf = p;
+      else a.out_surf[nos++] = p;
     }
   }
   a.ngptot = ngptot;
@@ -471,11 +478,11 @@ bool fields_unregister(void* p, int device) {
   return true;
 }
 
-size_t member_bytes(int m, int precision, int ngptot, int nproma, int klev) {
+size_t member_bytes(int m, int precision, int ngptot, int nproma, int klev, int outputs = CLOUDSC_OUTPUTS_ALL) {
   const FieldDesc& d = kFieldTable[m];
   const size_t nb = (size_t)(ngptot / nproma + (ngptot % nproma ? 1 : 0));
   const size_t es = d.is_int ? sizeof(int) : precision_storage_bytes(precision);
-  return nb * per_block_elems(d.kind, nproma, klev) * es;
+  return nb * per_block_elems(field_kind_of(m, outputs), nproma, klev) * es;
 }
 
 }  // namespace
@@ -483,7 +490,8 @@ size_t member_bytes(int m, int precision, int ngptot, int nproma, int klev) {
 extern "C" int cloudsc_fields_free(int device, cloudsc_fields_t* f);
 
 // cloudsc_fields_alloc for an output selection: members the selection leaves out are not allocated (they stay
-// NULL) and take no part in the search or its probe
+// NULL) and take no part in the search or its probe; with CLOUDSC_OUTPUTS_SURFACE the four precipitation /
+// enthalpy flux members are allocated, searched and probed as surface fields
 static int fields_alloc(int device, int precision, int ngptot, int nproma, int klev, int flags, int outputs,
                         cloudsc_fields_t* out, cloudsc_placement_t* report) {
   if (!out || (flags & ~(CLOUDSC_PLACE_NONE | CLOUDSC_ALLOC_AEROSOLS))) return CLOUDSC_EINVAL;
@@ -497,7 +505,7 @@ static int fields_alloc(int device, int precision, int ngptot, int nproma, int k
     if (kFieldTable[m].dir == CLOUDSC_FD_AEROSOL && !(flags & CLOUDSC_ALLOC_AEROSOLS)) continue;
     if (!output_selected(m, outputs)) continue;
     void* p = nullptr;
-    const hipError_t e = dev_malloc(&p, member_bytes(m, precision, ngptot, nproma, klev));
+    const hipError_t e = dev_malloc(&p, member_bytes(m, precision, ngptot, nproma, klev, outputs));
     if (e != hipSuccess) {
       hip_fail(e, "hipMalloc");
       cloudsc_fields_free(device, out);
@@ -515,7 +523,7 @@ static int fields_alloc(int device, int precision, int ngptot, int nproma, int k
     if ((kFieldTable[m].dir == CLOUDSC_FD_OUT || kFieldTable[m].dir == CLOUDSC_FD_INOUT) &&
         output_selected(m, outputs)) {
       members[n] = m;
-      bytes[n] = member_bytes(m, precision, ngptot, nproma, klev);
+      bytes[n] = member_bytes(m, precision, ngptot, nproma, klev, outputs);
       set_bytes += bytes[n++];
     }
   // two candidate sets and their spacers at most (search_outputs)
@@ -587,7 +595,7 @@ extern "C" int cloudsc_fields_alloc(int device, int precision, int ngptot, int n
 
 extern "C" int cloudsc_fields_alloc_outputs(int device, int precision, int ngptot, int nproma, int klev, int flags,
                                             int outputs, cloudsc_fields_t* out, cloudsc_placement_t* report) {
-  if (outputs != CLOUDSC_OUTPUTS_ALL && outputs != CLOUDSC_OUTPUTS_PROGNOSTIC) return CLOUDSC_EINVAL;
+  if (!outputs_known(outputs)) return CLOUDSC_EINVAL;
   return fields_alloc(device, precision, ngptot, nproma, klev, flags, outputs, out, report);
 }
 

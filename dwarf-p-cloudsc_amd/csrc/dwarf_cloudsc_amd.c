@@ -60,7 +60,7 @@ typedef struct {
   int transfer, chunk_blocks, nstreams, exact_libm;
   int fields_caller;              /* --fields caller | tendbuf | tendbuf-inplace (1 | 2 | 3): caller-owned field sets */
   int tend_planes;                /* --fields tendbuf: planes per block of the two tendency buffers (0: not tendbuf) */
-  int outputs, outputs_given;     /* --outputs all|prognostic: CLOUDSC_OUTPUTS_* */
+  int outputs, outputs_given;     /* --outputs all|prognostic|surface: CLOUDSC_OUTPUTS_* */
   int place;                      /* placement search: 1 on, 0 off, -1 auto (on when reps > 1) */
   int narrow_pack;                /* NPROMA <= 32 packed into full waves: 1 on, 0 off, -1 the library's default */
   double energy_s;                /* --energy: seconds of back-to-back launches sampled for board power */
@@ -148,6 +148,9 @@ static void usage(const char *prog) {
           "  --tend-planes N       --fields tendbuf[-inplace]: planes per block of the two buffers, 8..64 (default 8)\n"
           "  --outputs all|prognostic  --fields caller|tendbuf|tendbuf-inplace: prognostic = a step without the ten\n"
           "                        diagnostic fluxes, which are not allocated, validated or printed (kseg, kcache)\n"
+          "  --outputs surface     prognostic, and PFPLSL, PFPLSN, PFHPSL, PFHPSN held at the surface only: their rows\n"
+          "                        are validated against the last half level of the reference profiles (kseg and\n"
+          "                        kcache as above; also --variant cpu, fp64 or mixed, without --fields)\n"
           "  --transfer            host-buffer path: block-layout arrays in host memory,\n"
           "                        H2D -> kernel -> D2H per chunk, overlapped on streams\n"
           "                        (TOTAL includes the transfers, like cloudsc_driver.cu)\n"
@@ -233,6 +236,7 @@ static int parse(int argc, char **argv, options_t *o) {
       o->outputs_given = 1;
       if (!strcmp(v, "all")) o->outputs = CLOUDSC_OUTPUTS_ALL;
       else if (!strcmp(v, "prognostic")) o->outputs = CLOUDSC_OUTPUTS_PROGNOSTIC;
+      else if (!strcmp(v, "surface")) o->outputs = CLOUDSC_OUTPUTS_SURFACE;
       else { fprintf(stderr, "bad --outputs %s\n", v); return -1; }
     }
     else if (!strcmp(a, "--fp32-exact-libm")) o->exact_libm = 1;
@@ -552,7 +556,8 @@ static const int k_out_kind[CLOUDSC_NFIELDS] = {CLOUDSC_FIELDS(OUT_KIND)};
 static int run_host(const options_t *o, const cloudsc_dataset_t *ds) {
   const int cpu = o->variant == VARIANT_CPU;
   const int es = precision_bytes(o->precision);
-  const int per_thread = cpu && o->precision == CLOUDSC_FP64;   /* the zinfo record: cloudsc_cpu_run_threads, fp64 */
+  /* the zinfo record: cloudsc_cpu_run_threads, fp64 (cloudsc_cpu_run_outputs, --outputs surface, keeps none) */
+  const int per_thread = cpu && o->precision == CLOUDSC_FP64 && o->outputs != CLOUDSC_OUTPUTS_SURFACE;
   const int nb = o->ngptot / o->nproma + (o->ngptot % o->nproma ? 1 : 0);
   const int aer = ds->params.laericesed || ds->params.laericeauto;
   cloudsc_fields_t f;
@@ -580,9 +585,13 @@ static int run_host(const options_t *o, const cloudsc_dataset_t *ds) {
       memcpy(plude0, dst, bytes);
     }
   }
+  /* --outputs surface (--variant cpu): the ten diagnostic fluxes are not allocated, the four others are surface fields */
+  const int surface = cpu && o->outputs == CLOUDSC_OUTPUTS_SURFACE;
   for (int m = 0; m < CLOUDSC_NFIELDS && !rc; m++) {
     if (k_out_kind[m] < 0) continue;
-    const size_t bytes = (size_t)nb * (size_t)cloudsc_io_elems(k_out_kind[m], ds->klev, o->nproma) * es;
+    if (surface && m >= CLOUDSC_M_pfsqlf && m <= CLOUDSC_M_pfsqitur) continue;
+    const int okind = surface && m >= CLOUDSC_M_pfplsl && m <= CLOUDSC_M_pfhpsn ? CLOUDSC_FK_SURFACE : k_out_kind[m];
+    const size_t bytes = (size_t)nb * (size_t)cloudsc_io_elems(okind, ds->klev, o->nproma) * es;
     void *dst = aligned_alloc(4096, (bytes + 4095) & ~(size_t)4095);
     if (!dst) { rc = CLOUDSC_ENOMEM; break; }
     memset(dst, 0xff, bytes);            /* NaN: the callee must write every element */
@@ -609,7 +618,9 @@ static int run_host(const options_t *o, const cloudsc_dataset_t *ds) {
     double ms = 0.0;
     if (cpu) {
       double secs = 0.0;
-      if (per_thread)
+      if (surface)
+        rc = cloudsc_cpu_run_outputs(nth, o->precision, o->outputs, o->ngptot, o->nproma, ds->klev, &ds->params, &f);
+      else if (per_thread)
         rc = cloudsc_cpu_run_threads(nth, o->ngptot, o->nproma, ds->klev, &ds->params, &f, &secs, th_step,
                                      th_blk_step, th_col_step);
       else
@@ -656,8 +667,14 @@ static int run_host(const options_t *o, const cloudsc_dataset_t *ds) {
       double worst = 0.0;
       for (int v = 0; v < CLOUDSC_NVALID; v++) {
         cloudsc_stats_t st;
-        const int kind = cloudsc_io_ref_kind[v];
-        cloudsc_io_field_stats(ds->ref[v], kind, ds->klev, ds->klon, fp[k_valid_field[v]], es, o->ngptot,
+        int kind = cloudsc_io_ref_kind[v];
+        const double *refv = ds->ref[v];
+        if (!fp[k_valid_field[v]]) continue;   /* --outputs surface: not allocated, not computed: no row */
+        if (surface && k_valid_field[v] >= CLOUDSC_M_pfplsl && k_valid_field[v] <= CLOUDSC_M_pfhpsn) {
+          refv += (size_t)ds->klev * ds->klon;   /* the surface row of the reference profile */
+          kind = CLOUDSC_FK_SURFACE;
+        }
+        cloudsc_io_field_stats(refv, kind, ds->klev, ds->klon, fp[k_valid_field[v]], es, o->ngptot,
                                o->nproma, 0, &st);
         const double rel = print_error(cloudsc_io_print_names[v], kind == 3 ? 1 : kind == 2 ? 3 : 2, &st,
                                        o->ngptot);
@@ -726,8 +743,12 @@ int main(int argc, char **argv) {
     cloudsc_io_free(&ds);
     return EXIT_FAILURE;
   }
-  if (o.outputs_given && (!o.fields_caller || o.transfer || o.exact_libm ||
-                          (o.variant != CLOUDSC_VARIANT_KSEG && o.variant != CLOUDSC_VARIANT_KCACHE))) {
+  /* (--outputs surface alone with --variant cpu: the host step, run_host) */
+  const int cpu_surface = o.outputs_given && o.outputs == CLOUDSC_OUTPUTS_SURFACE && o.variant == VARIANT_CPU &&
+                          !o.fields_caller && !o.transfer && !o.exact_libm;
+  if (o.outputs_given && !cpu_surface &&
+      (!o.fields_caller || o.transfer || o.exact_libm ||
+       (o.variant != CLOUDSC_VARIANT_KSEG && o.variant != CLOUDSC_VARIANT_KCACHE))) {
     fprintf(stderr, "dwarf-cloudsc-amd: --outputs goes with --fields caller|tendbuf|tendbuf-inplace and --variant "
                     "kseg|kcache (no --transfer, no --fp32-exact-libm)\n");
     cloudsc_io_free(&ds);
@@ -948,7 +969,9 @@ int main(int argc, char **argv) {
       if (sh[0].skipped[f]) continue;   /* --outputs prognostic: not allocated, not computed: no row */
       cloudsc_stats_t s = sh[0].stats[f];
       for (int d = 1; d < nused; d++) cloudsc_stats_combine(&s, &sh[d].stats[f]);   /* double-double sums */
-      const int kind = cloudsc_io_ref_kind[f];
+      int kind = cloudsc_io_ref_kind[f];
+      /* --outputs surface: the four rows are the surface row's statistics */
+      if (o.outputs == CLOUDSC_OUTPUTS_SURFACE && f >= CLOUDSC_F_PFPLSL && f <= CLOUDSC_F_PFHPSN) kind = CLOUDSC_FK_SURFACE;
       const double rel = print_error(cloudsc_io_print_names[f], kind == 3 ? 1 : kind == 2 ? 3 : 2, &s, o.ngptot);
       if (rel > worst) worst = rel;
       if (gate && !(rel <= o.tol)) bad++;

@@ -292,6 +292,17 @@ int cloudsc_fields_convert(int device, void *stream, int ngptot, int klev,
                            int src_precision, int src_nproma, const cloudsc_fields_t *src,
                            int dst_precision, int dst_nproma, const cloudsc_fields_t *dst);
 
+/* cloudsc_fields_convert for two sets of one output selection (below, "Output
+ * selection").  With CLOUDSC_OUTPUTS_SURFACE the members pfplsl, pfplsn, pfhpsl,
+ * pfhpsn of both sets are surface fields ([nblocks][nproma]) and are re-blocked
+ * and re-typed as such; every other member as in cloudsc_fields_convert, which
+ * this IS for CLOUDSC_OUTPUTS_ALL and CLOUDSC_OUTPUTS_PROGNOSTIC.  CLOUDSC_EINVAL:
+ * an unknown `outputs` value and every argument error of cloudsc_fields_convert,
+ * before the first HIP call. */
+int cloudsc_fields_convert_outputs(int device, void *stream, int ngptot, int klev, int outputs,
+                                   int src_precision, int src_nproma, const cloudsc_fields_t *src,
+                                   int dst_precision, int dst_nproma, const cloudsc_fields_t *dst);
+
 /* The same on HOST arrays, on `nthreads` host threads (<= 0: all hardware
  * threads) taking destination blocks from a shared counter: the same
  * semantics, conversion and errors.  Needs no GPU. */
@@ -396,6 +407,46 @@ int cloudsc_cpu_fields_convert_tendbuf(int nthreads, int ngptot, int klev,
  * pfplsn, pfhpsl, pfhpsn. */
 #define CLOUDSC_OUTPUTS_ALL        0   /* all 21 outputs, as cloudsc_gpu_run                        */
 #define CLOUDSC_OUTPUTS_PROGNOSTIC 1   /* the ten diagnostic fluxes neither computed nor written   */
+/* A selection is a bit set.  Bit 0 (value 1, CLOUDSC_OUTPUTS_PROGNOSTIC): no
+ * diagnostic flux profiles.  Bit 2 (value 4): the four precipitation / enthalpy
+ * fluxes pfplsl, pfplsn, pfhpsl, pfhpsn at the surface only; valid only together
+ * with bit 0.  The value 4 alone, the value 2 and every other value are unknown
+ * (CLOUDSC_EINVAL) everywhere a selection is taken.
+ *
+ * CLOUDSC_OUTPUTS_SURFACE: what a host model couples to its surface scheme is
+ * the surface precipitation and its enthalpy flux -- the last half-level row,
+ * row klev (0-based) of the klev + 1 rows of the four profiles; the other rows
+ * are budget diagnostics (at KLEV 137 in fp64 4,416 of the 56,036 B a column
+ * writes).  With this selection
+ *   - everything CLOUDSC_OUTPUTS_PROGNOSTIC says about the ten diagnostic
+ *     members holds: not computed, read or written, may be NULL, a non-NULL one
+ *     keeps every byte;
+ *   - pfplsl, pfplsn, pfhpsl, pfhpsn are SURFACE FIELDS with the layout of
+ *     prainfrac_toprfz, [nblocks][nproma] in the storage type; element [b][l]
+ *     holds, bit for bit, what the full step stores at [b][klev][l] of the
+ *     [nblocks][klev+1][nproma] profile, and nothing else of these profiles is
+ *     stored anywhere.  The four members are required (non-NULL); padding lanes
+ *     of a partial last block are not written;
+ *   - plude, tendency_loc_t/q/a/cld, pcovptot and prainfrac_toprfz have the bits
+ *     of the full step.
+ * Support: cloudsc_gpu_run_outputs, cloudsc_cpu_run_outputs,
+ * cloudsc_gpu_run_tendbuf_outputs, cloudsc_cpu_run_tendbuf_outputs,
+ * cloudsc_fields_alloc_outputs, cloudsc_fields_validate_tendbuf,
+ * cloudsc_fields_compare_outputs and cloudsc_fields_convert_outputs take it.
+ *   GPU: KCACHE and KSEG x fp64, fp32, mixed x aerosols on / off x unpacked /
+ *        packed narrow blocks x separate arrays / packed tendency buffers.
+ *        SCC, SCC_PRIVATE and CLOUDSC_FP32_EXACT_LIBM: CLOUDSC_EINVAL before any
+ *        HIP call.  One KSEG workspace serves ALL, PROGNOSTIC and SURFACE
+ *        launches in any order.
+ *   CPU: fp64 and mixed.
+ * Not covered: the device-resident state (cloudsc_state_*), the host pipelines
+ * and the drop-in always run CLOUDSC_OUTPUTS_ALL.  cloudsc_fields_compare,
+ * cloudsc_fields_convert, cloudsc_fields_expand and their _tendbuf forms walk
+ * members by the inventory's kind and know nothing of selections: a SURFACE set
+ * must pass them with these four members NULL (fields_subset in Python), or go
+ * through the _outputs forms below. */
+#define CLOUDSC_OUTPUTS_SURFACE_BIT 4
+#define CLOUDSC_OUTPUTS_SURFACE    5   /* PROGNOSTIC, and pfplsl/pfplsn/pfhpsl/pfhpsn as [nblocks][nproma] */
 
 /* cloudsc_gpu_run with an output selection.  With CLOUDSC_OUTPUTS_ALL it IS
  * cloudsc_gpu_run: the same kernels, the same argument rules.  With
@@ -462,6 +513,11 @@ int cloudsc_cpu_run_tendbuf_outputs(int nthreads, int precision, int outputs, in
  * members are not allocated and stay NULL (10 * (klev + 1) elements per column
  * of device memory less), and the placement search and its probe run over the
  * eleven allocated outputs only.  cloudsc_fields_free frees such a set.
+ * With CLOUDSC_OUTPUTS_SURFACE the ten stay NULL as well, and pfplsl, pfplsn,
+ * pfhpsl, pfhpsn are allocated as surface fields, nblocks * nproma elements
+ * each (4 * klev elements per column less again); the search and its probe run
+ * over the seven full-size outputs and these four small ones, the probe
+ * writing the four once per column after the last level, as the kernel does.
  * CLOUDSC_EINVAL: an unknown `outputs` value (before the first HIP call) and
  * every argument error of cloudsc_fields_alloc. */
 int cloudsc_fields_alloc_outputs(int device, int precision, int ngptot, int nproma, int klev, int flags,
@@ -885,6 +941,18 @@ int cloudsc_fields_compare(int device, void *stream, int ngptot, int klev,
                            int b_precision, int b_nproma, const cloudsc_fields_t *b,
                            cloudsc_field_diff_t *diff);
 
+/* cloudsc_fields_compare for two sets of one output selection.  With
+ * CLOUDSC_OUTPUTS_SURFACE the members pfplsl, pfplsn, pfhpsl, pfhpsn of both
+ * sets are surface fields ([nblocks][nproma], one row: compared = ngptot,
+ * first_row 0); every other member is walked by its kind.  With
+ * CLOUDSC_OUTPUTS_ALL and CLOUDSC_OUTPUTS_PROGNOSTIC it IS cloudsc_fields_compare.
+ * CLOUDSC_EINVAL: an unknown `outputs` value and every argument error of
+ * cloudsc_fields_compare, before the first HIP call. */
+int cloudsc_fields_compare_outputs(int device, void *stream, int ngptot, int klev, int outputs,
+                                   int a_precision, int a_nproma, const cloudsc_fields_t *a,
+                                   int b_precision, int b_nproma, const cloudsc_fields_t *b,
+                                   cloudsc_field_diff_t *diff);
+
 /* The same on HOST arrays, on `nthreads` host threads (<= 0: all hardware
  * threads) taking blocks of a from a shared counter, the threads' records
  * combined in thread order: the same semantics and errors.  Needs no GPU. */
@@ -936,7 +1004,11 @@ int cloudsc_fields_validate(int device, void *stream, int precision, int ngptot,
  * its stats[] record is then the "skipped" record of cloudsc_fields_compare,
  * {DBL_MAX, -DBL_MAX, 0, ...}.  A diagnostic member that is non-NULL while its
  * reference array is NULL, or the reverse, is CLOUDSC_EINVAL; one present on
- * both sides is validated.  tend_planes 0 with CLOUDSC_OUTPUTS_ALL is
+ * both sides is validated.  With CLOUDSC_OUTPUTS_SURFACE the same holds for the
+ * ten, and the four surface fields pfplsl, pfplsn, pfhpsl, pfhpsn are compared
+ * with row klev of their reference profiles ([klev+1][klon], required): their
+ * stats[] records, under the usual ids, are the statistics of that row alone.
+ * tend_planes 0 with CLOUDSC_OUTPUTS_ALL is
  * cloudsc_fields_validate.  Nothing is written to the fields; padding lanes and
  * planes no member points at are never read.  CLOUDSC_EINVAL also: an unknown
  * `outputs` value, a non-zero tend_planes outside 8..64 and every argument
