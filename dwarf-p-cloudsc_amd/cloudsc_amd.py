@@ -130,6 +130,12 @@ class Fields(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ALL_FIELDS]
 
 
+class TendCml(C.Structure):
+    """cloudsc_tend_cml_t: the plane starts of the cumulative tendency buffer (BUFFER_CML) in block 0; cld
+    is the first of five consecutive planes, the fifth (vapour) never touched."""
+    _fields_ = [(n, C.c_void_p) for n in ("t", "q", "a", "cld")]
+
+
 class Placement(C.Structure):
     """cloudsc_placement_t: what a placement search cost and found."""
     _fields_ = [("probe_first_ms", C.c_float), ("probe_final_ms", C.c_float), ("tries", C.c_int),
@@ -537,6 +543,16 @@ def gpu_lib(path: Optional[str] = None):
             C.c_longlong, C.POINTER(Fields), C.POINTER(Reference), C.POINTER(Stats)]
         lib.cloudsc_fields_expand_tendbuf.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                                       C.c_longlong, C.POINTER(Template), C.POINTER(Fields)]
+    if hasattr(lib, "cloudsc_gpu_run_tendbuf_cml"):   # (likewise: the cumulative tendency buffer)
+        lib.cloudsc_tendbuf_bind_cml.argtypes = [C.POINTER(TendCml), C.c_int, C.c_int, C.c_int, C.c_void_p]
+        lib.cloudsc_gpu_run_tendbuf_cml.argtypes = [C.c_int, C.c_void_p] + [C.c_int] * 7 + [
+            C.POINTER(Fields), C.POINTER(TendCml), C.c_void_p]
+        lib.cloudsc_cpu_run_tendbuf_cml.argtypes = [C.c_int] * 7 + [C.POINTER(Params), C.POINTER(Fields),
+                                                                    C.POINTER(TendCml)]
+        lib.cloudsc_fields_accumulate_tendbuf.argtypes = [C.c_int, C.c_void_p] + [C.c_int] * 5 + [
+            C.POINTER(Fields), C.c_int, C.POINTER(TendCml)]
+        lib.cloudsc_cpu_fields_accumulate_tendbuf.argtypes = [C.c_int] * 6 + [C.POINTER(Fields), C.c_int,
+                                                                              C.POINTER(TendCml)]
     if hasattr(lib, "cloudsc_fields_compare_outputs"):   # (likewise: the forms for a set of one output selection)
         lib.cloudsc_fields_convert_outputs.argtypes = [C.c_int, C.c_void_p] + [C.c_int] * 5 + [
             C.POINTER(Fields), C.c_int, C.c_int, C.POINTER(Fields)]
@@ -731,6 +747,63 @@ def cpu_run_tendbuf_outputs(params: "Params", f: "Fields", precision: int, outpu
     packed buffers, with an output selection (precision FP64 or MIXED)."""
     check(gpu_lib().cloudsc_cpu_run_tendbuf_outputs(nthreads, precision, outputs, ngptot, nproma, klev, tend_planes,
                                                     C.byref(params), C.byref(f)))
+
+
+def bind_tendbuf_cml(precision: int, nproma: int, klev: int, buffer_cml: int) -> "TendCml":
+    """cloudsc_tendbuf_bind_cml: the four cumulative plane starts of a packed buffer (host or device address)
+    in the reference's plane order."""
+    cml = TendCml()
+    check(gpu_lib().cloudsc_tendbuf_bind_cml(C.byref(cml), precision, nproma, klev, buffer_cml))
+    return cml
+
+
+def bind_tendbuf_three(f: "Fields", precision: int, nproma: int, klev: int, buffer_tmp: int, buffer_cml: int,
+                       buffer_loc: Optional[int] = None) -> tuple:
+    """The three buffers of a Fortran-driver caller bound in the reference's plane order: the tendency_tmp_*
+    members of f to buffer_tmp, the returned TendCml to buffer_cml, and tendency_loc_* to buffer_loc -- or to
+    None where the caller keeps no BUFFER_LOC (the fused form, gpu_run_tendbuf_cml, never touches them).
+    Returns (f, cml)."""
+    if buffer_loc is None:
+        bind_tendbuf(f, precision, nproma, klev, buffer_tmp, buffer_tmp)
+        for n in ("tendency_loc_t", "tendency_loc_q", "tendency_loc_a", "tendency_loc_cld"):
+            setattr(f, n, None)
+    else:
+        bind_tendbuf(f, precision, nproma, klev, buffer_tmp, buffer_loc)
+    return f, bind_tendbuf_cml(precision, nproma, klev, buffer_cml)
+
+
+def gpu_run_tendbuf_cml(f: "Fields", cml: "TendCml", precision: int, variant: int, outputs: int, ngptot: int,
+                        nproma: int, klev: int, tend_planes: int, scratch=None, device: int = 0, stream=None) -> None:
+    """cloudsc_gpu_run_tendbuf_cml: the prognostic (or surface) step on packed tendency buffers with its seven
+    local tendencies ADDED to the cumulative planes `cml` instead of stored to tendency_loc_* (which may be
+    None and are never touched).  fp64 / fp32: cml += loc, one add in the storage type; mixed: cml =
+    float32(float64(cml) + loc64).  The vapour plane of cml is neither read nor written.  OUTPUTS_ALL is
+    refused.  A launch adds once: repeated launches accumulate repeatedly.  Asynchronous."""
+    check(gpu_lib().cloudsc_gpu_run_tendbuf_cml(device, stream, precision, variant, outputs, ngptot, nproma, klev,
+                                                tend_planes, C.byref(f), C.byref(cml), scratch))
+
+
+def cpu_run_tendbuf_cml(params: "Params", f: "Fields", cml: "TendCml", precision: int, outputs: int, ngptot: int,
+                        nproma: int, klev: int, tend_planes: int, nthreads: int = 0) -> None:
+    """cloudsc_cpu_run_tendbuf_cml: the same on HOST memory (fp64 and mixed)."""
+    check(gpu_lib().cloudsc_cpu_run_tendbuf_cml(nthreads, precision, outputs, ngptot, nproma, klev, tend_planes,
+                                                C.byref(params), C.byref(f), C.byref(cml)))
+
+
+def accumulate_tendbuf(loc: "Fields", cml: "TendCml", precision: int, ngptot: int, nproma: int, klev: int,
+                       loc_tend_planes: int, cml_tend_planes: int, device: int = 0, stream=None) -> None:
+    """cloudsc_fields_accumulate_tendbuf: cml += tendency_loc_* of `loc` over the seven planes on the device,
+    one add in the storage type (float for fp32 and mixed: the stored float is added, unlike the fused form's
+    mixed rule).  *_tend_planes: 0 for separate arrays, 8..64 for planes of a packed buffer.  Asynchronous."""
+    check(gpu_lib().cloudsc_fields_accumulate_tendbuf(device, stream, precision, ngptot, nproma, klev,
+                                                      loc_tend_planes, C.byref(loc), cml_tend_planes, C.byref(cml)))
+
+
+def cpu_accumulate_tendbuf(loc: "Fields", cml: "TendCml", precision: int, ngptot: int, nproma: int, klev: int,
+                           loc_tend_planes: int, cml_tend_planes: int, nthreads: int = 0) -> None:
+    """cloudsc_cpu_fields_accumulate_tendbuf: the same on HOST arrays."""
+    check(gpu_lib().cloudsc_cpu_fields_accumulate_tendbuf(nthreads, precision, ngptot, nproma, klev, loc_tend_planes,
+                                                          C.byref(loc), cml_tend_planes, C.byref(cml)))
 
 
 def convert_fields_tendbuf(src: "Fields", dst: "Fields", ngptot: int, klev: int, src_precision: int,

@@ -40,8 +40,9 @@ struct HostColumn {
 // real: the compute type, S: the fields' element type (float under double = CLOUDSC_MIXED);
 // TB: the tendency members are planes of packed buffers and A is a KArgsTB (cloudsc_kcache.h);
 // PROG: the prognostic-outputs form, the ten diagnostic flux members of A never touched (flux_level);
-// SURF: the surface-fluxes form, the other four flux members surface fields written after the last level
-template <typename real, bool AER, bool TB, bool PROG = false, bool SURF = false, typename S>
+// SURF: the surface-fluxes form, the other four flux members surface fields written after the last level;
+// CML: the cumulative tendency form, A a KArgsCML and the local tendencies added to its planes (load_cml, store_level_cml)
+template <typename real, bool AER, bool TB, bool PROG = false, bool SURF = false, bool CML = false, typename S>
 void run_block(const DevParams<real>& c, const KArgs<real, S>& A, int b, std::vector<HostColumn<real>>& col) {
   const int nproma = A.nproma, klev = A.klev;
   const int bsize = std::min(nproma, A.ngptot - b * nproma);
@@ -82,7 +83,13 @@ void run_block(const DevParams<real>& c, const KArgs<real, S>& A, int b, std::ve
       po.atend = R(0.0);
       po.zcovptot_out = R(0.0);
       if (physics) physics_level(c, k, klev, ncldtop0, cur, h.nb, h.cc, ls, h.cs, po);
-      store_level<TB>(A, u2, u3, k, klev, nproma, lo, physics, ls, po);
+      if constexpr (CML) {
+        CmlIn<real> cm;
+        load_cml(cm, A, u2, k, klev, nproma, lo);
+        store_level_cml(A, u2, k, klev, nproma, lo, ls, po, cm);
+      } else {
+        store_level<TB>(A, u2, u3, k, klev, nproma, lo, physics, ls, po);
+      }
       flux_level<PROG, SURF>(c, A, uh + (size_t)(k + 1) * nproma, lo, cur, ls, po, h.nb.paph_k, h.nb.paph_n, h.cs);
       h.cs.t_prev = ls.ztp1;
       h.cs.a_prev = ls.za;
@@ -105,17 +112,21 @@ void run_block(const DevParams<real>& c, const KArgs<real, S>& A, int b, std::ve
 template <typename S>
 int cpu_run(int nthreads, int ngptot, int nproma, int klev, const cloudsc_params_t* params,
             const cloudsc_fields_t* f, double* seconds, double* thread_seconds, int* thread_blocks,
-            int* thread_columns, int tend_planes = 0, int outputs = CLOUDSC_OUTPUTS_ALL) {
+            int* thread_columns, int tend_planes = 0, int outputs = CLOUDSC_OUTPUTS_ALL,
+            const cloudsc_tend_cml_t* cml = nullptr) {
   int rc = cloudsc_impl::check_params(params);
   if (rc) return rc;
-  if (!f || !cloudsc_impl::fields_complete(f, outputs) || ngptot <= 0 || nproma <= 0 || klev < 2) return CLOUDSC_EINVAL;
+  if (!f || !cloudsc_impl::fields_complete(f, outputs, cml != nullptr) || ngptot <= 0 || nproma <= 0 || klev < 2)
+    return CLOUDSC_EINVAL;
   const bool aer = params->laericesed || params->laericeauto;
   if (aer && (!f->pre_ice || !f->picrit_aer || !f->pnice)) return CLOUDSC_EINVAL;
   if (nthreads <= 0 && (thread_seconds || thread_blocks || thread_columns)) return CLOUDSC_EINVAL;
   const DevParams<double> c = fold_params<double>(*params);
-  KArgsTB<double, S> A;
+  KArgsCML<double, S> A;
   static_cast<KArgs<double, S>&>(A) = make_kargs<double, S>(f, ngptot, nproma, klev, nullptr);
   A.tend_planes = tend_planes;   // 0: separate arrays
+  A.cml_t = A.cml_q = A.cml_a = A.cml_cld = nullptr;
+  if (cml) { A.cml_t = (S*)cml->t; A.cml_q = (S*)cml->q; A.cml_a = (S*)cml->a; A.cml_cld = (S*)cml->cld; }
   const int nblocks = ngptot / nproma + (ngptot % nproma ? 1 : 0);
   if (nthreads <= 0) nthreads = (int)std::max(1u, std::thread::hardware_concurrency());
   const int nreq = nthreads;                 // the caller's per-thread arrays have nreq entries
@@ -133,7 +144,13 @@ int cpu_run(int nthreads, int ngptot, int nproma, int klev, const cloudsc_params
     std::vector<HostColumn<double>> col((size_t)nproma);
     int icalls = 0, igpc = 0;
     for (int b = next.fetch_add(1); b < nblocks; b = next.fetch_add(1)) {
-      if (outputs == CLOUDSC_OUTPUTS_SURFACE && tend_planes) {
+      if (cml && outputs == CLOUDSC_OUTPUTS_SURFACE) {
+        if (aer) run_block<double, true, true, true, true, true>(c, A, b, col);
+        else run_block<double, false, true, true, true, true>(c, A, b, col);
+      } else if (cml) {
+        if (aer) run_block<double, true, true, true, false, true>(c, A, b, col);
+        else run_block<double, false, true, true, false, true>(c, A, b, col);
+      } else if (outputs == CLOUDSC_OUTPUTS_SURFACE && tend_planes) {
         if (aer) run_block<double, true, true, true, true>(c, A, b, col);
         else run_block<double, false, true, true, true>(c, A, b, col);
       } else if (outputs == CLOUDSC_OUTPUTS_SURFACE) {
@@ -245,6 +262,24 @@ extern "C" int cloudsc_cpu_run_tendbuf_outputs(int nthreads, int precision, int 
     case sizeof(float):
       return cpu_run<float>(nthreads, ngptot, nproma, klev, params, f, nullptr, nullptr, nullptr, nullptr, tend_planes,
                             outputs);
+    default: return CLOUDSC_EINVAL;
+  }
+}
+
+extern "C" int cloudsc_cpu_run_tendbuf_cml(int nthreads, int precision, int outputs, int ngptot, int nproma, int klev,
+                                           int tend_planes, const cloudsc_params_t* params, const cloudsc_fields_t* f,
+                                           const cloudsc_tend_cml_t* cml) {
+  if (outputs != CLOUDSC_OUTPUTS_PROGNOSTIC && outputs != CLOUDSC_OUTPUTS_SURFACE) return CLOUDSC_EINVAL;   // not ALL
+  if (tend_planes < CLOUDSC_TENDBUF_PLANES_MIN || tend_planes > CLOUDSC_TENDBUF_PLANES_MAX) return CLOUDSC_EINVAL;
+  if (!cloudsc_impl::precision_computes_double(precision)) return CLOUDSC_EINVAL;   // as cloudsc_cpu_run_precision
+  if (cloudsc_impl::check_tend_cml(f, cml)) return CLOUDSC_EINVAL;
+  switch (cloudsc_impl::precision_storage_bytes(precision)) {
+    case sizeof(double):
+      return cpu_run<double>(nthreads, ngptot, nproma, klev, params, f, nullptr, nullptr, nullptr, nullptr, tend_planes,
+                             outputs, cml);
+    case sizeof(float):
+      return cpu_run<float>(nthreads, ngptot, nproma, klev, params, f, nullptr, nullptr, nullptr, nullptr, tend_planes,
+                            outputs, cml);
     default: return CLOUDSC_EINVAL;
   }
 }

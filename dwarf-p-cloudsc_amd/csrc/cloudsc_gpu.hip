@@ -133,11 +133,23 @@ const ParamSet* device_default_params(int device) {
   return g_default[device].dev ? &g_default[device] : nullptr;
 }
 
-bool fields_complete(const cloudsc_fields_t* f, int outputs) {
+bool fields_complete(const cloudsc_fields_t* f, int outputs, bool cml) {
   const void* const* p = (const void* const*)f;
   for (int m = 0; m < kNumFields; m++)
-    if (!p[m] && kFieldTable[m].dir != CLOUDSC_FD_AEROSOL && output_selected(m, outputs)) return false;
+    if (!p[m] && kFieldTable[m].dir != CLOUDSC_FD_AEROSOL && output_selected(m, outputs) && !(cml && is_tendency_loc(m)))
+      return false;
   return true;
+}
+
+int check_tend_cml(const cloudsc_fields_t* f, const cloudsc_tend_cml_t* cml) {
+  if (!f || !cml || !cml->t || !cml->q || !cml->a || !cml->cld) return CLOUDSC_EINVAL;
+  const void* const mine[4] = {cml->t, cml->q, cml->a, cml->cld};
+  const void* const theirs[8] = {f->tendency_tmp_t,   f->tendency_tmp_q, f->tendency_tmp_a, f->tendency_tmp_cld,
+                                 f->tendency_loc_t,   f->tendency_loc_q, f->tendency_loc_a, f->tendency_loc_cld};
+  for (const void* a : mine)
+    for (const void* b : theirs)
+      if (a == b) return CLOUDSC_EINVAL;
+  return CLOUDSC_OK;
 }
 
 }  // namespace cloudsc_impl
@@ -176,6 +188,9 @@ __device__ __forceinline__ cptr<typename F::params> params_of(cptr<typename F::f
 //   F::surf  the surface-fluxes form (CLOUDSC_OUTPUTS_SURFACE): F::prog, and the
 //            members pfplsl, pfplsn, pfhpsl, pfhpsn point at [nblocks][nproma]
 //            surface fields, written once after the last level;
+//   F::cml   the cumulative tendency form (cloudsc_gpu_run_tendbuf_cml): F::tb and
+//            F::prog, the first argument a KArgsCML, the four BUFFER_CML plane starts
+//            behind tend_planes; the tendency_loc_* members are never read;
 //   F::pack  narrow blocks (NPROMA <= 32) packed into full waves: a workgroup
 //            is one wave that walks PackArgs::pack consecutive blocks.
 // A kernel has exactly the arguments its form needs: Pack is PackArgs for
@@ -279,15 +294,18 @@ int dispatch_bools(Fn&& f, bool c, Rest... rest) {
 // kFormProg and kFormSurf) has a kernel.  MIXED runs on the k-caching variants only; so do the tendency buffer
 // and the prognostic-outputs forms, alone or combined, which fp32 has with its default
 // exp/pow only; the surface-fluxes form is a prognostic-outputs form (kFormSurf without kFormProg
-// does not exist); the SCC variants are plain.  (The exact-libm bit means nothing outside fp32;
-// every k-caching kernel has its packed twin, so kFormPack is not asked about.)
+// does not exist); the cumulative tendency form is a tendency buffer, prognostic-outputs form, with or
+// without kFormSurf (kFormCml without both does not exist); the SCC variants are plain.  (The exact-libm
+// bit means nothing outside fp32; every k-caching kernel has its packed twin, so kFormPack is not asked about.)
 constexpr bool form_exists(int kind, int precision, bool exact_libm, unsigned form) {
   const bool tb = (form & kFormTb) != 0, prog = (form & kFormProg) != 0, surf = (form & kFormSurf) != 0;
+  const bool cml = (form & kFormCml) != 0;
   const bool kcaching = kind == CLOUDSC_VARIANT_KCACHE || kind == CLOUDSC_VARIANT_KSEG;
   if (!kcaching && kind != CLOUDSC_VARIANT_SCC && kind != CLOUDSC_VARIANT_SCC_PRIVATE) return false;
   if (precision != CLOUDSC_FP64 && precision != CLOUDSC_FP32 && precision != CLOUDSC_MIXED) return false;
   if (precision == CLOUDSC_MIXED && !kcaching) return false;
   if (surf && !prog) return false;
+  if (cml && !(tb && prog)) return false;
   if (tb || prog) return kcaching && !(precision == CLOUDSC_FP32 && exact_libm);
   return true;
 }
@@ -302,7 +320,7 @@ constexpr int kPrecisionOf = !std::is_same<real, S>::value ? CLOUDSC_MIXED : siz
 template <typename real, typename S, bool FAST>
 constexpr bool kernel_kept(int kind, bool aer, unsigned form = 0u) {
 #ifdef CLOUDSC_ONLY_KSEG
-  if (kind != CLOUDSC_VARIANT_KSEG || aer || (form & (kFormTb | kFormProg | kFormSurf)) || sizeof(real) != CLOUDSC_ONLY_KSEG ||
+  if (kind != CLOUDSC_VARIANT_KSEG || aer || (form & (kFormTb | kFormProg | kFormSurf | kFormCml)) || sizeof(real) != CLOUDSC_ONLY_KSEG ||
       sizeof(S) != CLOUDSC_ONLY_KSEG)
     return false;
 #endif
@@ -323,7 +341,7 @@ struct LaunchForm {
   using product = cfg<DefaultCfg<real>::waves, DefaultCfg<real>::pf, false>;
 };
 constexpr bool cfg_table_applies(int kind, unsigned form) {
-  return !(form & (kFormTb | kFormProg | kFormSurf)) && (kind == CLOUDSC_VARIANT_KSEG || !(form & kFormPack));
+  return !(form & (kFormTb | kFormProg | kFormSurf | kFormCml)) && (kind == CLOUDSC_VARIANT_KSEG || !(form & kFormPack));
 }
 template <typename LF, bool TABLE, typename Fn>
 int with_cfg(Fn&& f) {
@@ -341,16 +359,21 @@ int with_cfg(Fn&& f) {
   return f(typename LF::product{});
 }
 
-// the kernel arguments of a launch: a's, with tend_planes behind them in the tendency buffer form
+// the kernel arguments of a launch: a's, with tend_planes behind them in the tendency buffer form and the
+// BUFFER_CML plane starts behind that in the cumulative tendency form
 template <typename F>
-typename F::kargs kernel_args(const typename F::fields& a, int tend_planes) {
+typename F::kargs kernel_args(const typename F::fields& a, int tend_planes, const cloudsc_tend_cml_t* cml) {
   if constexpr (F::tb) {
     typename F::kargs t;
     static_cast<typename F::fields&>(t) = a;
     t.tend_planes = tend_planes;
+    if constexpr (F::cml) {
+      using S = typename F::store;
+      t.cml_t = (S*)cml->t; t.cml_q = (S*)cml->q; t.cml_a = (S*)cml->a; t.cml_cld = (S*)cml->cld;
+    }
     return t;
   } else {
-    (void)tend_planes;
+    (void)tend_planes; (void)cml;
     return a;
   }
 }
@@ -548,10 +571,12 @@ int launch_kseg_cfg(hipStream_t st, const typename F::kargs& a, const PersistArg
 template <typename real, bool FAST, typename ST = real>
 int launch_v(hipStream_t st, int variant, const cloudsc_fields_t* f, int ngptot, int nproma, int klev,
              void* scratch, const void* plude_in, const ParamSet& ps, KsegEpoch* ep, const LaunchEvents* ev,
-             int tend_planes, int outputs) {
-  // tend_planes != 0: the tendency buffer form; the selection's bits: the prognostic-outputs and surface-fluxes forms
+             int tend_planes, int outputs, const cloudsc_tend_cml_t* cml) {
+  // tend_planes != 0: the tendency buffer form; the selection's bits: the prognostic-outputs and surface-fluxes forms;
+  // cml: the cumulative tendency form
   const bool aer = ps.aer, tb = tend_planes != 0, prog = outputs_prognostic(outputs), surf = outputs_surface(outputs);
-  if (!kernel_kept<real, ST, FAST>(variant, aer, (tb ? kFormTb : 0u) | (prog ? kFormProg : 0u) | (surf ? kFormSurf : 0u)))
+  if (!kernel_kept<real, ST, FAST>(variant, aer, (tb ? kFormTb : 0u) | (prog ? kFormProg : 0u) | (surf ? kFormSurf : 0u) |
+                                                     (cml ? kFormCml : 0u)))
     return CLOUDSC_EINVAL;
   KArgs<real, ST> a = make_kargs<real, ST>(
       f, ngptot, nproma, klev, (const DevParams<real>*)((const char*)ps.dev + (sizeof(real) == 8 ? 0 : kSpOffset)));
@@ -569,20 +594,20 @@ int launch_v(hipStream_t st, int variant, const cloudsc_fields_t* f, int ngptot,
   // conditions become F's members here, and only kernels that exist are instantiated
   const auto with_form = [&](auto kind, auto&& go) {
     return dispatch_bools(
-        [&](auto AER, auto PACK, auto TB, auto PROG, auto SURF) {
-          constexpr unsigned form =
-              (PACK ? kFormPack : 0u) | (TB ? kFormTb : 0u) | (PROG ? kFormProg : 0u) | (SURF ? kFormSurf : 0u);
+        [&](auto AER, auto PACK, auto TB, auto PROG, auto SURF, auto CML) {
+          constexpr unsigned form = (PACK ? kFormPack : 0u) | (TB ? kFormTb : 0u) | (PROG ? kFormProg : 0u) |
+                                    (SURF ? kFormSurf : 0u) | (CML ? kFormCml : 0u);
           if constexpr (kernel_kept<real, ST, FAST>(kind, AER, form))
             return with_cfg<LaunchForm<real, ST, AER, FAST, form>, cfg_table_applies(kind, form)>(go);
           else
             return (int)CLOUDSC_EINVAL;
         },
-        aer, pack > 1, tb, prog, surf);
+        aer, pack > 1, tb, prog, surf, cml != nullptr);
   };
   if (variant == CLOUDSC_VARIANT_KCACHE) {
     rc = with_form(std::integral_constant<int, CLOUDSC_VARIANT_KCACHE>{}, [&](auto form) {
       using F = decltype(form);
-      return launch_kcache<F>(st, kernel_args<F>(a, tend_planes), nblocks, nproma, pk, ev);
+      return launch_kcache<F>(st, kernel_args<F>(a, tend_planes, cml), nblocks, nproma, pk, ev);
     });
   } else if (variant == CLOUDSC_VARIANT_KSEG) {
     if (!scratch) return CLOUDSC_EINVAL;
@@ -638,7 +663,7 @@ int launch_v(hipStream_t st, int variant, const cloudsc_fields_t* f, int ngptot,
     int grid = 0;
     rc = with_form(std::integral_constant<int, CLOUDSC_VARIANT_KSEG>{}, [&](auto form) {
       using F = decltype(form);
-      return launch_kseg_cfg<F>(st, kernel_args<F>(a, tend_planes), pa, nproma, pa.nitems, &grid, ev, pk);
+      return launch_kseg_cfg<F>(st, kernel_args<F>(a, tend_planes, cml), pa, nproma, pa.nitems, &grid, ev, pk);
     });
     if (rc) return rc;
     HIPCHK(hipGetLastError());
@@ -683,32 +708,33 @@ int launch_v(hipStream_t st, int variant, const cloudsc_fields_t* f, int ngptot,
 template <typename real>
 int launch(hipStream_t st, int variant, bool exact_libm, const cloudsc_fields_t* f, int ngptot, int nproma,
            int klev, void* scratch, const void* plude_in, const ParamSet& ps, KsegEpoch* ep, const LaunchEvents* ev,
-           int tend_planes, int outputs) {
+           int tend_planes, int outputs, const cloudsc_tend_cml_t* cml) {
   if constexpr (std::is_same<real, float>::value) {
     if (!exact_libm)
       return launch_v<real, true>(st, variant, f, ngptot, nproma, klev, scratch, plude_in, ps, ep, ev, tend_planes,
-                                  outputs);
+                                  outputs, cml);
   }
   (void)exact_libm;
   return launch_v<real, false>(st, variant, f, ngptot, nproma, klev, scratch, plude_in, ps, ep, ev, tend_planes,
-                               outputs);
+                               outputs, cml);
 }
 
 // The launch of a precision code.  CLOUDSC_MIXED is the fp64 launch (exp/pow,
 // parameter mirror, configuration, workspace) over float fields.
 int launch_precision(int precision, hipStream_t st, int variant, bool exact_libm, const cloudsc_fields_t* f,
                      int ngptot, int nproma, int klev, void* scratch, const void* plude_in, const ParamSet& ps,
-                     KsegEpoch* ep, const LaunchEvents* ev, int tend_planes, int outputs) {
+                     KsegEpoch* ep, const LaunchEvents* ev, int tend_planes, int outputs,
+                     const cloudsc_tend_cml_t* cml) {
   switch (precision) {
     case CLOUDSC_FP64:
       return launch<double>(st, variant, exact_libm, f, ngptot, nproma, klev, scratch, plude_in, ps, ep, ev, tend_planes,
-                            outputs);
+                            outputs, cml);
     case CLOUDSC_FP32:
       return launch<float>(st, variant, exact_libm, f, ngptot, nproma, klev, scratch, plude_in, ps, ep, ev, tend_planes,
-                           outputs);
+                           outputs, cml);
     case CLOUDSC_MIXED:
       return launch_v<double, false, float>(st, variant, f, ngptot, nproma, klev, scratch, plude_in, ps, ep, ev,
-                                            tend_planes, outputs);
+                                            tend_planes, outputs, cml);
     default: return CLOUDSC_EINVAL;
   }
 }
@@ -789,7 +815,7 @@ int validate_run_args(int device, int precision, int variant, int ngptot, int np
 // ps: the parameter set of the launch (NULL = the device's default set).
 int gpu_run_impl(int device, void* stream, int precision, int variant, int ngptot, int nproma, int klev,
                  const cloudsc_fields_t* f, void* scratch, const void* plude_in, const ParamSet* ps,
-                 KsegEpoch* ep, const LaunchEvents* lev, int tend_planes, int outputs) {
+                 KsegEpoch* ep, const LaunchEvents* lev, int tend_planes, int outputs, const cloudsc_tend_cml_t* cml) {
   // unknown option bits are an argument error here, before they are stripped (validate_run_args below sees
   // the variant's kind only): such a call must never launch
   if (variant & ~(0xff | CLOUDSC_FP32_EXACT_LIBM)) return CLOUDSC_EINVAL;
@@ -800,11 +826,11 @@ int gpu_run_impl(int device, void* stream, int precision, int variant, int ngpto
   if (!ps) ps = device_default_params(device);
   if (!ps || !ps->dev) return CLOUDSC_ENOINIT;
   if (ps->device != device) return CLOUDSC_EINVAL;
-  if (!f || !fields_complete(f, outputs)) return CLOUDSC_EINVAL;
+  if (!f || !fields_complete(f, outputs, cml != nullptr)) return CLOUDSC_EINVAL;
   HIPCHK(hipSetDevice(device));
   hipStream_t st = (hipStream_t)stream;
   return launch_precision(precision, st, variant, exact_libm, f, ngptot, nproma, klev, scratch, plude_in, *ps, ep, lev,
-                          tend_planes, outputs);
+                          tend_planes, outputs, cml);
 }
 
 int kseg_clock(int device, void* stream, void* scratch, bool reset, double* ghz, double* seconds) {
@@ -914,6 +940,36 @@ int cloudsc_gpu_run_tendbuf_outputs(int device, void* stream, int precision, int
   if (!f || !fields_complete(f, outputs) || (kind == CLOUDSC_VARIANT_KSEG && !scratch)) return CLOUDSC_EINVAL;
   return gpu_run_impl(device, stream, precision, variant, ngptot, nproma, klev, f, scratch, nullptr, nullptr, nullptr,
                       nullptr, tend_planes, outputs);
+}
+
+int cloudsc_tendbuf_bind_cml(cloudsc_tend_cml_t* cml, int precision, int nproma, int klev, void* buffer_cml) {
+  const size_t eb = precision_storage_bytes(precision);
+  if (!cml || !eb || nproma < 1 || klev < 1 || !buffer_cml) return CLOUDSC_EINVAL;
+  const size_t plane = (size_t)klev * (size_t)nproma * eb;
+  char* b = (char*)buffer_cml;
+  cml->t = b + CLOUDSC_TENDBUF_T * plane;
+  cml->a = b + CLOUDSC_TENDBUF_A * plane;
+  cml->q = b + CLOUDSC_TENDBUF_Q * plane;
+  cml->cld = b + CLOUDSC_TENDBUF_CLD * plane;
+  return CLOUDSC_OK;
+}
+
+int cloudsc_gpu_run_tendbuf_cml(int device, void* stream, int precision, int variant, int outputs, int ngptot,
+                                int nproma, int klev, int tend_planes, const cloudsc_fields_t* f,
+                                const cloudsc_tend_cml_t* cml, void* scratch) {
+  // every argument rule first, the device's among them last: no HIP call before an argument error
+  if (outputs != CLOUDSC_OUTPUTS_PROGNOSTIC && outputs != CLOUDSC_OUTPUTS_SURFACE) return CLOUDSC_EINVAL;   // not ALL
+  if (tend_planes < CLOUDSC_TENDBUF_PLANES_MIN || tend_planes > CLOUDSC_TENDBUF_PLANES_MAX) return CLOUDSC_EINVAL;
+  if (variant & ~0xff) return CLOUDSC_EINVAL;   // no option bits (so no fp32 exact-libm)
+  const int kind = variant_kind(variant);
+  const int rc = validate_shape_args(precision, kind, ngptot, nproma, klev);
+  if (rc) return rc;
+  const unsigned form = kFormCml | kFormTb | kFormProg | (outputs_surface(outputs) ? kFormSurf : 0u);
+  if (!form_exists(kind, precision, /*exact_libm=*/false, form)) return CLOUDSC_EINVAL;   // no SCC form
+  if (!f || !fields_complete(f, outputs, /*cml=*/true) || (kind == CLOUDSC_VARIANT_KSEG && !scratch)) return CLOUDSC_EINVAL;
+  if (check_tend_cml(f, cml)) return CLOUDSC_EINVAL;
+  return gpu_run_impl(device, stream, precision, variant, ngptot, nproma, klev, f, scratch, nullptr, nullptr, nullptr,
+                      nullptr, tend_planes, outputs, cml);
 }
 
 int cloudsc_gpu_check(int device, void* stream, int variant, void* scratch) {

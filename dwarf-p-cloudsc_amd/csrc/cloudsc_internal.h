@@ -98,9 +98,14 @@ constexpr int field_kind_of(int member, int outputs) {
 constexpr bool output_selected(int member, int outputs) {
   return !outputs_prognostic(outputs) || !is_flux_diagnostic(member);
 }
-// every pointer the kernel reads or writes (aerosol inputs and, with CLOUDSC_OUTPUTS_PROGNOSTIC, the ten
-// diagnostic fluxes excepted) is set
-bool fields_complete(const cloudsc_fields_t* f, int outputs = CLOUDSC_OUTPUTS_ALL);
+// The four local tendency members (consecutive): the cumulative tendency form never touches them
+constexpr bool is_tendency_loc(int member) { return member >= CLOUDSC_M_tendency_loc_t && member <= CLOUDSC_M_tendency_loc_cld; }
+// every pointer the kernel reads or writes (aerosol inputs, with CLOUDSC_OUTPUTS_PROGNOSTIC the ten
+// diagnostic fluxes and, in the cumulative tendency form `cml`, tendency_loc_t/q/a/cld excepted) is set
+bool fields_complete(const cloudsc_fields_t* f, int outputs = CLOUDSC_OUTPUTS_ALL, bool cml = false);
+// the pointer rules of a cumulative tendency form's planes: cml and its four members set, none of them a
+// tendency_tmp_* or tendency_loc_* member of f (pointer equality only)
+int check_tend_cml(const cloudsc_fields_t* f, const cloudsc_tend_cml_t* cml);
 // Host record of one KSEG workspace owned by a caller that launches on it in
 // stream order (a state): after the first launch zeroes it, later launches
 // continue its ticket counter and flag stamps instead of zeroing it again.
@@ -119,11 +124,11 @@ struct LaunchEvents {
 // KSEG workspace record (NULL = zero the workspace before every KSEG launch)
 // and optional events timing the physics kernel (NULL = none); tend_planes != 0:
 // the tendency members of f are planes of packed buffers (cloudsc_gpu_run_tendbuf); outputs: CLOUDSC_OUTPUTS_*
-// (cloudsc_gpu_run_outputs)
+// (cloudsc_gpu_run_outputs); cml: the cumulative tendency form (cloudsc_gpu_run_tendbuf_cml)
 int gpu_run_impl(int device, void* stream, int precision, int variant, int ngptot, int nproma, int klev,
                  const cloudsc_fields_t* f, void* scratch, const void* plude_in, const ParamSet* ps,
                  KsegEpoch* ep = nullptr, const LaunchEvents* lev = nullptr, int tend_planes = 0,
-                 int outputs = CLOUDSC_OUTPUTS_ALL);
+                 int outputs = CLOUDSC_OUTPUTS_ALL, const cloudsc_tend_cml_t* cml = nullptr);
 // the kernel variant of a `variant` argument without its option bits (CLOUDSC_FP32_EXACT_LIBM)
 inline int variant_kind(int variant) { return variant & 0xff; }
 // waits for `stream` and returns CLOUDSC_EHANDOFF if the last KSEG launch on

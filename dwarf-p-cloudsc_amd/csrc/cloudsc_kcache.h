@@ -59,6 +59,15 @@ template <typename real, typename store = real>
 struct KArgsTB : KArgs<real, store> {
   int tend_planes;
 };
+// The kernel arguments of the "cumulative tendency" form (CML, cloudsc_gpu_run_tendbuf_cml): KArgsTB,
+// and the plane starts in block 0 of a third buffer of the same shape and block stride (the Fortran
+// drivers' BUFFER_CML), to which the step adds its seven local tendencies (T, Q, A, CLD ql/qi/qr/qs)
+// instead of storing them: tlt, tlq, tla and tlcld are never touched (they may be NULL), and the fifth
+// (vapour) plane behind cml_cld is neither read nor written.
+template <typename real, typename store = real>
+struct KArgsCML : KArgsTB<real, store> {
+  store *cml_t, *cml_q, *cml_a, *cml_cld;
+};
 
 // One k-caching kernel, described at compile time: the compute and storage
 // types, the configuration (occupancy target WAVES, load schedule PF, aerosol
@@ -69,9 +78,10 @@ struct KArgsTB : KArgs<real, store> {
 //   kFormProg  the prognostic-outputs form (flux_level)
 //   kFormSurf  the surface-fluxes form (flux_surface): kFormProg, and pfplsl, pfplsn, pfhpsl, pfhpsn
 //              stored once, after the last level, as surface fields
+//   kFormCml   the cumulative tendency form (KArgsCML, load_cml, store_level_cml): kFormTb and kFormProg
 // The kernel entries, the bodies below and the host's launch path all take the
 // descriptor and read its members by name.
-enum : unsigned { kFormPack = 1u, kFormTb = 2u, kFormProg = 4u, kFormSurf = 8u };
+enum : unsigned { kFormPack = 1u, kFormTb = 2u, kFormProg = 4u, kFormSurf = 8u, kFormCml = 16u };
 template <typename Real, typename Store, int WAVES, int PF, bool AER, bool LDSC, bool FAST, unsigned FORM = 0u>
 struct KForm {
   using real = Real;
@@ -79,10 +89,13 @@ struct KForm {
   static constexpr int waves = WAVES, pf = PF;
   static constexpr bool aer = AER, ldsc = LDSC, fast = FAST;
   static constexpr bool pack = (FORM & kFormPack) != 0, tb = (FORM & kFormTb) != 0, prog = (FORM & kFormProg) != 0;
-  static constexpr bool surf = (FORM & kFormSurf) != 0;
+  static constexpr bool surf = (FORM & kFormSurf) != 0, cml = (FORM & kFormCml) != 0;
   static_assert(!surf || prog, "the surface-fluxes form is a prognostic-outputs form");
+  static_assert(!cml || (tb && prog), "the cumulative tendency form is a tendency buffer, prognostic-outputs form");
   using fields = KArgs<real, store>;   // what the bodies read: the kernel arguments, or their base in the TB form
-  using kargs = typename std::conditional<tb, KArgsTB<real, store>, fields>::type;   // the kernel's first argument
+  // the kernel's first argument
+  using kargs = typename std::conditional<cml, KArgsCML<real, store>,
+                                          typename std::conditional<tb, KArgsTB<real, store>, fields>::type>::type;
   using params = DevParamsT<real, fast>;                                              // the parameter block
 };
 
@@ -226,6 +239,30 @@ CLOUDSC_HD int tend_planes_of(const KArgs<real, S>& A) {
 CLOUDSC_HD unsigned lo_tend(unsigned lo, int) { return lo; }      // [nblocks][tend_planes][klev][nproma]
 CLOUDSC_HD unsigned lo_tend(const PackLo& p, int tend_planes) {
   return p.sb * (unsigned)(tend_planes * p.klev) + p.jb;
+}
+template <typename real, typename S>
+CLOUDSC_HD const KArgsCML<real, S>& cml_args_of(const KArgs<real, S>& A) {
+  return static_cast<const KArgsCML<real, S>&>(A);
+}
+
+// The cumulative tendency form (CML): the seven elements of BUFFER_CML that level k of one column
+// adds to, at the indices store_level forms for the local tendencies (TB); store_level_cml stores the sums.  Read once: streaming
+// loads.  Where in the level they are issued is CLOUDSC_CML_AT (kcache_levels).
+template <typename real>
+struct CmlIn {
+  real t, q, a, cld[4];
+};
+struct NoCml {};   // what the other forms have in its place
+template <typename real, typename S, typename LO>
+CLOUDSC_HD void load_cml(CmlIn<real>& C, const KArgs<real, S>& A, size_t u2, int k, int klev, int nproma, LO lane) {
+  const KArgsCML<real, S>& M = cml_args_of(A);
+  const int tp = M.tend_planes;
+  const size_t t3 = u2 * (size_t)tp, it = t3 + (size_t)k * nproma;
+  const unsigned lot = lo_tend(lane, tp);
+  C.t = ldg1(M.cml_t, it, lot); C.q = ldg1(M.cml_q, it, lot); C.a = ldg1(M.cml_a, it, lot);
+#pragma unroll
+  for (int m = 0; m < 4; m++)
+    C.cld[m] = ldg1_sp<kSpOpaque<real, S>>(M.cml_cld, t3 + ((size_t)m * klev + k) * nproma, lot);
 }
 
 // Per-level inputs of one column (the prefetch unit).
@@ -1278,6 +1315,30 @@ CLOUDSC_HD void store_level(const KArgs<real, S>& A, size_t u2, size_t u3, int k
   stg_sp<kSpOpaque<real, S>>(A.tlcld, t3 + ((size_t)4 * klev + k) * nproma, lsp, R(0.0));
 }
 
+// store_level of the cumulative tendency form (CML, always with TB).  The seven local tendencies are
+// not stored: each is added to the element of BUFFER_CML that load_cml read for it (`cm`) -- one add in
+// `real`, its own rounding (-ffp-contract=off), narrowed by the store where the fields are float under
+// double -- and the sum stored there with the outputs' write-through policy.  tlt, tlq, tla and tlcld
+// are not touched; the vapour plane of CML, whose local tendency is identically zero, neither.
+template <typename real, typename S, typename LO>
+CLOUDSC_HD void store_level_cml(const KArgs<real, S>& A, size_t u2, int k, int klev, int nproma, LO lane,
+                                const LevelState<real>& ls, const PhysOut<real>& po, const CmlIn<real>& cm) {
+  const KArgsCML<real, S>& M = cml_args_of(A);
+  const size_t i = u2 + (size_t)k * nproma;
+  const unsigned lo = lo_full(lane);
+  const int tp = M.tend_planes;
+  const size_t t3 = u2 * (size_t)tp, it = t3 + (size_t)k * nproma;
+  const unsigned lot = lo_tend(lane, tp);
+  stg(M.cml_t, it, lot, cm.t + ls.ttend);
+  stg(M.cml_q, it, lot, cm.q + ls.qtend);
+  stg(M.cml_a, it, lot, cm.a + po.atend);
+  stg(A.pcovptot, i, lo, po.zcovptot_out);
+  stg(A.plude, i, lo, po.plude_k);   // as store_level
+#pragma unroll
+  for (int m = 0; m < 4; m++)
+    stg_sp<kSpOpaque<real, S>>(M.cml_cld, t3 + ((size_t)m * klev + k) * nproma, lot, cm.cld[m] + po.ctend[m]);
+}
+
 template <typename real, bool PROG = false, typename CS>
 CLOUDSC_HD void init_carry(CS& cs) {
   cs.t_prev = cs.a_prev = cs.pap_prev = R(0.0);
@@ -1308,7 +1369,18 @@ __device__ __forceinline__ const auto& params_here(const PV& pv, cptr<PT> cpar) 
 //
 // F: the kernel's descriptor (KForm).  F::tb: the tendency buffer form (`ka`
 // then points at a KArgsTB); F::prog: the prognostic-outputs form (flux_level); F::surf: the
-// surface-fluxes form (flux_level stores nothing; the caller stores the surface row, flux_surface).
+// surface-fluxes form (flux_level stores nothing; the caller stores the surface row, flux_surface);
+// F::cml: the cumulative tendency form (`ka` points at a KArgsCML; load_cml, store_level_cml).
+//
+// Where F::cml issues the seven BUFFER_CML loads of level k (CLOUDSC_CML_AT): 2 = at the top of the
+// level, behind the level's own loads; 1 = in the middle of the level (the physics' mid hook), ahead
+// of the next level's early inputs; 0 = just before the stores that consume them.  The product is
+// the earliest that leaves every kernel of the form without scratch and without VGPR spills at two
+// waves per SIMD (profiles/tendbuf_cml/kernel_resources.txt); experiment builds override it
+// (make variant VFLAGS=-DCLOUDSC_CML_AT=n).
+#ifndef CLOUDSC_CML_AT
+#define CLOUDSC_CML_AT 2
+#endif
 template <typename F, typename CS, typename LO>
 __device__ __forceinline__ void kcache_levels(cptr<typename F::fields> ka, cptr<typename F::params> cpar, int b,
                                               LO lo0, int lev0, int lev1, CS& cs) {
@@ -1394,6 +1466,7 @@ __device__ __forceinline__ void kcache_levels(cptr<typename F::fields> ka, cptr<
     const bool physics = k >= ncldtop0;
     // ---- issue the loads of the next levels (software pipelining) ----
     real paph_nn, pmfu_nn, pmfd_nn, plu_nn;
+    typename std::conditional<F::cml, CmlIn<real>, NoCml>::type cm;   // F::cml: this level's elements of BUFFER_CML
     {
       const KArgs<real, S>& A = *(const KArgs<real, S>*)launder_uniform(ka);
       // indices clamped instead of branched: the last levels re-read valid data
@@ -1421,6 +1494,7 @@ __device__ __forceinline__ void kcache_levels(cptr<typename F::fields> ka, cptr<
         const size_t i2 = u2 + (size_t)k2 * nproma;
         pmfu_nn = ldg1(A.pmfu, i2, lo_full(lo)); pmfd_nn = ldg1(A.pmfd, i2, lo_full(lo)); plu_nn = ldg1(A.plu, i2, lo_full(lo));
       }
+      if constexpr (F::cml && CLOUDSC_CML_AT == 2) load_cml(cm, A, u2, k, klev, nproma, lo);
     }
 
     LevelState<real> ls;
@@ -1436,6 +1510,8 @@ __device__ __forceinline__ void kcache_levels(cptr<typename F::fields> ka, cptr<
       // PF 3: the next level's early inputs, issued in the middle of this level
       // (clamped at the last level: a re-read of valid data, never consumed)
       const auto mid = [&]() {
+        if constexpr (F::cml && CLOUDSC_CML_AT == 1)
+          load_cml(cm, *(const KArgs<real, S>*)launder_uniform(ka), u2, k, klev, nproma, launder_vgpr(lo0));
         if (PFM || PFA) {
           const int k1 = k + 1 < klev ? k + 1 : klev - 1;
           if (PFM)
@@ -1463,7 +1539,9 @@ __device__ __forceinline__ void kcache_levels(cptr<typename F::fields> ka, cptr<
       // (packed: a fresh copy as well, so that neither the top-of-level copy nor the
       // offsets formed from it stay live across the physics)
       const LO los = PVR || std::is_same<LO, PackLo>::value ? launder_vgpr(lo0) : lo;
-      store_level<F::tb>(A, u2, u3, k, klev, nproma, los, physics, ls, po);
+      if constexpr (F::cml && CLOUDSC_CML_AT == 0) load_cml(cm, A, u2, k, klev, nproma, los);
+      if constexpr (F::cml) store_level_cml(A, u2, k, klev, nproma, los, ls, po, cm);
+      else store_level<F::tb>(A, u2, u3, k, klev, nproma, los, physics, ls, po);
       flux_level<F::prog, F::surf>(c, A, uh + (size_t)(k + 1) * nproma, los, cur, ls, po, nb.paph_k, nb.paph_n, cs);
     }
 

@@ -58,7 +58,7 @@
 typedef struct {
   int numomp, ngptot, nproma, ngpus, precision, variant, reps, warmup;
   int transfer, chunk_blocks, nstreams, exact_libm;
-  int fields_caller;              /* --fields caller | tendbuf | tendbuf-inplace (1 | 2 | 3): caller-owned field sets */
+  int fields_caller;              /* --fields caller | tendbuf | tendbuf-inplace | tendbuf-cml (1 | 2 | 3 | 4): caller-owned field sets */
   int tend_planes;                /* --fields tendbuf: planes per block of the two tendency buffers (0: not tendbuf) */
   int outputs, outputs_given;     /* --outputs all|prognostic|surface: CLOUDSC_OUTPUTS_* */
   int place;                      /* placement search: 1 on, 0 off, -1 auto (on when reps > 1) */
@@ -75,6 +75,7 @@ typedef struct {
   int caller, place_on, aerosols; /* --fields caller; its placement search; aerosol inputs allocated */
   int tend_planes;                /* --fields tendbuf: the step runs on two packed tendency buffers of that many planes */
   int inplace;                    /* --fields tendbuf-inplace: fill, step and validation on the buffers themselves */
+  int cml;                        /* --fields tendbuf-cml: inplace, the step adding its tendencies to a zeroed BUFFER_CML (no BUFFER_LOC) */
   int outputs;                    /* --outputs: CLOUDSC_OUTPUTS_* */
   double energy_s;
   long long col_offset;
@@ -145,6 +146,9 @@ static void usage(const char *prog) {
           "  --fields tendbuf-inplace  tendbuf without the two conversions: cloudsc_fields_expand_tendbuf,\n"
           "                        cloudsc_gpu_run_tendbuf_outputs, cloudsc_fields_validate_tendbuf on BUFFER_LOC (the\n"
           "                        separate tendency arrays cloudsc_fields_alloc makes are never read or written)\n"
+          "  --fields tendbuf-cml  tendbuf-inplace without a BUFFER_LOC: cloudsc_gpu_run_tendbuf_cml adds the step's\n"
+          "                        tendencies to a zeroed third buffer (BUFFER_CML), whose planes are validated in\n"
+          "                        place; needs --outputs prognostic|surface\n"
           "  --tend-planes N       --fields tendbuf[-inplace]: planes per block of the two buffers, 8..64 (default 8)\n"
           "  --outputs all|prognostic  --fields caller|tendbuf|tendbuf-inplace: prognostic = a step without the ten\n"
           "                        diagnostic fluxes, which are not allocated, validated or printed (kseg, kcache)\n"
@@ -221,6 +225,7 @@ static int parse(int argc, char **argv, options_t *o) {
       else if (!strcmp(v, "caller")) o->fields_caller = 1;
       else if (!strcmp(v, "tendbuf")) o->fields_caller = 2;
       else if (!strcmp(v, "tendbuf-inplace")) o->fields_caller = 3;
+      else if (!strcmp(v, "tendbuf-cml")) o->fields_caller = 4;
       else { fprintf(stderr, "bad --fields %s\n", v); return -1; }
     }
     else if (!strcmp(a, "--tend-planes")) {
@@ -382,7 +387,11 @@ static void *hip_sym(const char *name) {
 }
 
 /* one step of a --fields caller | tendbuf shard on the field set f (tendbuf: its tendencies in the buffers) */
-static int caller_step(const shard_t *s, int variant, int klev, const cloudsc_fields_t *f, void *ws) {
+static int caller_step(const shard_t *s, int variant, int klev, const cloudsc_fields_t *f, void *ws,
+                       const cloudsc_tend_cml_t *cml) {
+  if (s->cml)                                            /* --fields tendbuf-cml */
+    return cloudsc_gpu_run_tendbuf_cml(s->device, NULL, s->precision, variant, s->outputs, s->ngptot, s->nproma, klev,
+                                       s->tend_planes, f, cml, ws);
   if (s->outputs != CLOUDSC_OUTPUTS_ALL || s->inplace)   /* --outputs prognostic, --fields tendbuf-inplace */
     return s->tend_planes
                ? cloudsc_gpu_run_tendbuf_outputs(s->device, NULL, s->precision, variant, s->outputs, s->ngptot,
@@ -409,7 +418,10 @@ static void shard_caller(shard_t *s) {
    * the tendency_tmp_* / tendency_loc_* members alone, of the separate arrays (sep) and of the buffers (buf) */
   const int tp = s->tend_planes, inplace = s->inplace, alloc_flags =
       (s->place_on ? 0 : CLOUDSC_PLACE_NONE) | (s->aerosols ? CLOUDSC_ALLOC_AEROSOLS : 0);
-  void *buf_tmp = NULL, *buf_loc = NULL;
+  void *buf_tmp = NULL, *buf_loc = NULL, *buf_cml = NULL;
+  size_t buf_bytes = 0;
+  cloudsc_tend_cml_t cml;
+  memset(&cml, 0, sizeof(cml));
   cloudsc_fields_t g, tmp_sep, tmp_buf, loc_sep, loc_buf;
   memset(&tmp_sep, 0, sizeof(tmp_sep)); memset(&tmp_buf, 0, sizeof(tmp_buf));
   memset(&loc_sep, 0, sizeof(loc_sep)); memset(&loc_buf, 0, sizeof(loc_buf));
@@ -429,8 +441,14 @@ static void shard_caller(shard_t *s) {
     const size_t es = s->precision == CLOUDSC_FP64 ? 8 : 4;
     const size_t nb = (size_t)(s->ngptot / s->nproma + (s->ngptot % s->nproma ? 1 : 0));
     const size_t bytes = nb * (size_t)tp * (size_t)klev * (size_t)s->nproma * es;
-    if (set_device(s->device) || dmalloc(&buf_tmp, bytes) || dmalloc(&buf_loc, bytes)) s->rc = CLOUDSC_ENOMEM;
-    if (!s->rc) s->rc = cloudsc_tendbuf_bind(&g, s->precision, s->nproma, klev, buf_tmp, buf_loc);
+    buf_bytes = bytes;
+    /* tendbuf-cml: BUFFER_CML in the place of BUFFER_LOC, which the caller does not have */
+    if (set_device(s->device) || dmalloc(&buf_tmp, bytes) || dmalloc(s->cml ? &buf_cml : &buf_loc, bytes)) s->rc = CLOUDSC_ENOMEM;
+    if (!s->rc) s->rc = cloudsc_tendbuf_bind(&g, s->precision, s->nproma, klev, buf_tmp, s->cml ? buf_cml : buf_loc);
+    if (!s->rc && s->cml) {
+      s->rc = cloudsc_tendbuf_bind_cml(&cml, s->precision, s->nproma, klev, buf_cml);
+      g.tendency_loc_t = g.tendency_loc_a = g.tendency_loc_q = g.tendency_loc_cld = NULL;   /* never touched */
+    }
     tmp_sep.tendency_tmp_t = f.tendency_tmp_t; tmp_sep.tendency_tmp_a = f.tendency_tmp_a;
     tmp_sep.tendency_tmp_q = f.tendency_tmp_q; tmp_sep.tendency_tmp_cld = f.tendency_tmp_cld;
     tmp_buf.tendency_tmp_t = g.tendency_tmp_t; tmp_buf.tendency_tmp_a = g.tendency_tmp_a;
@@ -452,7 +470,9 @@ static void shard_caller(shard_t *s) {
   /* plude is INOUT: expanded again before every step, outside the timing */
   for (int r = 0; r < s->warmup && !s->rc; r++) {
     if (r) s->rc = cloudsc_fields_expand(s->device, NULL, s->precision, s->ngptot, s->nproma, s->col_offset, s->tmpl, &plude);
-    if (!s->rc) s->rc = caller_step(s, variant, klev, &g, ws);
+    /* a launch adds once: BUFFER_CML is zeroed again before every step, outside the timing */
+    if (!s->rc && s->cml && dmemset(buf_cml, 0, buf_bytes)) s->rc = CLOUDSC_EHIP;
+    if (!s->rc) s->rc = caller_step(s, variant, klev, &g, ws, &cml);
     if (!s->rc) s->rc = cloudsc_gpu_check(s->device, NULL, s->variant, ws);
   }
   pthread_barrier_wait(s->barrier);
@@ -461,9 +481,10 @@ static void shard_caller(shard_t *s) {
   for (int r = 0; r < s->reps && !s->rc; r++) {
     if (r || s->warmup)
       s->rc = cloudsc_fields_expand(s->device, NULL, s->precision, s->ngptot, s->nproma, s->col_offset, s->tmpl, &plude);
+    if (!s->rc && s->cml && dmemset(buf_cml, 0, buf_bytes)) s->rc = CLOUDSC_EHIP;
     if (!s->rc) s->rc = cloudsc_gpu_check(s->device, NULL, CLOUDSC_VARIANT_KCACHE, NULL);   /* the expansion is done */
     const double k0 = now();
-    if (!s->rc) s->rc = caller_step(s, variant, klev, &g, ws);
+    if (!s->rc) s->rc = caller_step(s, variant, klev, &g, ws, &cml);
     if (!s->rc) s->rc = cloudsc_gpu_check(s->device, NULL, s->variant, ws);
     s->kernel_ms[r] = (float)(1e3 * (now() - k0));   /* launch to the check's return, on the host clock */
     timed += now() - k0;
@@ -481,6 +502,9 @@ static void shard_caller(shard_t *s) {
     CLOUDSC_FIELDS(VALID_MEMBER)
 #undef VALID_MEMBER
     cloudsc_reference_t ref = *s->ref;
+    if (s->cml) {   /* 0 + loc: the cumulative planes validate as tendency_loc_* (the untouched vapour plane as zeros) */
+      g.tendency_loc_t = cml.t; g.tendency_loc_a = cml.a; g.tendency_loc_q = cml.q; g.tendency_loc_cld = cml.cld;
+    }
     for (int id = 0; id < CLOUDSC_NVALID; id++)
       if (!((const void *const *)&f)[member[id]]) { ref.field[id] = NULL; s->skipped[id] = 1; }
     s->rc = cloudsc_fields_validate_tendbuf(s->device, NULL, s->precision, s->ngptot, s->nproma, klev, inplace ? tp : 0,
@@ -492,6 +516,7 @@ static void shard_caller(shard_t *s) {
   if (ws) dfree(ws);
   if (buf_tmp) dfree(buf_tmp);
   if (buf_loc) dfree(buf_loc);
+  if (buf_cml) dfree(buf_cml);
   cloudsc_fields_free(s->device, &f);
 }
 
@@ -738,7 +763,7 @@ int main(int argc, char **argv) {
     return rc ? EXIT_FAILURE : EXIT_SUCCESS;
   }
 
-  if (o.tend_planes && o.fields_caller != 2 && o.fields_caller != 3) {
+  if (o.tend_planes && o.fields_caller != 2 && o.fields_caller != 3 && o.fields_caller != 4) {
     fprintf(stderr, "dwarf-cloudsc-amd: --tend-planes goes with --fields tendbuf\n");
     cloudsc_io_free(&ds);
     return EXIT_FAILURE;
@@ -751,6 +776,16 @@ int main(int argc, char **argv) {
        (o.variant != CLOUDSC_VARIANT_KSEG && o.variant != CLOUDSC_VARIANT_KCACHE))) {
     fprintf(stderr, "dwarf-cloudsc-amd: --outputs goes with --fields caller|tendbuf|tendbuf-inplace and --variant "
                     "kseg|kcache (no --transfer, no --fp32-exact-libm)\n");
+    cloudsc_io_free(&ds);
+    return EXIT_FAILURE;
+  }
+  if (o.fields_caller == 4 && (!o.outputs_given || o.outputs == CLOUDSC_OUTPUTS_ALL)) {
+    fprintf(stderr, "dwarf-cloudsc-amd: --fields tendbuf-cml needs --outputs prognostic|surface\n");
+    cloudsc_io_free(&ds);
+    return EXIT_FAILURE;
+  }
+  if (o.fields_caller == 4 && o.exact_libm) {
+    fprintf(stderr, "dwarf-cloudsc-amd: --fields tendbuf-cml has no --fp32-exact-libm form\n");
     cloudsc_io_free(&ds);
     return EXIT_FAILURE;
   }
@@ -854,7 +889,8 @@ int main(int argc, char **argv) {
     s->energy_s = o.energy_s;
     s->caller = o.fields_caller; s->place_on = place;
     s->tend_planes = o.fields_caller >= 2 ? o.tend_planes : 0;
-    s->inplace = o.fields_caller == 3;
+    s->inplace = o.fields_caller == 3 || o.fields_caller == 4;
+    s->cml = o.fields_caller == 4;
     s->outputs = o.outputs;
     s->aerosols = ds.params.laericesed || ds.params.laericeauto;
     s->tmpl = &tmpl; s->params = &ds.params; s->ref = ds.has_reference ? &ref : NULL; s->barrier = &bar;

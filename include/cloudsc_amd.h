@@ -508,6 +508,129 @@ int cloudsc_cpu_run_tendbuf_outputs(int nthreads, int precision, int outputs, in
                                     int tend_planes, const cloudsc_params_t *params,
                                     const cloudsc_fields_t *host_fields);
 
+/* ------------------------------------------------------------------------ */
+/* The cumulative tendency buffer (BUFFER_CML)                               */
+/* ------------------------------------------------------------------------ */
+/* The reference's Fortran GPU, Loki and Python-interface drivers carry a third
+ * buffer of the shape of BUFFER_TMP and BUFFER_LOC, BUFFER_CML(NPROMA, NLEV,
+ * 3+NCLV, NGPBLKS), the "cumulative tendency used for final output"
+ * (cloudsc_driver_gpu_scc_mod.F90:27,50).  The dwarf's kernel never reads it; a
+ * host model adds every physics process's local tendency to it.  The entry
+ * points below do that for this step: fused into the step
+ * (cloudsc_gpu_run_tendbuf_cml: the caller needs no BUFFER_LOC at all, 8 * klev
+ * elements per column of device memory less), or as a separate streaming pass
+ * over a BUFFER_LOC that a step has filled (cloudsc_fields_accumulate_tendbuf).
+ *
+ * The four members are plane starts in block 0 of a buffer [nblocks]
+ * [tend_planes][klev][nproma] of the precision's storage type -- t, q, a one
+ * plane each, cld the first of five consecutive planes (ql, qi, qr, qs, vapour)
+ * -- with the block stride tend_planes * klev * nproma elements, tend_planes
+ * being the one the call is given.  Which planes they are is the caller's
+ * choice; cloudsc_tendbuf_bind_cml sets the reference's order. */
+typedef struct cloudsc_tend_cml { void *t, *q, *a, *cld; } cloudsc_tend_cml_t;
+
+/* Set the four members of *cml to the plane starts of buffer_cml in the
+ * reference's plane order (CLOUDSC_TENDBUF_T/A/Q/CLD), as cloudsc_tendbuf_bind
+ * does for the other two buffers.  Pointer arithmetic only: a host or a device
+ * buffer, any tend_planes.  CLOUDSC_EINVAL: a NULL argument, an unknown
+ * precision, nproma or klev < 1. */
+int cloudsc_tendbuf_bind_cml(cloudsc_tend_cml_t *cml, int precision, int nproma, int klev, void *buffer_cml);
+
+/* cloudsc_gpu_run_tendbuf_outputs with the step's local tendencies ADDED to the
+ * cumulative planes instead of stored to tendency_loc_*: one launch, the same
+ * kernels' physics, 7 * klev more element loads per column and seven planes
+ * stored instead of eight.
+ *
+ * What is accumulated.  For each of the seven planes T, Q, A, CLD(ql, qi, qr,
+ * qs), every level and every real column, with `loc` what the step holds for
+ * tendency_loc_* at that element:
+ *   CLOUDSC_FP64   cml = cml + loc, one IEEE double add; loc is, bit for bit,
+ *                  what cloudsc_gpu_run stores to tendency_loc_*;
+ *   CLOUDSC_FP32   the same with one float add on the fp32 step's float;
+ *   CLOUDSC_MIXED  cml = (float)((double)cml + loc64), loc64 the double the
+ *                  kernel holds BEFORE its narrowing store: the mixed identity
+ *                  out = (float) fp64_form((double) in) extends to CML, bit for
+ *                  bit.  (cloudsc_fields_accumulate_tendbuf, below, adds the
+ *                  already narrowed float in float arithmetic: in mixed the
+ *                  fused form and step + pass differ in the last bit of some
+ *                  elements; in fp64 and fp32 they are equal bit for bit.)
+ * The add is its own rounding: it never merges into the multiply that produces
+ * the tendency (-ffp-contract=off).
+ * A launch adds once; repeated launches accumulate repeatedly (the caller
+ * zeroes or carries BUFFER_CML as its time step requires).
+ *
+ * What is left alone.  The vapour plane (the fifth behind cml->cld) is neither
+ * read nor written: the step's local vapour tendency is identically zero.
+ * tendency_loc_t/q/a/cld of device_fields are neither read nor written: they
+ * may be NULL, and a non-NULL one keeps every byte.  In BUFFER_CML only the
+ * seven planes' elements in lanes of real columns are touched: other planes,
+ * the vapour plane and the padding lanes of a partial last block keep every
+ * byte.  Every other kept output (plude, pcovptot, prainfrac_toprfz, the four
+ * precipitation fluxes as profiles or surface fields) has the full step's bits.
+ *
+ * `outputs` is CLOUDSC_OUTPUTS_PROGNOSTIC or CLOUDSC_OUTPUTS_SURFACE.
+ * CLOUDSC_OUTPUTS_ALL is refused (CLOUDSC_EINVAL): a caller that wants the
+ * flux diagnostics runs its step and then cloudsc_fields_accumulate_tendbuf.
+ * KCACHE and KSEG, every precision, with and without aerosols, packed and
+ * unpacked narrow blocks; one KSEG workspace serves this form and all others in
+ * any order.  The device-resident state, the host pipelines and the drop-in do
+ * not have the form.
+ * CLOUDSC_EINVAL, all checked before the first HIP call: CLOUDSC_VARIANT_SCC,
+ * CLOUDSC_VARIANT_SCC_PRIVATE, the option bit CLOUDSC_FP32_EXACT_LIBM, an
+ * unknown option bit, tend_planes outside 8..64, a NULL cml or a NULL member of
+ * it, a cml member equal to a tendency_tmp_* or tendency_loc_* member (pointer
+ * equality only: overlapping planes are the caller's to avoid), and every
+ * argument error of cloudsc_gpu_run_tendbuf_outputs (tendency_loc_* excepted).
+ *
+ * Rate (one MI355X, 163,840 columns, KSEG, four alternated runs of 3 x 20
+ * steps each per precision, profiles/tendbuf_cml/rate.jsonl):
+ * against the parent commit's cloudsc_gpu_run_tendbuf_outputs(PROGNOSTIC) the
+ * fused step takes 1.081 (fp64), 1.017 (mixed), 1.072 (fp32) of the time; against
+ * the same step followed by cloudsc_fields_accumulate_tendbuf 0.723, 0.788,
+ * 0.733: fused is below step + pass in every precision. */
+int cloudsc_gpu_run_tendbuf_cml(int device, void *stream, int precision, int variant, int outputs,
+                                int ngptot, int nproma, int klev, int tend_planes,
+                                const cloudsc_fields_t *device_fields, const cloudsc_tend_cml_t *cml,
+                                void *scratch);
+
+/* The host twin, on HOST memory through the same phase functions, fp64 and
+ * mixed as the other host forms (CLOUDSC_FP32: CLOUDSC_EINVAL): the same
+ * contract, the mixed rule included.  CLOUDSC_EINVAL: CLOUDSC_OUTPUTS_ALL or an
+ * unknown `outputs` value, tend_planes outside 8..64, the cml rules above and
+ * every argument error of cloudsc_cpu_run_tendbuf_outputs (tendency_loc_*
+ * excepted).  Needs no GPU. */
+int cloudsc_cpu_run_tendbuf_cml(int nthreads, int precision, int outputs, int ngptot, int nproma, int klev,
+                                int tend_planes, const cloudsc_params_t *params,
+                                const cloudsc_fields_t *host_fields, const cloudsc_tend_cml_t *cml);
+
+/* The separate pass: cml += tendency_loc_* over the same seven planes, for
+ * callers outside the fused form (the SCC variants, CLOUDSC_OUTPUTS_ALL,
+ * separate tendency arrays).  For every level and every real column
+ *   cml = cml + loc   in the storage type's arithmetic: double for
+ *                     CLOUDSC_FP64, float for CLOUDSC_FP32 AND CLOUDSC_MIXED
+ *                     (the stored, already narrowed float is added: not the
+ *                     fused form's mixed contract, above).
+ * loc_tend_planes (cml_tend_planes) is 0 where tendency_loc_* of loc_fields
+ * (the members of cml) are separate arrays -- [nblocks][klev][nproma] and
+ * [nblocks][5][klev][nproma] -- or 8..64 where they are planes of a packed
+ * buffer, independently on each side.  Only tendency_loc_t/q/a/cld of
+ * loc_fields are looked at.  The vapour planes of both sides, other planes and
+ * padding lanes are neither read nor written.  One streaming launch through
+ * the field set item walker, like convert, compare and expand: asynchronous in
+ * `stream`, no cloudsc_gpu_init needed, no workspace.  A launch adds once.
+ * CLOUDSC_EINVAL (before the first HIP call): an unknown precision, ngptot,
+ * nproma or klev < 1, nproma > 2^24, a *_tend_planes that is neither 0 nor
+ * 8..64, a NULL argument, a NULL tendency_loc_* or cml member, a cml member
+ * equal to a tendency_loc_* member.  CLOUDSC_ENODEV: no such device. */
+int cloudsc_fields_accumulate_tendbuf(int device, void *stream, int precision, int ngptot, int nproma, int klev,
+                                      int loc_tend_planes, const cloudsc_fields_t *loc_fields,
+                                      int cml_tend_planes, const cloudsc_tend_cml_t *cml);
+
+/* The same on HOST arrays, bit for bit.  Needs no GPU. */
+int cloudsc_cpu_fields_accumulate_tendbuf(int nthreads, int precision, int ngptot, int nproma, int klev,
+                                          int loc_tend_planes, const cloudsc_fields_t *loc_fields,
+                                          int cml_tend_planes, const cloudsc_tend_cml_t *cml);
+
 /* cloudsc_fields_alloc for an output selection.  With CLOUDSC_OUTPUTS_ALL it is
  * cloudsc_fields_alloc.  With CLOUDSC_OUTPUTS_PROGNOSTIC the ten diagnostic
  * members are not allocated and stay NULL (10 * (klev + 1) elements per column
