@@ -130,6 +130,17 @@ class Fields(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ALL_FIELDS]
 
 
+class LevelsFields(Fields):
+    """The Fields of a LAYOUT_LEVELS set (DeviceFields(layout=LAYOUT_LEVELS)): the same struct, marked so that
+    the step wrappers can refuse it -- only convert_fields_layout takes such a set."""
+
+
+def require_blocked(f, what: str) -> None:
+    if isinstance(f, LevelsFields):
+        raise ValueError("%s takes a block-layout field set; this one is LAYOUT_LEVELS: convert it first "
+                         "(convert_fields_layout / DeviceFields.convert_to)" % what)
+
+
 class TendCml(C.Structure):
     """cloudsc_tend_cml_t: the plane starts of the cumulative tendency buffer (BUFFER_CML) in block 0; cld
     is the first of five consecutive planes, the fifth (vapour) never touched."""
@@ -161,6 +172,9 @@ DIAGNOSTIC_FLUX_FIELDS = ("pfsqlf", "pfsqif", "pfcqnng", "pfcqlng", "pfsqrf", "p
                           "pfsqltur", "pfsqitur")
 # the four flux outputs OUTPUTS_SURFACE keeps as surface fields [nblocks][nproma]: row klev of their profiles
 SURFACE_FLUX_FIELDS = ("pfplsl", "pfplsn", "pfhpsl", "pfhpsn")
+# field set layouts (cloudsc_fields_convert_layout): [nblocks][rows][nproma], what every step takes, and
+# [ngptot][rows], the rows of one column contiguous
+LAYOUT_BLOCKED, LAYOUT_LEVELS = 0, 1
 
 
 def selected_outputs(outputs: int = OUTPUTS_ALL) -> tuple:
@@ -558,6 +572,12 @@ def gpu_lib(path: Optional[str] = None):
             C.POINTER(Fields), C.c_int, C.c_int, C.POINTER(Fields)]
         lib.cloudsc_fields_compare_outputs.argtypes = lib.cloudsc_fields_convert_outputs.argtypes + \
             [C.POINTER(FieldDiff)]
+    if hasattr(lib, "cloudsc_fields_convert_layout"):   # (likewise: the layout conversion)
+        # (device, stream | nthreads), ngptot, klev, outputs, then precision, layout, nproma, fields of src and of dst
+        lib.cloudsc_fields_convert_layout.argtypes = [C.c_int, C.c_void_p] + [C.c_int] * 6 + [C.POINTER(Fields)] + \
+            [C.c_int] * 3 + [C.POINTER(Fields)]
+        lib.cloudsc_cpu_fields_convert_layout.argtypes = [C.c_int] * 7 + [C.POINTER(Fields)] + [C.c_int] * 3 + \
+            [C.POINTER(Fields)]
     lib.cloudsc_fields_diff_sizeof.restype = C.c_longlong
     lib.cloudsc_fields_compare_release.argtypes = [C.c_int]
     lib.cloudsc_debug_set_compare_grid.argtypes = [C.c_int]
@@ -660,6 +680,26 @@ def convert_fields_outputs(src: "Fields", dst: "Fields", ngptot: int, klev: int,
                                                    C.byref(src), dst_precision, dst_nproma, C.byref(dst)))
 
 
+def convert_fields_layout(src: "Fields", dst: "Fields", ngptot: int, klev: int, src_precision: int, src_layout: int,
+                          src_nproma: int, dst_precision: int, dst_layout: int, dst_nproma: int,
+                          outputs: int = OUTPUTS_ALL, device: int = 0, stream=None) -> None:
+    """cloudsc_fields_convert_layout: convert_fields_outputs between DEVICE field sets of either layout
+    (LAYOUT_BLOCKED: [nblocks][rows][nproma]; LAYOUT_LEVELS: [ngptot][rows], its nproma 0).  Asynchronous on
+    `stream`: synchronise it before reading dst from the host."""
+    check(gpu_lib().cloudsc_fields_convert_layout(device, stream, ngptot, klev, outputs, src_precision, src_layout,
+                                                  src_nproma, C.byref(src), dst_precision, dst_layout, dst_nproma,
+                                                  C.byref(dst)))
+
+
+def cpu_convert_fields_layout(src: "Fields", dst: "Fields", ngptot: int, klev: int, src_precision: int,
+                              src_layout: int, src_nproma: int, dst_precision: int, dst_layout: int, dst_nproma: int,
+                              outputs: int = OUTPUTS_ALL, nthreads: int = 0) -> None:
+    """cloudsc_cpu_fields_convert_layout: the same on two Fields of HOST pointers."""
+    check(gpu_lib().cloudsc_cpu_fields_convert_layout(nthreads, ngptot, klev, outputs, src_precision, src_layout,
+                                                      src_nproma, C.byref(src), dst_precision, dst_layout,
+                                                      dst_nproma, C.byref(dst)))
+
+
 def cpu_convert_fields(src, dst, ngptot: Optional[int] = None, klev: Optional[int] = None,
                        src_precision: Optional[int] = None, src_nproma: Optional[int] = None,
                        dst_precision: Optional[int] = None, dst_nproma: Optional[int] = None, names=None,
@@ -703,6 +743,7 @@ def gpu_run_tendbuf(f: "Fields", precision: int, variant: int, ngptot: int, npro
     """cloudsc_gpu_run_tendbuf: one step on DEVICE fields whose tendency members are planes of packed
     buffers of tend_planes planes per block.  Asynchronous on `stream`; KSEG callers follow it with
     cloudsc_gpu_check."""
+    require_blocked(f, "gpu_run_tendbuf")
     check(gpu_lib().cloudsc_gpu_run_tendbuf(device, stream, precision, variant, ngptot, nproma, klev, tend_planes,
                                             C.byref(f), scratch))
 
@@ -711,6 +752,7 @@ def cpu_run_tendbuf(params: "Params", f: "Fields", precision: int, ngptot: int, 
                     tend_planes: int, nthreads: int = 0) -> None:
     """cloudsc_cpu_run_tendbuf: the CPU variant on HOST fields whose tendency members are planes of packed
     buffers (precision FP64 or MIXED)."""
+    require_blocked(f, "cpu_run_tendbuf")
     check(gpu_lib().cloudsc_cpu_run_tendbuf(nthreads, precision, ngptot, nproma, klev, tend_planes, C.byref(params),
                                             C.byref(f)))
 
@@ -720,6 +762,7 @@ def gpu_run_outputs(f: "Fields", precision: int, variant: int, outputs: int, ngp
     """cloudsc_gpu_run_outputs: one step on DEVICE fields with an output selection.  OUTPUTS_ALL is
     cloudsc_gpu_run; with OUTPUTS_PROGNOSTIC the DIAGNOSTIC_FLUX_FIELDS members are neither read nor written
     (they may be None).  Asynchronous on `stream`; KSEG callers follow it with cloudsc_gpu_check."""
+    require_blocked(f, "gpu_run_outputs")
     check(gpu_lib().cloudsc_gpu_run_outputs(device, stream, precision, variant, outputs, ngptot, nproma, klev,
                                             C.byref(f), scratch))
 
@@ -728,6 +771,7 @@ def cpu_run_outputs(params: "Params", f: "Fields", precision: int, outputs: int,
                     klev: int, nthreads: int = 0) -> None:
     """cloudsc_cpu_run_outputs: the CPU variant on HOST fields with an output selection (precision FP64 or
     MIXED)."""
+    require_blocked(f, "cpu_run_outputs")
     check(gpu_lib().cloudsc_cpu_run_outputs(nthreads, precision, outputs, ngptot, nproma, klev, C.byref(params),
                                             C.byref(f)))
 
@@ -737,6 +781,7 @@ def gpu_run_tendbuf_outputs(f: "Fields", precision: int, variant: int, outputs: 
     """cloudsc_gpu_run_tendbuf_outputs: gpu_run_tendbuf with an output selection.  OUTPUTS_ALL is
     cloudsc_gpu_run_tendbuf; with OUTPUTS_PROGNOSTIC the DIAGNOSTIC_FLUX_FIELDS members are neither read nor
     written (they may be None).  Asynchronous on `stream`; KSEG callers follow it with cloudsc_gpu_check."""
+    require_blocked(f, "gpu_run_tendbuf_outputs")
     check(gpu_lib().cloudsc_gpu_run_tendbuf_outputs(device, stream, precision, variant, outputs, ngptot, nproma,
                                                     klev, tend_planes, C.byref(f), scratch))
 
@@ -745,6 +790,7 @@ def cpu_run_tendbuf_outputs(params: "Params", f: "Fields", precision: int, outpu
                             klev: int, tend_planes: int, nthreads: int = 0) -> None:
     """cloudsc_cpu_run_tendbuf_outputs: the CPU variant on HOST fields whose tendency members are planes of
     packed buffers, with an output selection (precision FP64 or MIXED)."""
+    require_blocked(f, "cpu_run_tendbuf_outputs")
     check(gpu_lib().cloudsc_cpu_run_tendbuf_outputs(nthreads, precision, outputs, ngptot, nproma, klev, tend_planes,
                                                     C.byref(params), C.byref(f)))
 
@@ -779,6 +825,7 @@ def gpu_run_tendbuf_cml(f: "Fields", cml: "TendCml", precision: int, variant: in
     None and are never touched).  fp64 / fp32: cml += loc, one add in the storage type; mixed: cml =
     float32(float64(cml) + loc64).  The vapour plane of cml is neither read nor written.  OUTPUTS_ALL is
     refused.  A launch adds once: repeated launches accumulate repeatedly.  Asynchronous."""
+    require_blocked(f, "gpu_run_tendbuf_cml")
     check(gpu_lib().cloudsc_gpu_run_tendbuf_cml(device, stream, precision, variant, outputs, ngptot, nproma, klev,
                                                 tend_planes, C.byref(f), C.byref(cml), scratch))
 
@@ -786,6 +833,7 @@ def gpu_run_tendbuf_cml(f: "Fields", cml: "TendCml", precision: int, variant: in
 def cpu_run_tendbuf_cml(params: "Params", f: "Fields", cml: "TendCml", precision: int, outputs: int, ngptot: int,
                         nproma: int, klev: int, tend_planes: int, nthreads: int = 0) -> None:
     """cloudsc_cpu_run_tendbuf_cml: the same on HOST memory (fp64 and mixed)."""
+    require_blocked(f, "cpu_run_tendbuf_cml")
     check(gpu_lib().cloudsc_cpu_run_tendbuf_cml(nthreads, precision, outputs, ngptot, nproma, klev, tend_planes,
                                                 C.byref(params), C.byref(f), C.byref(cml)))
 
@@ -1215,16 +1263,28 @@ class DeviceFields:
     the placement search runs over the eleven other outputs; the set runs with gpu_run_outputs.
     outputs=OUTPUTS_SURFACE: likewise, and the SURFACE_FLUX_FIELDS members are surface fields [nblocks][nproma]
     (selected_field_shape): upload, download, copy_from, convert_to and compare take them as such, between
-    sets of the same selection."""
+    sets of the same selection.
+    layout=LAYOUT_LEVELS: the caller's level-contiguous arrays -- member `name` is (ngptot, rows) or (ngptot,)
+    (shape), nproma must be 0, no placement search is done and tend_planes is refused.  upload, download and
+    convert_to (cloudsc_fields_convert_layout when the two layouts differ) take such a set; the step wrappers,
+    compare, validate and expand refuse it (self.f is a LevelsFields)."""
 
     def __init__(self, ngptot: int, nproma: int, klev: int, precision: int = FP64, device: int = 0,
-                 place: bool = True, aerosols: bool = False, tend_planes: int = 0, outputs: int = OUTPUTS_ALL):
+                 place: bool = True, aerosols: bool = False, tend_planes: int = 0, outputs: int = OUTPUTS_ALL,
+                 layout: int = LAYOUT_BLOCKED):
+        if layout not in (LAYOUT_BLOCKED, LAYOUT_LEVELS):
+            raise ValueError("unknown layout: %r" % (layout,))
+        if layout == LAYOUT_LEVELS and (nproma or tend_planes):
+            raise ValueError("a LAYOUT_LEVELS set has no NPROMA (pass 0) and no packed tendency buffers")
         self.lib = gpu_lib()
         self.ngptot, self.nproma, self.klev, self.precision, self.device = ngptot, nproma, klev, precision, device
-        self.f = Fields()
+        self.layout = layout
+        self.f = Fields() if layout == LAYOUT_BLOCKED else LevelsFields()
         self.report = Placement()
         flags = (0 if place else PLACE_NONE) | (ALLOC_AEROSOLS if aerosols else 0)
         self.outputs = outputs
+        if layout == LAYOUT_LEVELS:   # [ngptot][rows] has the elements of one block of ngptot columns: no padding
+            nproma, flags = ngptot, flags | PLACE_NONE
         if outputs == OUTPUTS_ALL:
             check(self.lib.cloudsc_fields_alloc(device, precision, ngptot, nproma, klev, flags, C.byref(self.f),
                                                 C.byref(self.report)))
@@ -1261,11 +1321,21 @@ class DeviceFields:
 
     def nbytes(self, name: str) -> int:
         es = 4 if name == "ktype" else np.dtype(storage_dtype(self.precision)).itemsize
+        if self._layout() == LAYOUT_LEVELS:
+            return int(np.prod(self.shape(name))) * es
         return nblocks_of(self.ngptot, self.nproma) * int(np.prod(self.shape(name))) * es
 
     def shape(self, name: str) -> tuple:
-        """The per-block shape of a member of this set (selected_field_shape of its output selection)."""
+        """The per-block shape of a member of this set (selected_field_shape of its output selection); of a
+        LAYOUT_LEVELS set the whole member's: (ngptot, rows), or (ngptot,) for a member of one row."""
+        per_column = selected_field_shape(name, self.klev, 1, self._selection())
+        if self._layout() == LAYOUT_LEVELS:
+            rows = int(np.prod(per_column))
+            return (self.ngptot, rows) if len(per_column) > 1 else (self.ngptot,)
         return selected_field_shape(name, self.klev, self.nproma, self._selection())
+
+    def _layout(self) -> int:
+        return getattr(self, "layout", LAYOUT_BLOCKED)
 
     def _selection(self) -> int:
         """This set's output selection (OUTPUTS_ALL for a set put together without one)."""
@@ -1286,7 +1356,8 @@ class DeviceFields:
                 raise CloudscError("hipMemcpy %s failed (%d)" % (n, rc))
 
     def upload(self, arrays: Dict[str, np.ndarray]) -> None:
-        """Host block-layout arrays (make_host_state(...).arrays) into the device buffers."""
+        """Host arrays in this set's layout (block layout: make_host_state(...).arrays; LAYOUT_LEVELS:
+        shape(name) each) into the device buffers."""
         self.hip.hipSetDevice(self.device)
         for n, a in arrays.items():
             if getattr(self.f, n, None) is None:
@@ -1304,13 +1375,23 @@ class DeviceFields:
         if (other.ngptot, other.klev, other.device) != (self.ngptot, self.klev, self.device):
             raise ValueError("convert_to: ngptot, klev and device must be the same")
         a, b = fields_subset(self.f, names, other.f), fields_subset(other.f, names, self.f)
-        if OUTPUTS_SURFACE in (self._selection(), other._selection()) and any(getattr(a, n) for n in SURFACE_FLUX_FIELDS):
-            self._same_selection(other, "convert_to")
-            convert_fields_outputs(a, b, self.ngptot, self.klev, OUTPUTS_SURFACE, self.precision, self.nproma,
-                                   other.precision, other.nproma, self.device, stream)
+        surface = (OUTPUTS_SURFACE in (self._selection(), other._selection())
+                   and any(getattr(a, n) for n in SURFACE_FLUX_FIELDS))
+        if self._layout() != other._layout():
+            if surface:
+                self._same_selection(other, "convert_to")
+            convert_fields_layout(a, b, self.ngptot, self.klev, self.precision, self._layout(), self.nproma,
+                                  other.precision, other._layout(), other.nproma,
+                                  OUTPUTS_SURFACE if surface else OUTPUTS_ALL, self.device, stream)
             return
-        convert_fields(a, b, self.ngptot, self.klev, self.precision, self.nproma, other.precision, other.nproma,
-                       self.device, stream)
+        # (two LEVELS sets: one block of ngptot columns each, the same element positions)
+        snp, dnp = (self.nproma or self.ngptot), (other.nproma or other.ngptot)
+        if surface:
+            self._same_selection(other, "convert_to")
+            convert_fields_outputs(a, b, self.ngptot, self.klev, OUTPUTS_SURFACE, self.precision, snp,
+                                   other.precision, dnp, self.device, stream)
+            return
+        convert_fields(a, b, self.ngptot, self.klev, self.precision, snp, other.precision, dnp, self.device, stream)
 
     def compare(self, other: "DeviceFields", names=None, stream=None) -> Dict[str, dict]:
         """cloudsc_fields_compare of this set against `other` as the reference (another blocking and / or
@@ -1318,6 +1399,8 @@ class DeviceFields:
         sets hold.  See compare_fields for the result."""
         if (other.ngptot, other.klev, other.device) != (self.ngptot, self.klev, self.device):
             raise ValueError("compare: ngptot, klev and device must be the same")
+        require_blocked(self.f, "compare")
+        require_blocked(other.f, "compare")
         a, b = fields_subset(self.f, names, other.f), fields_subset(other.f, names, self.f)
         if OUTPUTS_SURFACE in (self._selection(), other._selection()) and any(getattr(a, n) for n in SURFACE_FLUX_FIELDS):
             self._same_selection(other, "compare")
@@ -1330,6 +1413,7 @@ class DeviceFields:
         """cloudsc_fields_validate: the 21 validated fields against ds.reference on the device; the list
         of 7-tuples GpuState.validate returns.  (A tend_planes set: its separate arrays, self.separate --
         unpack BUFFER_LOC first, or validate it in place with validate_fields_tendbuf.)"""
+        require_blocked(self.f, "validate")
         keep: list = []
         ref = make_reference(ds, keep)
         st = (Stats * 21)()
@@ -1343,6 +1427,7 @@ class DeviceFields:
         dataset's template on the device.  Asynchronous on `stream` (None = the default stream).
         (A tend_planes set: its separate arrays, self.separate -- pack tendency_tmp_* afterwards, or fill the buffers
         in place with expand_fields_tendbuf.)"""
+        require_blocked(self.f, "expand")
         if ds.klev != self.klev:
             raise ValueError("expand: the dataset's klev is not this set's")
         keep: list = []
@@ -1351,19 +1436,22 @@ class DeviceFields:
                                              col_offset, C.byref(tmpl), C.byref(self.separate or self.f)))
 
     def download_raw(self, name: str) -> np.ndarray:
-        """One field in block layout in its storage type (after a device synchronise)."""
+        """One field in this set's layout in its storage type (after a device synchronise): block layout
+        (nblocks,) + shape(name), LAYOUT_LEVELS shape(name)."""
         self.hip.hipSetDevice(self.device)
         self.hip.hipDeviceSynchronize()
         dt = np.int32 if name == "ktype" else storage_dtype(self.precision)
-        nb = nblocks_of(self.ngptot, self.nproma)
-        out = np.empty((nb,) + self.shape(name), dtype=dt)
+        if self._layout() == LAYOUT_LEVELS:
+            out = np.empty(self.shape(name), dtype=dt)
+        else:
+            out = np.empty((nblocks_of(self.ngptot, self.nproma),) + self.shape(name), dtype=dt)
         rc = self.hip.hipMemcpy(out.ctypes.data, getattr(self.f, name), out.nbytes, 2)
         if rc != 0:
             raise CloudscError("hipMemcpy %s failed (%d)" % (name, rc))
         return out
 
     def download(self, name: str) -> np.ndarray:
-        """One field in block layout as float64."""
+        """One field in this set's layout as float64."""
         return self.download_raw(name).astype(np.float64)
 
     def close(self) -> None:

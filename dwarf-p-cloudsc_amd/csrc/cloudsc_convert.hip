@@ -24,31 +24,6 @@ namespace {
 
 using ConvTable = FsTable<void>;   // entry {a, b} = {src, dst}
 
-// the element type of a storage size; a copy between equal sizes moves bits
-template <int BYTES> struct ConvReal { using type = double; using bits = unsigned long long; };
-template <> struct ConvReal<4> { using type = float; using bits = unsigned; };
-template <int SB, int DB> struct ConvPair {
-  using S = typename std::conditional<SB == DB, typename ConvReal<SB>::bits, typename ConvReal<SB>::type>::type;
-  using D = typename std::conditional<SB == DB, typename ConvReal<DB>::bits, typename ConvReal<DB>::type>::type;
-};
-
-// nrows rows of one column: src + so, dst + doff address the first row, the row strides are the NPROMAs
-template <typename S, typename D>
-__device__ __forceinline__ void conv_rows(const void* src, void* dst, size_t so, size_t doff, size_t snp, size_t dnp,
-                                          int nrows) {
-  const S* __restrict__ s = (const S*)src + so;
-  D* __restrict__ d = (D*)dst + doff;
-  for (int r = 0; r < nrows; r += kFsBatch) {
-    S v[kFsBatch];
-#pragma unroll
-    for (int q = 0; q < kFsBatch; q++)
-      if (r + q < nrows) v[q] = __builtin_nontemporal_load(s + (size_t)(r + q) * snp);
-#pragma unroll
-    for (int q = 0; q < kFsBatch; q++)
-      if (r + q < nrows) __builtin_nontemporal_store((D)v[q], d + (size_t)(r + q) * dnp);
-  }
-}
-
 // the per-item part of fs_kernel
 template <int SB, int DB>
 struct ConvItem {
@@ -153,11 +128,11 @@ extern "C" int cloudsc_fields_convert_outputs(int device, void* stream, int ngpt
                       outputs);
 }
 
-extern "C" int cloudsc_cpu_fields_convert(int nthreads, int ngptot, int klev, int src_precision, int src_nproma,
-                                          const cloudsc_fields_t* src, int dst_precision, int dst_nproma,
-                                          const cloudsc_fields_t* dst) {
+int cloudsc_impl::cpu_convert(int nthreads, int ngptot, int klev, int src_precision, int src_nproma,
+                              const cloudsc_fields_t* src, int dst_precision, int dst_nproma,
+                              const cloudsc_fields_t* dst, int outputs) {
   ConvTable a = {};
-  int rc = fs_build(ngptot, klev, src_precision, src_nproma, src, dst_precision, dst_nproma, dst, &a);
+  int rc = fs_build(ngptot, klev, src_precision, src_nproma, src, dst_precision, dst_nproma, dst, &a, nullptr, outputs);
   if (rc) return rc;
   const bool s8 = precision_storage_bytes(src_precision) == 8, d8 = precision_storage_bytes(dst_precision) == 8;
   void (*block)(const ConvTable&, long long, const long long*, const long long*) =
@@ -165,6 +140,13 @@ extern "C" int cloudsc_cpu_fields_convert(int nthreads, int ngptot, int klev, in
   const long long nblocks = ((long long)ngptot + dst_nproma - 1) / dst_nproma;
   fs_run_blocks(nthreads, nblocks, [&](int, long long b) { block(a, b, nullptr, nullptr); });
   return CLOUDSC_OK;
+}
+
+extern "C" int cloudsc_cpu_fields_convert(int nthreads, int ngptot, int klev, int src_precision, int src_nproma,
+                                          const cloudsc_fields_t* src, int dst_precision, int dst_nproma,
+                                          const cloudsc_fields_t* dst) {
+  return cpu_convert(nthreads, ngptot, klev, src_precision, src_nproma, src, dst_precision, dst_nproma, dst,
+                     CLOUDSC_OUTPUTS_ALL);
 }
 
 extern "C" int cloudsc_fields_convert_tendbuf(int device, void* stream, int ngptot, int klev, int src_precision,

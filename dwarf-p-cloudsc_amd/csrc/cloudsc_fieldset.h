@@ -120,6 +120,31 @@ __device__ __forceinline__ size_t fs_wrapped(unsigned g, long long col_offset, i
   return r.row0 * (size_t)klon + (size_t)((col_offset + (long long)g) % klon);
 }
 
+// The copies (cloudsc_convert.hip, cloudsc_transpose.hip).  The element type of a storage size; a copy between equal sizes moves bits
+template <int BYTES> struct ConvReal { using type = double; using bits = unsigned long long; };
+template <> struct ConvReal<4> { using type = float; using bits = unsigned; };
+template <int SB, int DB> struct ConvPair {
+  using S = typename std::conditional<SB == DB, typename ConvReal<SB>::bits, typename ConvReal<SB>::type>::type;
+  using D = typename std::conditional<SB == DB, typename ConvReal<DB>::bits, typename ConvReal<DB>::type>::type;
+};
+
+// nrows rows of one column: src + so, dst + doff address the first row, the row strides are the NPROMAs
+template <typename S, typename D>
+__device__ __forceinline__ void conv_rows(const void* src, void* dst, size_t so, size_t doff, size_t snp, size_t dnp,
+                                          int nrows) {
+  const S* __restrict__ s = (const S*)src + so;
+  D* __restrict__ d = (D*)dst + doff;
+  for (int r = 0; r < nrows; r += kFsBatch) {
+    S v[kFsBatch];
+#pragma unroll
+    for (int q = 0; q < kFsBatch; q++)
+      if (r + q < nrows) v[q] = __builtin_nontemporal_load(s + (size_t)(r + q) * snp);
+#pragma unroll
+    for (int q = 0; q < kFsBatch; q++)
+      if (r + q < nrows) __builtin_nontemporal_store((D)v[q], d + (size_t)(r + q) * dnp);
+  }
+}
+
 // ---------------------------------------------------------------------------
 // host side; no HIP call up to fs_device
 // ---------------------------------------------------------------------------
@@ -222,6 +247,10 @@ inline int fs_device(int device, int* ncu) {
   }
   return CLOUDSC_OK;
 }
+
+// cloudsc_cpu_fields_convert for two sets of one output selection (cloudsc_convert.hip)
+int cpu_convert(int nthreads, int ngptot, int klev, int src_precision, int src_nproma, const cloudsc_fields_t* src,
+                int dst_precision, int dst_nproma, const cloudsc_fields_t* dst, int outputs);
 
 // The host twins walk a block of one set and meet the other set in runs: fn(jl, b, j, run) for the columns
 // [g0 + jl, g0 + jl + run) of [g0, g0 + n), which are columns [j, j + run) of block b in blocks of np

@@ -58,6 +58,7 @@
 typedef struct {
   int numomp, ngptot, nproma, ngpus, precision, variant, reps, warmup;
   int transfer, chunk_blocks, nstreams, exact_libm;
+  int fields_levels;              /* --fields levels: --fields caller from and into CLOUDSC_LAYOUT_LEVELS arrays */
   int fields_caller;              /* --fields caller | tendbuf | tendbuf-inplace | tendbuf-cml (1 | 2 | 3 | 4): caller-owned field sets */
   int tend_planes;                /* --fields tendbuf: planes per block of the two tendency buffers (0: not tendbuf) */
   int outputs, outputs_given;     /* --outputs all|prognostic|surface: CLOUDSC_OUTPUTS_* */
@@ -73,6 +74,7 @@ typedef struct {
   int device, ngptot, nproma, precision, variant, reps, warmup;
   int libm_bit;                   /* CLOUDSC_FP32_EXACT_LIBM or 0 */
   int caller, place_on, aerosols; /* --fields caller; its placement search; aerosol inputs allocated */
+  int levels;                     /* --fields levels: caller, the set held level-contiguous at both ends */
   int tend_planes;                /* --fields tendbuf: the step runs on two packed tendency buffers of that many planes */
   int inplace;                    /* --fields tendbuf-inplace: fill, step and validation on the buffers themselves */
   int cml;                        /* --fields tendbuf-cml: inplace, the step adding its tendencies to a zeroed BUFFER_CML (no BUFFER_LOC) */
@@ -140,6 +142,10 @@ static void usage(const char *prog) {
           "                        CUDA driver's shape on caller-owned device fields, per shard\n"
           "                        cloudsc_fields_alloc, _expand, cloudsc_gpu_run, cloudsc_gpu_check,\n"
           "                        cloudsc_fields_validate (not with --transfer or --variant cpu)\n"
+          "  --fields levels       caller, with the caller's data level-contiguous ([ngptot][rows]) at both ends:\n"
+          "                        the template expanded into a blocked staging set and converted to LEVELS,\n"
+          "                        cloudsc_fields_convert_layout LEVELS -> the placed NPROMA set, the step, the\n"
+          "                        outputs -> LEVELS -> blocked, validated there (kseg and kcache only)\n"
           "  --fields tendbuf      caller, with the tendencies in the reference Fortran drivers' two packed\n"
           "                        buffers: tendency_tmp_* packed into a BUFFER_TMP, cloudsc_gpu_run_tendbuf,\n"
           "                        BUFFER_LOC unpacked before the validation (kseg and kcache only)\n"
@@ -221,8 +227,10 @@ static int parse(int argc, char **argv, options_t *o) {
     else if (!strcmp(a, "--transfer")) o->transfer = 1;
     else if (!strcmp(a, "--fields")) {
       NEEDV();
+      o->fields_levels = 0;   /* the last --fields decides */
       if (!strcmp(v, "state")) o->fields_caller = 0;
       else if (!strcmp(v, "caller")) o->fields_caller = 1;
+      else if (!strcmp(v, "levels")) { o->fields_caller = 1; o->fields_levels = 1; }
       else if (!strcmp(v, "tendbuf")) o->fields_caller = 2;
       else if (!strcmp(v, "tendbuf-inplace")) o->fields_caller = 3;
       else if (!strcmp(v, "tendbuf-cml")) o->fields_caller = 4;
@@ -404,6 +412,28 @@ static int caller_step(const shard_t *s, int variant, int klev, const cloudsc_fi
   return cloudsc_gpu_run(s->device, NULL, s->precision, variant, s->ngptot, s->nproma, klev, f, ws);
 }
 
+/* the members of f the step reads (want_out 0: inputs and plude) or writes (1: outputs and plude) */
+#define FIELD_DIR(n, N, k, d, i) CLOUDSC_FD_##d,
+static const int k_field_dir[CLOUDSC_NFIELDS] = {CLOUDSC_FIELDS(FIELD_DIR)};
+static void fields_part(const cloudsc_fields_t *f, int want_out, cloudsc_fields_t *part) {
+  memset(part, 0, sizeof(*part));
+  for (int m = 0; m < CLOUDSC_NFIELDS; m++)
+    if (k_field_dir[m] == CLOUDSC_FD_INOUT || (k_field_dir[m] == CLOUDSC_FD_OUT) == (want_out != 0))
+      ((const void **)part)[m] = ((const void *const *)f)[m];
+}
+
+/* --fields levels: `part` (0 inputs, 1 outputs) of src -> dst, a LEVELS side's NPROMA given as 0 */
+static int levels_convert(const shard_t *s, int klev, int part, const cloudsc_fields_t *src, int src_nproma,
+                          const cloudsc_fields_t *dst, int dst_nproma) {
+  cloudsc_fields_t a, b;
+  fields_part(src, part, &a);
+  fields_part(dst, part, &b);
+  return cloudsc_fields_convert_layout(s->device, NULL, s->ngptot, klev, s->outputs, s->precision,
+                                       src_nproma ? CLOUDSC_LAYOUT_BLOCKED : CLOUDSC_LAYOUT_LEVELS, src_nproma, &a,
+                                       s->precision, dst_nproma ? CLOUDSC_LAYOUT_BLOCKED : CLOUDSC_LAYOUT_LEVELS,
+                                       dst_nproma, &b);
+}
+
 static void shard_caller(shard_t *s) {
   int (*set_device)(int) = (int (*)(int))hip_sym("hipSetDevice");
   int (*dmalloc)(void **, size_t) = (int (*)(void **, size_t))hip_sym("hipMalloc");
@@ -431,8 +461,23 @@ static void shard_caller(shard_t *s) {
                                          &f, &s->place);
   else if (!s->rc)
     s->rc = cloudsc_fields_alloc(s->device, s->precision, s->ngptot, s->nproma, klev, alloc_flags, &f, &s->place);
+  /* --fields levels: `lev` is the caller's data, [ngptot][rows] (the elements of one block of ngptot columns);
+   * `stage` the blocked set the template is expanded into and the outputs are validated in */
+  cloudsc_fields_t stage, lev;
+  memset(&stage, 0, sizeof(stage));
+  memset(&lev, 0, sizeof(lev));
+  if (!s->rc && s->levels) {
+    const int flags = alloc_flags | CLOUDSC_PLACE_NONE;
+    cloudsc_placement_t none;
+    s->rc = cloudsc_fields_alloc_outputs(s->device, s->precision, s->ngptot, s->nproma, klev, flags, s->outputs, &stage, &none);
+    if (!s->rc)
+      s->rc = cloudsc_fields_alloc_outputs(s->device, s->precision, s->ngptot, s->ngptot, klev, flags, s->outputs, &lev, &none);
+    if (!s->rc) s->rc = cloudsc_fields_expand(s->device, NULL, s->precision, s->ngptot, s->nproma, s->col_offset, s->tmpl, &stage);
+    if (!s->rc) s->rc = levels_convert(s, klev, 0, &stage, s->nproma, &lev, 0);
+    if (!s->rc) s->rc = levels_convert(s, klev, 0, &lev, 0, &f, s->nproma);
+  }
   /* (tendbuf-inplace fills g below, once the tendency members are bound to the buffers) */
-  if (!s->rc && !inplace) s->rc = cloudsc_fields_expand(s->device, NULL, s->precision, s->ngptot, s->nproma, s->col_offset, s->tmpl, &f);
+  if (!s->rc && !inplace && !s->levels) s->rc = cloudsc_fields_expand(s->device, NULL, s->precision, s->ngptot, s->nproma, s->col_offset, s->tmpl, &f);
   const long long wsb = cloudsc_gpu_scratch_bytes(s->precision, s->variant, s->ngptot, s->nproma, klev);
   if (!s->rc && wsb < 0) s->rc = CLOUDSC_EINVAL;
   if (!s->rc && wsb > 0 && (set_device(s->device) || dmalloc(&ws, (size_t)wsb) || dmemset(ws, 0, 256))) s->rc = CLOUDSC_ENOMEM;
@@ -494,6 +539,9 @@ static void shard_caller(shard_t *s) {
   if (!s->rc && tp && !inplace)   /* unpack BUFFER_LOC into the separate tendency_loc_* arrays the validation reads */
     s->rc = cloudsc_fields_convert_tendbuf(s->device, NULL, s->ngptot, klev, s->precision, s->nproma, tp, &loc_buf,
                                            s->precision, s->nproma, 0, &loc_sep);
+  if (!s->rc && s->levels) s->rc = levels_convert(s, klev, 1, &f, s->nproma, &lev, 0);
+  if (!s->rc && s->levels) s->rc = levels_convert(s, klev, 1, &lev, 0, &stage, s->nproma);
+  const cloudsc_fields_t *vf = s->levels ? &stage : &f;   /* the separate arrays the validation reads */
   if (!s->rc && s->ref && (inplace || s->outputs != CLOUDSC_OUTPUTS_ALL)) {
     /* in place: BUFFER_LOC itself.  A prognostic set: the fields cloudsc_fields_alloc_outputs allocated -- the
      * library's selection, read off the set: a validated member it left NULL has no reference array either */
@@ -506,11 +554,11 @@ static void shard_caller(shard_t *s) {
       g.tendency_loc_t = cml.t; g.tendency_loc_a = cml.a; g.tendency_loc_q = cml.q; g.tendency_loc_cld = cml.cld;
     }
     for (int id = 0; id < CLOUDSC_NVALID; id++)
-      if (!((const void *const *)&f)[member[id]]) { ref.field[id] = NULL; s->skipped[id] = 1; }
+      if (!((const void *const *)vf)[member[id]]) { ref.field[id] = NULL; s->skipped[id] = 1; }
     s->rc = cloudsc_fields_validate_tendbuf(s->device, NULL, s->precision, s->ngptot, s->nproma, klev, inplace ? tp : 0,
-                                            s->outputs, s->col_offset, inplace ? &g : &f, &ref, s->stats);
+                                            s->outputs, s->col_offset, inplace ? &g : vf, &ref, s->stats);
   } else if (!s->rc && s->ref)
-    s->rc = cloudsc_fields_validate(s->device, NULL, s->precision, s->ngptot, s->nproma, klev, s->col_offset, &f, s->ref,
+    s->rc = cloudsc_fields_validate(s->device, NULL, s->precision, s->ngptot, s->nproma, klev, s->col_offset, vf, s->ref,
                                     s->stats);
   if (s->rc) snprintf(s->err, sizeof(s->err), "%s", cloudsc_last_hip_error());
   if (ws) dfree(ws);
@@ -518,6 +566,8 @@ static void shard_caller(shard_t *s) {
   if (buf_loc) dfree(buf_loc);
   if (buf_cml) dfree(buf_cml);
   cloudsc_fields_free(s->device, &f);
+  cloudsc_fields_free(s->device, &stage);
+  cloudsc_fields_free(s->device, &lev);
 }
 
 static void *shard_main(void *arg) {
@@ -800,6 +850,12 @@ int main(int argc, char **argv) {
     cloudsc_io_free(&ds);
     return EXIT_FAILURE;
   }
+  if (o.fields_levels && (o.transfer || (o.variant != CLOUDSC_VARIANT_KSEG && o.variant != CLOUDSC_VARIANT_KCACHE))) {
+    fprintf(stderr, "dwarf-cloudsc-amd: --fields levels runs --variant kseg|kcache on device fields (no --transfer, "
+                    "no cpu, scc or scc-private)\n");
+    cloudsc_io_free(&ds);
+    return EXIT_FAILURE;
+  }
   if (o.fields_caller >= 2 && !o.tend_planes) o.tend_planes = CLOUDSC_TENDBUF_PLANES_MIN;
   if (o.fields_caller && (o.transfer || o.variant == VARIANT_CPU)) {
     fprintf(stderr, "dwarf-cloudsc-amd: --fields caller runs the GPU variants on device fields (no --transfer, no "
@@ -887,7 +943,7 @@ int main(int argc, char **argv) {
     s->precision = o.precision; s->variant = o.variant; s->reps = o.reps; s->warmup = o.warmup;
     s->libm_bit = o.exact_libm ? CLOUDSC_FP32_EXACT_LIBM : 0;
     s->energy_s = o.energy_s;
-    s->caller = o.fields_caller; s->place_on = place;
+    s->caller = o.fields_caller; s->place_on = place; s->levels = o.fields_levels;
     s->tend_planes = o.fields_caller >= 2 ? o.tend_planes : 0;
     s->inplace = o.fields_caller == 3 || o.fields_caller == 4;
     s->cml = o.fields_caller == 4;

@@ -310,6 +310,55 @@ int cloudsc_cpu_fields_convert(int nthreads, int ngptot, int klev,
                                int src_precision, int src_nproma, const cloudsc_fields_t *src,
                                int dst_precision, int dst_nproma, const cloudsc_fields_t *dst);
 
+/* Field set layouts.  Every other entry point takes CLOUDSC_LAYOUT_BLOCKED.  In
+ * CLOUDSC_LAYOUT_LEVELS the rows of one column are contiguous and there is no
+ * padding: a member is [ngptot][rows] with the rows of its kind in the block
+ * layout -- klev, klev + 1, CLOUDSC_NCLV * klev (row m * klev + k of species m:
+ * [ngptot][CLOUDSC_NCLV][klev]) or 1 (surface members and ktype: [ngptot]).  It
+ * is what MPAS (nVertLevels, nCells), (ncol, nlev) views and [sample][level]
+ * NumPy arrays look like. */
+#define CLOUDSC_LAYOUT_BLOCKED 0   /* [nblocks][rows][nproma], what every other entry point takes */
+#define CLOUDSC_LAYOUT_LEVELS  1   /* [ngptot][rows]: the rows of one column contiguous, no padding */
+
+/* cloudsc_fields_convert_outputs between field sets of either layout on
+ * `device`, asynchronously on `stream`.  For every member that is non-NULL in
+ * both sets, every row r of its kind under `outputs` and every global column
+ * g < ngptot, the element [g / nproma][r][g % nproma] of a BLOCKED side and
+ * [g][r] of a LEVELS side:  dst = (dst type) src, the conversion of
+ * cloudsc_fields_convert (equal types copy bits, ktype is an int32 copy).
+ * A LEVELS side has no NPROMA: its *_nproma must be 0.  The padding lanes of a
+ * BLOCKED destination's last block are never written; a LEVELS destination is
+ * written in exactly ngptot * rows elements.
+ * BLOCKED -> BLOCKED is cloudsc_fields_convert_outputs; LEVELS -> LEVELS is that
+ * copy over one block of ngptot columns (so ngptot <= 2^24 there).  Between the
+ * two layouts the members of one row take the same copy, and the others one
+ * transposing kernel through LDS tiles (at most two launches; DESIGN.md §3.27
+ * has the access pattern and the rates).
+ * CLOUDSC_EINVAL, before the first HIP call and so on a machine without a GPU
+ * too: an unknown layout or `outputs`, a non-zero NPROMA on a LEVELS side, and
+ * every argument error of cloudsc_fields_convert.  Never synchronises; needs no
+ * cloudsc_gpu_init.  The step entry points take BLOCKED sets only: convert the
+ * inputs once, and the outputs after a step.  Packed tendency buffers are not a
+ * side of this call (unpack with cloudsc_fields_convert_tendbuf first). */
+int cloudsc_fields_convert_layout(int device, void *stream, int ngptot, int klev, int outputs,
+                                  int src_precision, int src_layout, int src_nproma, const cloudsc_fields_t *src,
+                                  int dst_precision, int dst_layout, int dst_nproma, const cloudsc_fields_t *dst);
+
+/* The same on HOST arrays, on `nthreads` host threads (<= 0: all hardware
+ * threads) taking destination blocks (BLOCKED) or ranges of 256 columns
+ * (LEVELS) from a shared counter.  Needs no GPU. */
+int cloudsc_cpu_fields_convert_layout(int nthreads, int ngptot, int klev, int outputs,
+                                      int src_precision, int src_layout, int src_nproma, const cloudsc_fields_t *src,
+                                      int dst_precision, int dst_layout, int dst_nproma, const cloudsc_fields_t *dst);
+
+/* What the loaded code object says about kernel `which` (0..7: the storage pairs
+ * 8->8, 8->4, 4->8, 4->4 towards LEVELS, then the same towards BLOCKED) of the
+ * layout conversion on `device`: scratch bytes per lane and LDS bytes per
+ * workgroup.  For the tests; asks the runtime, launches nothing.  A library built
+ * with -DCLOUDSC_LAYOUT_NAIVE (make variant) has no such kernels and does not
+ * export this symbol. */
+int cloudsc_debug_layout_kernel_resources(int device, int which, int *scratch_bytes, int *lds_bytes);
+
 /* ------------------------------------------------------------------------ */
 /* Packed tendency buffers (the reference's Fortran drivers)                 */
 /* ------------------------------------------------------------------------ */
