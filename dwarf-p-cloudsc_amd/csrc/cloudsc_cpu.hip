@@ -42,7 +42,7 @@ struct HostColumn {
 // PROG: the prognostic-outputs form, the ten diagnostic flux members of A never touched (flux_level);
 // SURF: the surface-fluxes form, the other four flux members surface fields written after the last level;
 // CML: the cumulative tendency form, A a KArgsCML and the local tendencies added to its planes (load_cml, store_level_cml)
-template <typename real, bool AER, bool TB, bool PROG = false, bool SURF = false, bool CML = false, typename S>
+template <typename real, bool AER, bool TB, bool PROG, bool SURF, bool CML, typename S>
 void run_block(const DevParams<real>& c, const KArgs<real, S>& A, int b, std::vector<HostColumn<real>>& col) {
   const int nproma = A.nproma, klev = A.klev;
   const int bsize = std::min(nproma, A.ngptot - b * nproma);
@@ -108,35 +108,47 @@ void run_block(const DevParams<real>& c, const KArgs<real, S>& A, int b, std::ve
     for (int jl = 0; jl < bsize; jl++) flux_surface(c, A, u1, (unsigned)jl * (unsigned)sizeof(S), col[jl].cs);
 }
 
+// The host threads of a run (<= 0: one per hardware thread), and where its wall time and the per-thread records go
+// (each may be NULL; nthreads entries): a thread's own wall time, the NPROMA blocks it took, the columns it computed
+struct CpuThreads {
+  int nthreads;
+  double* seconds = nullptr;
+  double* thread_seconds = nullptr;
+  int* thread_blocks = nullptr;
+  int* thread_columns = nullptr;
+};
+
 // the block loop over fields of element type S, computed in double
 template <typename S>
-int cpu_run(int nthreads, int ngptot, int nproma, int klev, const cloudsc_params_t* params,
-            const cloudsc_fields_t* f, double* seconds, double* thread_seconds, int* thread_blocks,
-            int* thread_columns, int tend_planes = 0, int outputs = CLOUDSC_OUTPUTS_ALL,
-            const cloudsc_tend_cml_t* cml = nullptr) {
-  int rc = cloudsc_impl::check_params(params);
+int cpu_run(int ngptot, int nproma, int klev, const cloudsc_params_t* params, const cloudsc_fields_t* f,
+            const cloudsc_impl::StepForm& form, const CpuThreads& th) {
+  using namespace cloudsc_impl;
+  int nthreads = th.nthreads;
+  int rc = check_params(params);
   if (rc) return rc;
-  if (!f || !cloudsc_impl::fields_complete(f, outputs, cml != nullptr) || ngptot <= 0 || nproma <= 0 || klev < 2)
-    return CLOUDSC_EINVAL;
+  if (!f || !fields_complete(f, form) || ngptot <= 0 || nproma <= 0 || klev < 2) return CLOUDSC_EINVAL;
   const bool aer = params->laericesed || params->laericeauto;
   if (aer && (!f->pre_ice || !f->picrit_aer || !f->pnice)) return CLOUDSC_EINVAL;
-  if (nthreads <= 0 && (thread_seconds || thread_blocks || thread_columns)) return CLOUDSC_EINVAL;
+  if (nthreads <= 0 && (th.thread_seconds || th.thread_blocks || th.thread_columns)) return CLOUDSC_EINVAL;
   const DevParams<double> c = fold_params<double>(*params);
   KArgsCML<double, S> A;
   static_cast<KArgs<double, S>&>(A) = make_kargs<double, S>(f, ngptot, nproma, klev, nullptr);
-  A.tend_planes = tend_planes;   // 0: separate arrays
+  A.tend_planes = form.tend_planes;   // 0: separate arrays
   A.cml_t = A.cml_q = A.cml_a = A.cml_cld = nullptr;
-  if (cml) { A.cml_t = (S*)cml->t; A.cml_q = (S*)cml->q; A.cml_a = (S*)cml->a; A.cml_cld = (S*)cml->cld; }
+  if (const cloudsc_tend_cml_t* cml = form.cml) {
+    A.cml_t = (S*)cml->t; A.cml_q = (S*)cml->q; A.cml_a = (S*)cml->a; A.cml_cld = (S*)cml->cld;
+  }
   const int nblocks = ngptot / nproma + (ngptot % nproma ? 1 : 0);
   if (nthreads <= 0) nthreads = (int)std::max(1u, std::thread::hardware_concurrency());
   const int nreq = nthreads;                 // the caller's per-thread arrays have nreq entries
   nthreads = std::min(nthreads, nblocks);
   for (int t = 0; t < nreq; t++) {           // threads beyond the block count do nothing
-    if (thread_seconds) thread_seconds[t] = 0.0;
-    if (thread_blocks) thread_blocks[t] = 0;
-    if (thread_columns) thread_columns[t] = 0;
+    if (th.thread_seconds) th.thread_seconds[t] = 0.0;
+    if (th.thread_blocks) th.thread_blocks[t] = 0;
+    if (th.thread_columns) th.thread_columns[t] = 0;
   }
   std::atomic<int> next{0};
+  const unsigned bits = form_bits(form);
   // per thread, as the C dwarf's zinfo (cloudsc_driver.c:185-228): its own
   // wall time, NPROMA blocks taken (icalls) and columns computed (igpc)
   auto worker = [&](int tid) {
@@ -144,39 +156,21 @@ int cpu_run(int nthreads, int ngptot, int nproma, int klev, const cloudsc_params
     std::vector<HostColumn<double>> col((size_t)nproma);
     int icalls = 0, igpc = 0;
     for (int b = next.fetch_add(1); b < nblocks; b = next.fetch_add(1)) {
-      if (cml && outputs == CLOUDSC_OUTPUTS_SURFACE) {
-        if (aer) run_block<double, true, true, true, true, true>(c, A, b, col);
-        else run_block<double, false, true, true, true, true>(c, A, b, col);
-      } else if (cml) {
-        if (aer) run_block<double, true, true, true, false, true>(c, A, b, col);
-        else run_block<double, false, true, true, false, true>(c, A, b, col);
-      } else if (outputs == CLOUDSC_OUTPUTS_SURFACE && tend_planes) {
-        if (aer) run_block<double, true, true, true, true>(c, A, b, col);
-        else run_block<double, false, true, true, true>(c, A, b, col);
-      } else if (outputs == CLOUDSC_OUTPUTS_SURFACE) {
-        if (aer) run_block<double, true, false, true, true>(c, A, b, col);
-        else run_block<double, false, false, true, true>(c, A, b, col);
-      } else if (outputs == CLOUDSC_OUTPUTS_PROGNOSTIC && tend_planes) {
-        if (aer) run_block<double, true, true, true>(c, A, b, col);
-        else run_block<double, false, true, true>(c, A, b, col);
-      } else if (outputs == CLOUDSC_OUTPUTS_PROGNOSTIC) {
-        if (aer) run_block<double, true, false, true>(c, A, b, col);
-        else run_block<double, false, false, true>(c, A, b, col);
-      } else if (tend_planes) {
-        if (aer) run_block<double, true, true>(c, A, b, col);
-        else run_block<double, false, true>(c, A, b, col);
-      } else if (aer) {
-        run_block<double, true, false>(c, A, b, col);
-      } else {
-        run_block<double, false, false>(c, A, b, col);
-      }
+      // the run_block of the form: the sixteen whose bits go together (form_bits_consistent), as on the GPU
+      dispatch_bools(
+          [&](auto AER, auto TB, auto PROG, auto SURF, auto CML) {
+            if constexpr (form_bits_consistent(form_bits(TB, PROG, SURF, CML)))
+              run_block<double, AER, TB, PROG, SURF, CML>(c, A, b, col);
+            return 0;
+          },
+          aer, (bits & kFormTb) != 0, (bits & kFormProg) != 0, (bits & kFormSurf) != 0, (bits & kFormCml) != 0);
       icalls++;
       igpc += std::min(nproma, ngptot - b * nproma);
     }
     const auto s1 = std::chrono::steady_clock::now();
-    if (thread_seconds) thread_seconds[tid] = std::chrono::duration<double>(s1 - s0).count();
-    if (thread_blocks) thread_blocks[tid] = icalls;
-    if (thread_columns) thread_columns[tid] = igpc;
+    if (th.thread_seconds) th.thread_seconds[tid] = std::chrono::duration<double>(s1 - s0).count();
+    if (th.thread_blocks) th.thread_blocks[tid] = icalls;
+    if (th.thread_columns) th.thread_columns[tid] = igpc;
   };
   const auto t0 = std::chrono::steady_clock::now();
   if (nthreads == 1) {
@@ -192,8 +186,21 @@ int cpu_run(int nthreads, int ngptot, int nproma, int klev, const cloudsc_params
     for (auto& t : pool) t.join();
   }
   const auto t1 = std::chrono::steady_clock::now();
-  if (seconds) *seconds = std::chrono::duration<double>(t1 - t0).count();
+  if (th.seconds) *th.seconds = std::chrono::duration<double>(t1 - t0).count();
   return rc;
+}
+
+// A run entry: the form's rules (check_step_form, with the bits `need` of the entry), then the block loop of the
+// precision's storage type.  The host form computes in double: CLOUDSC_FP64 and CLOUDSC_MIXED.
+int cpu_run_form(int precision, int ngptot, int nproma, int klev, const cloudsc_params_t* params,
+                 const cloudsc_fields_t* f, const cloudsc_impl::StepForm& form, unsigned need, const CpuThreads& th) {
+  if (cloudsc_impl::check_step_form(form, need, f) || !cloudsc_impl::precision_computes_double(precision))
+    return CLOUDSC_EINVAL;
+  switch (cloudsc_impl::precision_storage_bytes(precision)) {
+    case sizeof(double): return cpu_run<double>(ngptot, nproma, klev, params, f, form, th);
+    case sizeof(float): return cpu_run<float>(ngptot, nproma, klev, params, f, form, th);
+    default: return CLOUDSC_EINVAL;
+  }
 }
 
 }  // namespace
@@ -201,21 +208,14 @@ int cpu_run(int nthreads, int ngptot, int nproma, int klev, const cloudsc_params
 extern "C" int cloudsc_cpu_run_threads(int nthreads, int ngptot, int nproma, int klev,
                                        const cloudsc_params_t* params, const cloudsc_fields_t* f, double* seconds,
                                        double* thread_seconds, int* thread_blocks, int* thread_columns) {
-  return cpu_run<double>(nthreads, ngptot, nproma, klev, params, f, seconds, thread_seconds, thread_blocks,
-                         thread_columns);
+  return cpu_run_form(CLOUDSC_FP64, ngptot, nproma, klev, params, f, {}, 0u,
+                      {nthreads, seconds, thread_seconds, thread_blocks, thread_columns});
 }
 
 extern "C" int cloudsc_cpu_run_precision(int nthreads, int precision, int ngptot, int nproma, int klev,
                                          const cloudsc_params_t* params, const cloudsc_fields_t* f,
                                          double* seconds) {
-  if (!cloudsc_impl::precision_computes_double(precision)) return CLOUDSC_EINVAL;   // the host form computes in double
-  switch (cloudsc_impl::precision_storage_bytes(precision)) {
-    case sizeof(double):
-      return cpu_run<double>(nthreads, ngptot, nproma, klev, params, f, seconds, nullptr, nullptr, nullptr);
-    case sizeof(float):
-      return cpu_run<float>(nthreads, ngptot, nproma, klev, params, f, seconds, nullptr, nullptr, nullptr);
-    default: return CLOUDSC_EINVAL;
-  }
+  return cpu_run_form(precision, ngptot, nproma, klev, params, f, {}, 0u, {nthreads, seconds});
 }
 
 extern "C" int cloudsc_cpu_run(int nthreads, int ngptot, int nproma, int klev, const cloudsc_params_t* params,
@@ -225,61 +225,24 @@ extern "C" int cloudsc_cpu_run(int nthreads, int ngptot, int nproma, int klev, c
 
 extern "C" int cloudsc_cpu_run_tendbuf(int nthreads, int precision, int ngptot, int nproma, int klev, int tend_planes,
                                        const cloudsc_params_t* params, const cloudsc_fields_t* f) {
-  if (tend_planes < CLOUDSC_TENDBUF_PLANES_MIN || tend_planes > CLOUDSC_TENDBUF_PLANES_MAX) return CLOUDSC_EINVAL;
-  if (!cloudsc_impl::precision_computes_double(precision)) return CLOUDSC_EINVAL;   // as cloudsc_cpu_run_precision
-  switch (cloudsc_impl::precision_storage_bytes(precision)) {
-    case sizeof(double):
-      return cpu_run<double>(nthreads, ngptot, nproma, klev, params, f, nullptr, nullptr, nullptr, nullptr, tend_planes);
-    case sizeof(float):
-      return cpu_run<float>(nthreads, ngptot, nproma, klev, params, f, nullptr, nullptr, nullptr, nullptr, tend_planes);
-    default: return CLOUDSC_EINVAL;
-  }
+  return cpu_run_form(precision, ngptot, nproma, klev, params, f, {tend_planes}, kFormTb, {nthreads});
 }
 
 extern "C" int cloudsc_cpu_run_outputs(int nthreads, int precision, int outputs, int ngptot, int nproma, int klev,
                                        const cloudsc_params_t* params, const cloudsc_fields_t* f) {
-  if (!cloudsc_impl::outputs_known(outputs)) return CLOUDSC_EINVAL;
-  if (!cloudsc_impl::precision_computes_double(precision)) return CLOUDSC_EINVAL;   // as cloudsc_cpu_run_precision
-  switch (cloudsc_impl::precision_storage_bytes(precision)) {
-    case sizeof(double):
-      return cpu_run<double>(nthreads, ngptot, nproma, klev, params, f, nullptr, nullptr, nullptr, nullptr, 0, outputs);
-    case sizeof(float):
-      return cpu_run<float>(nthreads, ngptot, nproma, klev, params, f, nullptr, nullptr, nullptr, nullptr, 0, outputs);
-    default: return CLOUDSC_EINVAL;
-  }
+  return cpu_run_form(precision, ngptot, nproma, klev, params, f, {0, outputs}, 0u, {nthreads});
 }
 
 extern "C" int cloudsc_cpu_run_tendbuf_outputs(int nthreads, int precision, int outputs, int ngptot, int nproma,
                                                int klev, int tend_planes, const cloudsc_params_t* params,
                                                const cloudsc_fields_t* f) {
-  if (!cloudsc_impl::outputs_known(outputs)) return CLOUDSC_EINVAL;
-  if (tend_planes < CLOUDSC_TENDBUF_PLANES_MIN || tend_planes > CLOUDSC_TENDBUF_PLANES_MAX) return CLOUDSC_EINVAL;
-  if (!cloudsc_impl::precision_computes_double(precision)) return CLOUDSC_EINVAL;   // as cloudsc_cpu_run_precision
-  switch (cloudsc_impl::precision_storage_bytes(precision)) {
-    case sizeof(double):
-      return cpu_run<double>(nthreads, ngptot, nproma, klev, params, f, nullptr, nullptr, nullptr, nullptr, tend_planes,
-                             outputs);
-    case sizeof(float):
-      return cpu_run<float>(nthreads, ngptot, nproma, klev, params, f, nullptr, nullptr, nullptr, nullptr, tend_planes,
-                            outputs);
-    default: return CLOUDSC_EINVAL;
-  }
+  return cpu_run_form(precision, ngptot, nproma, klev, params, f, {tend_planes, outputs}, kFormTb, {nthreads});
 }
 
+// (kFormProg: CLOUDSC_OUTPUTS_ALL is refused)
 extern "C" int cloudsc_cpu_run_tendbuf_cml(int nthreads, int precision, int outputs, int ngptot, int nproma, int klev,
                                            int tend_planes, const cloudsc_params_t* params, const cloudsc_fields_t* f,
                                            const cloudsc_tend_cml_t* cml) {
-  if (outputs != CLOUDSC_OUTPUTS_PROGNOSTIC && outputs != CLOUDSC_OUTPUTS_SURFACE) return CLOUDSC_EINVAL;   // not ALL
-  if (tend_planes < CLOUDSC_TENDBUF_PLANES_MIN || tend_planes > CLOUDSC_TENDBUF_PLANES_MAX) return CLOUDSC_EINVAL;
-  if (!cloudsc_impl::precision_computes_double(precision)) return CLOUDSC_EINVAL;   // as cloudsc_cpu_run_precision
-  if (cloudsc_impl::check_tend_cml(f, cml)) return CLOUDSC_EINVAL;
-  switch (cloudsc_impl::precision_storage_bytes(precision)) {
-    case sizeof(double):
-      return cpu_run<double>(nthreads, ngptot, nproma, klev, params, f, nullptr, nullptr, nullptr, nullptr, tend_planes,
-                             outputs, cml);
-    case sizeof(float):
-      return cpu_run<float>(nthreads, ngptot, nproma, klev, params, f, nullptr, nullptr, nullptr, nullptr, tend_planes,
-                            outputs, cml);
-    default: return CLOUDSC_EINVAL;
-  }
+  return cpu_run_form(precision, ngptot, nproma, klev, params, f, {tend_planes, outputs, cml},
+                      kFormCml | kFormTb | kFormProg, {nthreads});
 }

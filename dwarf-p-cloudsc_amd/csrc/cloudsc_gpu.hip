@@ -133,16 +133,23 @@ const ParamSet* device_default_params(int device) {
   return g_default[device].dev ? &g_default[device] : nullptr;
 }
 
-bool fields_complete(const cloudsc_fields_t* f, int outputs, bool cml) {
+bool fields_complete(const cloudsc_fields_t* f, const StepForm& form) {
   const void* const* p = (const void* const*)f;
   for (int m = 0; m < kNumFields; m++)
-    if (!p[m] && kFieldTable[m].dir != CLOUDSC_FD_AEROSOL && output_selected(m, outputs) && !(cml && is_tendency_loc(m)))
+    if (!p[m] && kFieldTable[m].dir != CLOUDSC_FD_AEROSOL && output_selected(m, form.outputs) &&
+        !(form.cml && is_tendency_loc(m)))
       return false;
   return true;
 }
 
-int check_tend_cml(const cloudsc_fields_t* f, const cloudsc_tend_cml_t* cml) {
-  if (!f || !cml || !cml->t || !cml->q || !cml->a || !cml->cld) return CLOUDSC_EINVAL;
+int check_step_form(const StepForm& form, unsigned need, const cloudsc_fields_t* f) {
+  const unsigned bits = form_bits(form);
+  if (!outputs_known(form.outputs) || (bits & need) != need || !form_bits_consistent(bits)) return CLOUDSC_EINVAL;
+  if (form.tend_planes && (form.tend_planes < CLOUDSC_TENDBUF_PLANES_MIN || form.tend_planes > CLOUDSC_TENDBUF_PLANES_MAX))
+    return CLOUDSC_EINVAL;
+  const cloudsc_tend_cml_t* cml = form.cml;
+  if (!cml) return CLOUDSC_OK;
+  if (!f || !cml->t || !cml->q || !cml->a || !cml->cld) return CLOUDSC_EINVAL;
   const void* const mine[4] = {cml->t, cml->q, cml->a, cml->cld};
   const void* const theirs[8] = {f->tendency_tmp_t,   f->tendency_tmp_q, f->tendency_tmp_a, f->tendency_tmp_cld,
                                  f->tendency_loc_t,   f->tendency_loc_q, f->tendency_loc_a, f->tendency_loc_cld};
@@ -279,36 +286,6 @@ void launch_physics(void (*kern)(Args...), dim3 grid, dim3 block, size_t lds, hi
   else hipLaunchKernelGGL(kern, grid, block, lds, st, args...);
 }
 
-// a launch's runtime conditions as compile-time constants, in one place:
-// dispatch_bools(f, c0, c1, ...) calls f(std::bool_constant<c0>{}, std::bool_constant<c1>{}, ...)
-template <bool... Bs, typename Fn>
-int dispatch_bools(Fn&& f) {
-  return f(std::integral_constant<bool, Bs>{}...);
-}
-template <bool... Bs, typename Fn, typename... Rest>
-int dispatch_bools(Fn&& f, bool c, Rest... rest) {
-  return c ? dispatch_bools<Bs..., true>(f, rest...) : dispatch_bools<Bs..., false>(f, rest...);
-}
-
-// The support matrix: whether (variant kind, precision, fp32 exact-libm, form bits kFormTb,
-// kFormProg and kFormSurf) has a kernel.  MIXED runs on the k-caching variants only; so do the tendency buffer
-// and the prognostic-outputs forms, alone or combined, which fp32 has with its default
-// exp/pow only; the surface-fluxes form is a prognostic-outputs form (kFormSurf without kFormProg
-// does not exist); the cumulative tendency form is a tendency buffer, prognostic-outputs form, with or
-// without kFormSurf (kFormCml without both does not exist); the SCC variants are plain.  (The exact-libm
-// bit means nothing outside fp32; every k-caching kernel has its packed twin, so kFormPack is not asked about.)
-constexpr bool form_exists(int kind, int precision, bool exact_libm, unsigned form) {
-  const bool tb = (form & kFormTb) != 0, prog = (form & kFormProg) != 0, surf = (form & kFormSurf) != 0;
-  const bool cml = (form & kFormCml) != 0;
-  const bool kcaching = kind == CLOUDSC_VARIANT_KCACHE || kind == CLOUDSC_VARIANT_KSEG;
-  if (!kcaching && kind != CLOUDSC_VARIANT_SCC && kind != CLOUDSC_VARIANT_SCC_PRIVATE) return false;
-  if (precision != CLOUDSC_FP64 && precision != CLOUDSC_FP32 && precision != CLOUDSC_MIXED) return false;
-  if (precision == CLOUDSC_MIXED && !kcaching) return false;
-  if (surf && !prog) return false;
-  if (cml && !(tb && prog)) return false;
-  if (tb || prog) return kcaching && !(precision == CLOUDSC_FP32 && exact_libm);
-  return true;
-}
 // the precision code of a (compute, storage) pair
 template <typename real, typename S>
 constexpr int kPrecisionOf = !std::is_same<real, S>::value ? CLOUDSC_MIXED : sizeof(real) == 8 ? CLOUDSC_FP64 : CLOUDSC_FP32;
@@ -362,18 +339,19 @@ int with_cfg(Fn&& f) {
 // the kernel arguments of a launch: a's, with tend_planes behind them in the tendency buffer form and the
 // BUFFER_CML plane starts behind that in the cumulative tendency form
 template <typename F>
-typename F::kargs kernel_args(const typename F::fields& a, int tend_planes, const cloudsc_tend_cml_t* cml) {
+typename F::kargs kernel_args(const typename F::fields& a, const StepForm& form) {
   if constexpr (F::tb) {
     typename F::kargs t;
     static_cast<typename F::fields&>(t) = a;
-    t.tend_planes = tend_planes;
+    t.tend_planes = form.tend_planes;
     if constexpr (F::cml) {
       using S = typename F::store;
+      const cloudsc_tend_cml_t* cml = form.cml;
       t.cml_t = (S*)cml->t; t.cml_q = (S*)cml->q; t.cml_a = (S*)cml->a; t.cml_cld = (S*)cml->cld;
     }
     return t;
   } else {
-    (void)tend_planes; (void)cml;
+    (void)form;
     return a;
   }
 }
@@ -566,134 +544,157 @@ int launch_kseg_cfg(hipStream_t st, const typename F::kargs& a, const PersistArg
   return CLOUDSC_OK;
 }
 
+// One launch, as gpu_run_impl asks for it: everything launch_v needs, by name
+struct LaunchRequest {
+  hipStream_t st;
+  int kind;          // CLOUDSC_VARIANT_*, without option bits
+  bool exact_libm;   // CLOUDSC_FP32_EXACT_LIBM
+  const cloudsc_fields_t* f;
+  int ngptot, nproma, klev;
+  void* scratch;
+  const void* plude_in;   // NULL: in place
+  const ParamSet& ps;
+  KsegEpoch* ep;
+  const LaunchEvents* ev;
+  StepForm form;
+};
+
+// The KSEG launch of a request: the schedule and the workspace's epoch, then with_form's kernel (launch_v)
+template <typename real, typename ST, typename WithForm>
+int launch_kseg(const LaunchRequest& rq, const KArgs<real, ST>& a, const PackArgs& pk, const WithForm& with_form) {
+  const hipStream_t st = rq.st;
+  void* const scratch = rq.scratch;
+  KsegEpoch* const ep = rq.ep;
+  const int nproma = rq.nproma, klev = rq.klev, nblocks = pk.nblocks, pack = pk.pack;
+  if (!scratch) return CLOUDSC_EINVAL;
+  PersistArgs<real> pa;
+  pa.ctr = (unsigned*)((char*)scratch + kKsegCtrOffset);
+  pa.err = (unsigned*)scratch + 1;
+  pa.clk = (unsigned long long*)((char*)scratch + kKsegClkOffset);
+  pa.flags = (unsigned*)((char*)scratch + kKsegFlagOffset);
+  pa.state = (real*)((char*)scratch + kseg_ctl_bytes(nblocks, nproma));
+  pa.nsub = pack > 1 ? 1 : kseg_nsub(nproma);
+  // the schedule's units: blocks, or groups of `pack` blocks (one flag each:
+  // the first pk.ngroups words of the flag area)
+  const int nunits = pack > 1 ? pk.ngroups : nblocks;
+  pa.spin_limit = g_kseg_spin_limit.load(std::memory_order_relaxed);
+  // item order (segment, block, sub-block); (segment, sub-block, block) measured
+  // the same within noise at NPROMA 128, 2 % slower at 256 (profiles/r01/kseg_subblock_order.jsonl)
+  pa.sb_major = 0;
+  pa.nseg = kKsegNseg;
+  if (const int n = g_kseg_nseg.load(std::memory_order_relaxed)) pa.nseg = n > kMaxSeg ? kMaxSeg : n;
+#ifdef CLOUDSC_DEBUG_KNOBS
+  pa.sb_major = env_int("CLOUDSC_KSEG_SBMAJOR", 0) != 0;
+  pa.nseg = env_int("CLOUDSC_KSEG_NSEG", kKsegNseg);
+  pa.nseg = pa.nseg < 1 ? 1 : (pa.nseg > kMaxSeg ? kMaxSeg : pa.nseg);
+#endif
+  if (pa.nseg > klev) pa.nseg = klev;
+  pa.nblocks = nblocks;
+  for (int q = 0; q <= kMaxSeg; q++) pa.lev[q] = klev;
+  kseg_bounds(pa.nseg, klev, rq.ps.ncldtop, kKsegSplitPct<real>, pa.lev);
+#ifdef CLOUDSC_DEBUG_KNOBS
+  if (const char* e = getenv("CLOUDSC_KSEG_BOUNDS")) {   // explicit interior boundaries
+    int n = 1, v = 0;
+    const char* q = e;
+    while (*q && n < kMaxSeg) {
+      v = (int)strtol(q, (char**)&q, 10);
+      if (v <= pa.lev[n - 1] || v >= klev) break;
+      pa.lev[n++] = v;
+      if (*q == ',') q++;
+    }
+    pa.nseg = n;
+    pa.lev[n] = klev;
+  }
+#endif
+  pa.nitems = pa.nseg * nunits * pa.nsub;
+  const bool zero_ws = !(ep && ep->ready);
+  if (zero_ws) {
+    const int nflags = nblocks * kseg_nsub(nproma);
+    const int g = (nflags + 255) / 256 < 64 ? (nflags + 255) / 256 : 64;
+    hipLaunchKernelGGL(kseg_prepare_kernel, dim3(g > 0 ? g : 1), dim3(256), 0, st, (unsigned*)scratch, nflags);
+    if (ep) ep->ready = false;
+  }
+  for (int q = 0; q < kKsegStripes; q++) pa.base[q] = zero_ws ? 0u : ep->base[q];
+  pa.stamp = zero_ws ? 0u : ep->stamp;
+  int grid = 0;
+  const int rc = with_form(std::integral_constant<int, CLOUDSC_VARIANT_KSEG>{}, [&](auto form) {
+    using F = decltype(form);
+    return launch_kseg_cfg<F>(st, kernel_args<F>(a, rq.form), pa, nproma, pa.nitems, &grid, rq.ev, pk);
+  });
+  if (rc) return rc;
+  HIPCHK(hipGetLastError());
+  if (ep) {   // the next launch on this workspace continues where this one ends
+    // stripe q took its items plus one past-the-end ticket per workgroup of it
+    const int S = kseg_nstripes(grid);
+    for (int q = 0; q < kKsegStripes; q++) {
+      const unsigned nbs = q < S ? (unsigned)((nunits - q + S - 1) / S) : 0u;
+      const unsigned wgs = q < S ? (unsigned)((grid - q + S - 1) / S) : 0u;
+      ep->base[q] = pa.base[q] + (unsigned)pa.nseg * nbs * (unsigned)pa.nsub + wgs;
+    }
+    ep->stamp = pa.stamp + (unsigned)(kMaxSeg + 1);
+    ep->ready = true;
+  }
+  return CLOUDSC_OK;
+}
+
 // real: the compute type; ST: the fields' element type (float under a double
 // `real` is CLOUDSC_MIXED: the k-caching kernels only)
 template <typename real, bool FAST, typename ST = real>
-int launch_v(hipStream_t st, int variant, const cloudsc_fields_t* f, int ngptot, int nproma, int klev,
-             void* scratch, const void* plude_in, const ParamSet& ps, KsegEpoch* ep, const LaunchEvents* ev,
-             int tend_planes, int outputs, const cloudsc_tend_cml_t* cml) {
-  // tend_planes != 0: the tendency buffer form; the selection's bits: the prognostic-outputs and surface-fluxes forms;
-  // cml: the cumulative tendency form
-  const bool aer = ps.aer, tb = tend_planes != 0, prog = outputs_prognostic(outputs), surf = outputs_surface(outputs);
-  if (!kernel_kept<real, ST, FAST>(variant, aer, (tb ? kFormTb : 0u) | (prog ? kFormProg : 0u) | (surf ? kFormSurf : 0u) |
-                                                     (cml ? kFormCml : 0u)))
-    return CLOUDSC_EINVAL;
+int launch_v(const LaunchRequest& rq) {
+  const cloudsc_fields_t* f = rq.f;
+  const int kind = rq.kind, nproma = rq.nproma, klev = rq.klev;
+  const bool aer = rq.ps.aer;
+  const unsigned bits = form_bits(rq.form);
+  if (!kernel_kept<real, ST, FAST>(kind, aer, bits)) return CLOUDSC_EINVAL;
   KArgs<real, ST> a = make_kargs<real, ST>(
-      f, ngptot, nproma, klev, (const DevParams<real>*)((const char*)ps.dev + (sizeof(real) == 8 ? 0 : kSpOffset)));
-  if (plude_in) a.plude_in = (const ST*)plude_in;
-  const int nblocks = ngptot / nproma + (ngptot % nproma ? 1 : 0);
+      f, rq.ngptot, nproma, klev, (const DevParams<real>*)((const char*)rq.ps.dev + (sizeof(real) == 8 ? 0 : kSpOffset)));
+  if (rq.plude_in) a.plude_in = (const ST*)rq.plude_in;
+  const int nblocks = rq.ngptot / nproma + (rq.ngptot % nproma ? 1 : 0);
   if (aer && (!f->pre_ice || !f->picrit_aer || !f->pnice)) return CLOUDSC_EINVAL;
   int rc = CLOUDSC_OK;
   // blocks per wave (1 = unpacked) and the packed launches' extra kernel argument
-  int pack = narrow_pack_factor(kPrecisionOf<real, ST>, variant, nproma, klev, aer);
+  int pack = narrow_pack_factor(kPrecisionOf<real, ST>, kind, nproma, klev, aer);
   // (a packed lane's offset in a tendency buffer: below pack * tend_planes * klev * nproma elements)
-  if ((unsigned long long)pack * (unsigned)tend_planes * (unsigned long long)klev * (unsigned)nproma * 8ull >= (1ull << 32))
+  if ((unsigned long long)pack * (unsigned)rq.form.tend_planes * (unsigned long long)klev * (unsigned)nproma * 8ull >=
+      (1ull << 32))
     pack = 1;
   const PackArgs pk{pack, nblocks, (nblocks + pack - 1) / pack};
   // The k-caching launch of this call: go(F{}) with the descriptor F of its kernel -- the runtime
   // conditions become F's members here, and only kernels that exist are instantiated
-  const auto with_form = [&](auto kind, auto&& go) {
+  const auto with_form = [&](auto kind_c, auto&& go) {
     return dispatch_bools(
         [&](auto AER, auto PACK, auto TB, auto PROG, auto SURF, auto CML) {
-          constexpr unsigned form = (PACK ? kFormPack : 0u) | (TB ? kFormTb : 0u) | (PROG ? kFormProg : 0u) |
-                                    (SURF ? kFormSurf : 0u) | (CML ? kFormCml : 0u);
-          if constexpr (kernel_kept<real, ST, FAST>(kind, AER, form))
-            return with_cfg<LaunchForm<real, ST, AER, FAST, form>, cfg_table_applies(kind, form)>(go);
+          constexpr unsigned form = form_bits(TB, PROG, SURF, CML) | (PACK ? kFormPack : 0u);
+          if constexpr (kernel_kept<real, ST, FAST>(kind_c, AER, form))
+            return with_cfg<LaunchForm<real, ST, AER, FAST, form>, cfg_table_applies(kind_c, form)>(go);
           else
             return (int)CLOUDSC_EINVAL;
         },
-        aer, pack > 1, tb, prog, surf, cml != nullptr);
+        aer, pack > 1, (bits & kFormTb) != 0, (bits & kFormProg) != 0, (bits & kFormSurf) != 0, (bits & kFormCml) != 0);
   };
-  if (variant == CLOUDSC_VARIANT_KCACHE) {
+  if (kind == CLOUDSC_VARIANT_KCACHE) {
     rc = with_form(std::integral_constant<int, CLOUDSC_VARIANT_KCACHE>{}, [&](auto form) {
       using F = decltype(form);
-      return launch_kcache<F>(st, kernel_args<F>(a, tend_planes, cml), nblocks, nproma, pk, ev);
+      return launch_kcache<F>(rq.st, kernel_args<F>(a, rq.form), nblocks, nproma, pk, rq.ev);
     });
-  } else if (variant == CLOUDSC_VARIANT_KSEG) {
-    if (!scratch) return CLOUDSC_EINVAL;
-    PersistArgs<real> pa;
-    pa.ctr = (unsigned*)((char*)scratch + kKsegCtrOffset);
-    pa.err = (unsigned*)scratch + 1;
-    pa.clk = (unsigned long long*)((char*)scratch + kKsegClkOffset);
-    pa.flags = (unsigned*)((char*)scratch + kKsegFlagOffset);
-    pa.state = (real*)((char*)scratch + kseg_ctl_bytes(nblocks, nproma));
-    pa.nsub = pack > 1 ? 1 : kseg_nsub(nproma);
-    // the schedule's units: blocks, or groups of `pack` blocks (one flag each:
-    // the first pk.ngroups words of the flag area)
-    const int nunits = pack > 1 ? pk.ngroups : nblocks;
-    pa.spin_limit = g_kseg_spin_limit.load(std::memory_order_relaxed);
-    // item order (segment, block, sub-block); (segment, sub-block, block) measured
-    // the same within noise at NPROMA 128, 2 % slower at 256 (profiles/r01/kseg_subblock_order.jsonl)
-    pa.sb_major = 0;
-    pa.nseg = kKsegNseg;
-    if (const int n = g_kseg_nseg.load(std::memory_order_relaxed)) pa.nseg = n > kMaxSeg ? kMaxSeg : n;
-#ifdef CLOUDSC_DEBUG_KNOBS
-    pa.sb_major = env_int("CLOUDSC_KSEG_SBMAJOR", 0) != 0;
-    pa.nseg = env_int("CLOUDSC_KSEG_NSEG", kKsegNseg);
-    pa.nseg = pa.nseg < 1 ? 1 : (pa.nseg > kMaxSeg ? kMaxSeg : pa.nseg);
-#endif
-    if (pa.nseg > klev) pa.nseg = klev;
-    pa.nblocks = nblocks;
-    for (int q = 0; q <= kMaxSeg; q++) pa.lev[q] = klev;
-    kseg_bounds(pa.nseg, klev, ps.ncldtop, kKsegSplitPct<real>, pa.lev);
-#ifdef CLOUDSC_DEBUG_KNOBS
-    if (const char* e = getenv("CLOUDSC_KSEG_BOUNDS")) {   // explicit interior boundaries
-      int n = 1, v = 0;
-      const char* q = e;
-      while (*q && n < kMaxSeg) {
-        v = (int)strtol(q, (char**)&q, 10);
-        if (v <= pa.lev[n - 1] || v >= klev) break;
-        pa.lev[n++] = v;
-        if (*q == ',') q++;
-      }
-      pa.nseg = n;
-      pa.lev[n] = klev;
-    }
-#endif
-    pa.nitems = pa.nseg * nunits * pa.nsub;
-    const bool zero_ws = !(ep && ep->ready);
-    if (zero_ws) {
-      const int nflags = nblocks * kseg_nsub(nproma);
-      const int g = (nflags + 255) / 256 < 64 ? (nflags + 255) / 256 : 64;
-      hipLaunchKernelGGL(kseg_prepare_kernel, dim3(g > 0 ? g : 1), dim3(256), 0, st, (unsigned*)scratch, nflags);
-      if (ep) ep->ready = false;
-    }
-    for (int q = 0; q < kKsegStripes; q++) pa.base[q] = zero_ws ? 0u : ep->base[q];
-    pa.stamp = zero_ws ? 0u : ep->stamp;
-    int grid = 0;
-    rc = with_form(std::integral_constant<int, CLOUDSC_VARIANT_KSEG>{}, [&](auto form) {
-      using F = decltype(form);
-      return launch_kseg_cfg<F>(st, kernel_args<F>(a, tend_planes, cml), pa, nproma, pa.nitems, &grid, ev, pk);
-    });
-    if (rc) return rc;
-    HIPCHK(hipGetLastError());
-    if (ep) {   // the next launch on this workspace continues where this one ends
-      // stripe q took its items plus one past-the-end ticket per workgroup of it
-      const int S = kseg_nstripes(grid);
-      for (int q = 0; q < kKsegStripes; q++) {
-        const unsigned nbs = q < S ? (unsigned)((nunits - q + S - 1) / S) : 0u;
-        const unsigned wgs = q < S ? (unsigned)((grid - q + S - 1) / S) : 0u;
-        ep->base[q] = pa.base[q] + (unsigned)pa.nseg * nbs * (unsigned)pa.nsub + wgs;
-      }
-      ep->stamp = pa.stamp + (unsigned)(kMaxSeg + 1);
-      ep->ready = true;
-    }
-  } else if (variant == CLOUDSC_VARIANT_SCC_PRIVATE) {
+  } else if (kind == CLOUDSC_VARIANT_KSEG) {
+    return launch_kseg(rq, a, pk, with_form);
+  } else if (kind == CLOUDSC_VARIANT_SCC_PRIVATE) {
     if (klev > kPrivKlev) return CLOUDSC_EINVAL;    // the private arrays are sized at compile time
     rc = dispatch_bools(
         [&](auto AER) {
           if constexpr (kernel_kept<real, ST, FAST>(CLOUDSC_VARIANT_SCC_PRIVATE, AER))
-            launch_physics(scc_private_entry<real, AER, FAST>, dim3(nblocks), dim3(nproma), 0, st, ev, a);
+            launch_physics(scc_private_entry<real, AER, FAST>, dim3(nblocks), dim3(nproma), 0, rq.st, rq.ev, a);
           return (int)CLOUDSC_OK;
         },
         aer);
   } else {
-    if (!scratch) return CLOUDSC_EINVAL;
+    if (!rq.scratch) return CLOUDSC_EINVAL;
     rc = dispatch_bools(
         [&](auto AER) {
           if constexpr (kernel_kept<real, ST, FAST>(CLOUDSC_VARIANT_SCC, AER))
-            launch_physics(scc_entry<real, AER, FAST>, dim3(nblocks), dim3(nproma), 0, st, ev, a,
-                           scc_scratch_carve<real>((char*)scratch, nblocks, nproma, klev));
+            launch_physics(scc_entry<real, AER, FAST>, dim3(nblocks), dim3(nproma), 0, rq.st, rq.ev, a,
+                           scc_scratch_carve<real>((char*)rq.scratch, nblocks, nproma, klev));
           return (int)CLOUDSC_OK;
         },
         aer);
@@ -703,38 +704,14 @@ int launch_v(hipStream_t st, int variant, const cloudsc_fields_t* f, int ngptot,
   return CLOUDSC_OK;
 }
 
-// fp32 runs the float-internal exp/pow unless the caller asks for the
-// reference CPU build's forms (CLOUDSC_FP32_EXACT_LIBM); fp64 has only those
-template <typename real>
-int launch(hipStream_t st, int variant, bool exact_libm, const cloudsc_fields_t* f, int ngptot, int nproma,
-           int klev, void* scratch, const void* plude_in, const ParamSet& ps, KsegEpoch* ep, const LaunchEvents* ev,
-           int tend_planes, int outputs, const cloudsc_tend_cml_t* cml) {
-  if constexpr (std::is_same<real, float>::value) {
-    if (!exact_libm)
-      return launch_v<real, true>(st, variant, f, ngptot, nproma, klev, scratch, plude_in, ps, ep, ev, tend_planes,
-                                  outputs, cml);
-  }
-  (void)exact_libm;
-  return launch_v<real, false>(st, variant, f, ngptot, nproma, klev, scratch, plude_in, ps, ep, ev, tend_planes,
-                               outputs, cml);
-}
-
-// The launch of a precision code.  CLOUDSC_MIXED is the fp64 launch (exp/pow,
-// parameter mirror, configuration, workspace) over float fields.
-int launch_precision(int precision, hipStream_t st, int variant, bool exact_libm, const cloudsc_fields_t* f,
-                     int ngptot, int nproma, int klev, void* scratch, const void* plude_in, const ParamSet& ps,
-                     KsegEpoch* ep, const LaunchEvents* ev, int tend_planes, int outputs,
-                     const cloudsc_tend_cml_t* cml) {
+// The launch of a precision code: its (real, ST, FAST).  CLOUDSC_MIXED is the fp64 launch (exp/pow, parameter
+// mirror, configuration, workspace) over float fields; fp32 runs the float-internal exp/pow unless the caller
+// asks for the reference CPU build's forms (CLOUDSC_FP32_EXACT_LIBM), which are the only ones fp64 has
+int launch(int precision, const LaunchRequest& rq) {
   switch (precision) {
-    case CLOUDSC_FP64:
-      return launch<double>(st, variant, exact_libm, f, ngptot, nproma, klev, scratch, plude_in, ps, ep, ev, tend_planes,
-                            outputs, cml);
-    case CLOUDSC_FP32:
-      return launch<float>(st, variant, exact_libm, f, ngptot, nproma, klev, scratch, plude_in, ps, ep, ev, tend_planes,
-                           outputs, cml);
-    case CLOUDSC_MIXED:
-      return launch_v<double, false, float>(st, variant, f, ngptot, nproma, klev, scratch, plude_in, ps, ep, ev,
-                                            tend_planes, outputs, cml);
+    case CLOUDSC_FP64: return launch_v<double, false>(rq);
+    case CLOUDSC_FP32: return dispatch_bools([&](auto FAST) { return launch_v<float, FAST>(rq); }, !rq.exact_libm);
+    case CLOUDSC_MIXED: return launch_v<double, false, float>(rq);
     default: return CLOUDSC_EINVAL;
   }
 }
@@ -810,27 +787,36 @@ int validate_run_args(int device, int precision, int variant, int ngptot, int np
   return validate_shape_args(precision, variant, ngptot, nproma, klev);
 }
 
-// plude_in: NULL = in place (the reference INOUT semantics); otherwise the
-// values of plude are read from there and the results written to f->plude.
-// ps: the parameter set of the launch (NULL = the device's default set).
-int gpu_run_impl(int device, void* stream, int precision, int variant, int ngptot, int nproma, int klev,
-                 const cloudsc_fields_t* f, void* scratch, const void* plude_in, const ParamSet* ps,
-                 KsegEpoch* ep, const LaunchEvents* lev, int tend_planes, int outputs, const cloudsc_tend_cml_t* cml) {
+int gpu_run_impl(int device, void* stream, const StepShape& sh, const cloudsc_fields_t* f, void* scratch,
+                 const StepForm& form, const RunContext& ctx) {
   // unknown option bits are an argument error here, before they are stripped (validate_run_args below sees
   // the variant's kind only): such a call must never launch
-  if (variant & ~(0xff | CLOUDSC_FP32_EXACT_LIBM)) return CLOUDSC_EINVAL;
-  const bool exact_libm = (variant & CLOUDSC_FP32_EXACT_LIBM) != 0;
-  variant = variant_kind(variant);
-  int rc = validate_run_args(device, precision, variant, ngptot, nproma, klev);
+  if (sh.variant & ~(0xff | CLOUDSC_FP32_EXACT_LIBM)) return CLOUDSC_EINVAL;
+  const int kind = variant_kind(sh.variant);
+  int rc = validate_run_args(device, sh.precision, kind, sh.ngptot, sh.nproma, sh.klev);
   if (rc) return rc;
-  if (!ps) ps = device_default_params(device);
+  const ParamSet* ps = ctx.ps ? ctx.ps : device_default_params(device);
   if (!ps || !ps->dev) return CLOUDSC_ENOINIT;
   if (ps->device != device) return CLOUDSC_EINVAL;
-  if (!f || !fields_complete(f, outputs, cml != nullptr)) return CLOUDSC_EINVAL;
+  if (!f || !fields_complete(f, form)) return CLOUDSC_EINVAL;
   HIPCHK(hipSetDevice(device));
-  hipStream_t st = (hipStream_t)stream;
-  return launch_precision(precision, st, variant, exact_libm, f, ngptot, nproma, klev, scratch, plude_in, *ps, ep, lev,
-                          tend_planes, outputs, cml);
+  return launch(sh.precision, LaunchRequest{(hipStream_t)stream, kind, (sh.variant & CLOUDSC_FP32_EXACT_LIBM) != 0, f,
+                                            sh.ngptot, sh.nproma, sh.klev, scratch, ctx.plude_in, *ps, ctx.ep, ctx.lev,
+                                            form});
+}
+
+// A form entry: every argument rule first -- the form's own (check_step_form, with the bits `need` of the entry), no
+// option bits (so no fp32 exact-libm), the shape, the support matrix, the fields the form touches, KSEG's workspace --
+// so that an argument error is CLOUDSC_EINVAL before any HIP call; then the run, the device's checks first
+static int gpu_run_form(int device, void* stream, const StepShape& sh, const cloudsc_fields_t* f, void* scratch,
+                        const StepForm& form, unsigned need) {
+  int rc = check_step_form(form, need, f);
+  if (rc) return rc;
+  if (sh.variant & ~0xff) return CLOUDSC_EINVAL;
+  if ((rc = validate_shape_args(sh.precision, sh.variant, sh.ngptot, sh.nproma, sh.klev))) return rc;
+  if (!form_exists(sh.variant, sh.precision, /*exact_libm=*/false, form_bits(form))) return CLOUDSC_EINVAL;   // no SCC form
+  if (!f || !fields_complete(f, form) || (sh.variant == CLOUDSC_VARIANT_KSEG && !scratch)) return CLOUDSC_EINVAL;
+  return gpu_run_impl(device, stream, sh, f, scratch, form, {});
 }
 
 int kseg_clock(int device, void* stream, void* scratch, bool reset, double* ghz, double* seconds) {
@@ -872,7 +858,7 @@ extern "C" {
 
 int cloudsc_gpu_run(int device, void* stream, int precision, int variant, int ngptot, int nproma,
                     int klev, const cloudsc_fields_t* f, void* scratch) {
-  return gpu_run_impl(device, stream, precision, variant, ngptot, nproma, klev, f, scratch, nullptr, nullptr);
+  return gpu_run_impl(device, stream, {precision, variant, ngptot, nproma, klev}, f, scratch, {}, {});
 }
 
 int cloudsc_tendbuf_bind(cloudsc_fields_t* f, int precision, int nproma, int klev, const void* buffer_tmp,
@@ -895,51 +881,21 @@ int cloudsc_tendbuf_bind(cloudsc_fields_t* f, int precision, int nproma, int kle
 
 int cloudsc_gpu_run_tendbuf(int device, void* stream, int precision, int variant, int ngptot, int nproma, int klev,
                             int tend_planes, const cloudsc_fields_t* f, void* scratch) {
-  // every argument rule first, the device's among them last: no HIP call before an argument error
-  if (tend_planes < CLOUDSC_TENDBUF_PLANES_MIN || tend_planes > CLOUDSC_TENDBUF_PLANES_MAX) return CLOUDSC_EINVAL;
-  if (variant & ~0xff) return CLOUDSC_EINVAL;   // no option bits (so no fp32 exact-libm)
-  const int kind = variant_kind(variant);
-  const int rc = validate_shape_args(precision, kind, ngptot, nproma, klev);
-  if (rc) return rc;
-  if (!form_exists(kind, precision, /*exact_libm=*/false, kFormTb)) return CLOUDSC_EINVAL;   // no SCC form
-  if (!f || !fields_complete(f) || (kind == CLOUDSC_VARIANT_KSEG && !scratch)) return CLOUDSC_EINVAL;
-  return gpu_run_impl(device, stream, precision, variant, ngptot, nproma, klev, f, scratch, nullptr, nullptr, nullptr,
-                      nullptr, tend_planes);
+  return gpu_run_form(device, stream, {precision, variant, ngptot, nproma, klev}, f, scratch, {tend_planes}, kFormTb);
 }
 
 int cloudsc_gpu_run_outputs(int device, void* stream, int precision, int variant, int outputs, int ngptot, int nproma,
                             int klev, const cloudsc_fields_t* f, void* scratch) {
-  if (!outputs_known(outputs)) return CLOUDSC_EINVAL;
-  if (outputs == CLOUDSC_OUTPUTS_ALL)   // cloudsc_gpu_run itself
-    return gpu_run_impl(device, stream, precision, variant, ngptot, nproma, klev, f, scratch, nullptr, nullptr);
-  // every argument rule first, the device's among them last: no HIP call before an argument error
-  if (variant & ~0xff) return CLOUDSC_EINVAL;   // no option bits (so no fp32 exact-libm)
-  const int kind = variant_kind(variant);
-  const int rc = validate_shape_args(precision, kind, ngptot, nproma, klev);
-  if (rc) return rc;
-  const unsigned form = kFormProg | (outputs_surface(outputs) ? kFormSurf : 0u);
-  if (!form_exists(kind, precision, /*exact_libm=*/false, form)) return CLOUDSC_EINVAL;   // no SCC form
-  if (!f || !fields_complete(f, outputs) || (kind == CLOUDSC_VARIANT_KSEG && !scratch)) return CLOUDSC_EINVAL;
-  return gpu_run_impl(device, stream, precision, variant, ngptot, nproma, klev, f, scratch, nullptr, nullptr, nullptr,
-                      nullptr, 0, outputs);
+  if (outputs == CLOUDSC_OUTPUTS_ALL)   // cloudsc_gpu_run itself: the device's checks first
+    return cloudsc_gpu_run(device, stream, precision, variant, ngptot, nproma, klev, f, scratch);
+  return gpu_run_form(device, stream, {precision, variant, ngptot, nproma, klev}, f, scratch, {0, outputs}, kFormProg);
 }
 
+// (with CLOUDSC_OUTPUTS_ALL the form, and so every rule, is cloudsc_gpu_run_tendbuf's)
 int cloudsc_gpu_run_tendbuf_outputs(int device, void* stream, int precision, int variant, int outputs, int ngptot,
                                     int nproma, int klev, int tend_planes, const cloudsc_fields_t* f, void* scratch) {
-  if (!outputs_known(outputs)) return CLOUDSC_EINVAL;
-  if (outputs == CLOUDSC_OUTPUTS_ALL)   // cloudsc_gpu_run_tendbuf itself
-    return cloudsc_gpu_run_tendbuf(device, stream, precision, variant, ngptot, nproma, klev, tend_planes, f, scratch);
-  // every argument rule first, the device's among them last: no HIP call before an argument error
-  if (tend_planes < CLOUDSC_TENDBUF_PLANES_MIN || tend_planes > CLOUDSC_TENDBUF_PLANES_MAX) return CLOUDSC_EINVAL;
-  if (variant & ~0xff) return CLOUDSC_EINVAL;   // no option bits (so no fp32 exact-libm)
-  const int kind = variant_kind(variant);
-  const int rc = validate_shape_args(precision, kind, ngptot, nproma, klev);
-  if (rc) return rc;
-  const unsigned form = kFormTb | kFormProg | (outputs_surface(outputs) ? kFormSurf : 0u);
-  if (!form_exists(kind, precision, /*exact_libm=*/false, form)) return CLOUDSC_EINVAL;   // no SCC form
-  if (!f || !fields_complete(f, outputs) || (kind == CLOUDSC_VARIANT_KSEG && !scratch)) return CLOUDSC_EINVAL;
-  return gpu_run_impl(device, stream, precision, variant, ngptot, nproma, klev, f, scratch, nullptr, nullptr, nullptr,
-                      nullptr, tend_planes, outputs);
+  return gpu_run_form(device, stream, {precision, variant, ngptot, nproma, klev}, f, scratch, {tend_planes, outputs},
+                      kFormTb);
 }
 
 int cloudsc_tendbuf_bind_cml(cloudsc_tend_cml_t* cml, int precision, int nproma, int klev, void* buffer_cml) {
@@ -954,22 +910,12 @@ int cloudsc_tendbuf_bind_cml(cloudsc_tend_cml_t* cml, int precision, int nproma,
   return CLOUDSC_OK;
 }
 
+// (kFormProg: CLOUDSC_OUTPUTS_ALL is refused)
 int cloudsc_gpu_run_tendbuf_cml(int device, void* stream, int precision, int variant, int outputs, int ngptot,
                                 int nproma, int klev, int tend_planes, const cloudsc_fields_t* f,
                                 const cloudsc_tend_cml_t* cml, void* scratch) {
-  // every argument rule first, the device's among them last: no HIP call before an argument error
-  if (outputs != CLOUDSC_OUTPUTS_PROGNOSTIC && outputs != CLOUDSC_OUTPUTS_SURFACE) return CLOUDSC_EINVAL;   // not ALL
-  if (tend_planes < CLOUDSC_TENDBUF_PLANES_MIN || tend_planes > CLOUDSC_TENDBUF_PLANES_MAX) return CLOUDSC_EINVAL;
-  if (variant & ~0xff) return CLOUDSC_EINVAL;   // no option bits (so no fp32 exact-libm)
-  const int kind = variant_kind(variant);
-  const int rc = validate_shape_args(precision, kind, ngptot, nproma, klev);
-  if (rc) return rc;
-  const unsigned form = kFormCml | kFormTb | kFormProg | (outputs_surface(outputs) ? kFormSurf : 0u);
-  if (!form_exists(kind, precision, /*exact_libm=*/false, form)) return CLOUDSC_EINVAL;   // no SCC form
-  if (!f || !fields_complete(f, outputs, /*cml=*/true) || (kind == CLOUDSC_VARIANT_KSEG && !scratch)) return CLOUDSC_EINVAL;
-  if (check_tend_cml(f, cml)) return CLOUDSC_EINVAL;
-  return gpu_run_impl(device, stream, precision, variant, ngptot, nproma, klev, f, scratch, nullptr, nullptr, nullptr,
-                      nullptr, tend_planes, outputs, cml);
+  return gpu_run_form(device, stream, {precision, variant, ngptot, nproma, klev}, f, scratch,
+                      {tend_planes, outputs, cml}, kFormCml | kFormTb | kFormProg);
 }
 
 int cloudsc_gpu_check(int device, void* stream, int variant, void* scratch) {

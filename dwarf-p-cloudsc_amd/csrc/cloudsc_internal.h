@@ -6,9 +6,15 @@
 
 #include <cstdint>
 #include <functional>
+#include <type_traits>
 
 #include "cloudsc_amd.h"
 #include "cloudsc_fields.def"
+
+namespace cloudsc {
+// the bits of a k-caching kernel's form (KForm, cloudsc_kcache.h)
+enum : unsigned { kFormPack = 1u, kFormTb = 2u, kFormProg = 4u, kFormSurf = 8u, kFormCml = 16u };
+}  // namespace cloudsc
 
 namespace cloudsc_impl {
 
@@ -100,12 +106,60 @@ constexpr bool output_selected(int member, int outputs) {
 }
 // The four local tendency members (consecutive): the cumulative tendency form never touches them
 constexpr bool is_tendency_loc(int member) { return member >= CLOUDSC_M_tendency_loc_t && member <= CLOUDSC_M_tendency_loc_cld; }
-// every pointer the kernel reads or writes (aerosol inputs, with CLOUDSC_OUTPUTS_PROGNOSTIC the ten
-// diagnostic fluxes and, in the cumulative tendency form `cml`, tendency_loc_t/q/a/cld excepted) is set
-bool fields_complete(const cloudsc_fields_t* f, int outputs = CLOUDSC_OUTPUTS_ALL, bool cml = false);
-// the pointer rules of a cumulative tendency form's planes: cml and its four members set, none of them a
-// tendency_tmp_* or tendency_loc_* member of f (pointer equality only)
-int check_tend_cml(const cloudsc_fields_t* f, const cloudsc_tend_cml_t* cml);
+
+// The form of one step, on the GPU and on the CPU: what every run entry says beyond the shape.  The default is
+// cloudsc_gpu_run's: separate tendency arrays, every output, the local tendencies stored.
+struct StepForm {
+  int tend_planes = 0;                      // != 0: tendency members are planes of packed buffers
+  int outputs = CLOUDSC_OUTPUTS_ALL;        // CLOUDSC_OUTPUTS_*
+  const cloudsc_tend_cml_t* cml = nullptr;  // the cumulative tendency planes
+};
+// a form's kForm* bits (kFormPack is the launch's own, not a form's)
+constexpr unsigned form_bits(bool tb, bool prog, bool surf, bool cml) {
+  using namespace cloudsc;
+  return (tb ? kFormTb : 0u) | (prog ? kFormProg : 0u) | (surf ? kFormSurf : 0u) | (cml ? kFormCml : 0u);
+}
+constexpr unsigned form_bits(const StepForm& s) {
+  return form_bits(s.tend_planes != 0, outputs_prognostic(s.outputs), outputs_surface(s.outputs), s.cml != nullptr);
+}
+// The support matrix, the part the bits alone decide: the surface-fluxes form is a prognostic-outputs form, the
+// cumulative tendency form a tendency buffer, prognostic-outputs form (KForm's static_asserts)
+constexpr bool form_bits_consistent(unsigned form) {
+  using namespace cloudsc;
+  return (!(form & kFormSurf) || (form & kFormProg)) && (!(form & kFormCml) || ((form & kFormTb) && (form & kFormProg)));
+}
+// The support matrix: whether (variant kind, precision, fp32 exact-libm, form bits) has a GPU kernel.  MIXED runs on the
+// k-caching variants only; so do the forms, alone or combined, which fp32 has with its default exp/pow only; the SCC
+// variants are plain.  (The exact-libm bit means nothing outside fp32; every k-caching kernel has its packed twin, so
+// kFormPack is not asked about.)  The CPU variant has every consistent form (cloudsc_cpu.hip).
+constexpr bool form_exists(int kind, int precision, bool exact_libm, unsigned form) {
+  const bool kcaching = kind == CLOUDSC_VARIANT_KCACHE || kind == CLOUDSC_VARIANT_KSEG;
+  if (!kcaching && kind != CLOUDSC_VARIANT_SCC && kind != CLOUDSC_VARIANT_SCC_PRIVATE) return false;
+  if (precision != CLOUDSC_FP64 && precision != CLOUDSC_FP32 && precision != CLOUDSC_MIXED) return false;
+  if (precision == CLOUDSC_MIXED && !kcaching) return false;
+  if (!form_bits_consistent(form)) return false;
+  if (form & ~cloudsc::kFormPack) return kcaching && !(precision == CLOUDSC_FP32 && exact_libm);
+  return true;
+}
+// runtime conditions as compile-time constants, in one place:
+// dispatch_bools(f, c0, c1, ...) calls f(std::bool_constant<c0>{}, std::bool_constant<c1>{}, ...)
+template <bool... Bs, typename Fn>
+int dispatch_bools(Fn&& f) {
+  return f(std::integral_constant<bool, Bs>{}...);
+}
+template <bool... Bs, typename Fn, typename... Rest>
+int dispatch_bools(Fn&& f, bool c, Rest... rest) {
+  return c ? dispatch_bools<Bs..., true>(f, rest...) : dispatch_bools<Bs..., false>(f, rest...);
+}
+
+// every pointer the step reads or writes (aerosol inputs, with CLOUDSC_OUTPUTS_PROGNOSTIC the ten diagnostic
+// fluxes and, in the cumulative tendency form, tendency_loc_t/q/a/cld excepted) is set
+bool fields_complete(const cloudsc_fields_t* f, const StepForm& form = {});
+// The rules of a form that need neither a shape nor a device, the same for the GPU and the CPU entries: a known
+// selection, the bits `need` that the entry stands for, bits that go together, a plane count in range, and the
+// pointer rules of the cumulative planes -- cml's four members set, none of them a tendency_tmp_* or
+// tendency_loc_* member of f (pointer equality only).  CLOUDSC_EINVAL or CLOUDSC_OK.
+int check_step_form(const StepForm& form, unsigned need, const cloudsc_fields_t* f);
 // Host record of one KSEG workspace owned by a caller that launches on it in
 // stream order (a state): after the first launch zeroes it, later launches
 // continue its ticket counter and flag stamps instead of zeroing it again.
@@ -119,16 +173,23 @@ struct KsegEpoch {
 struct LaunchEvents {
   hipEvent_t start, stop;
 };
-// cloudsc_gpu_run with an optional separate source of plude (NULL = in place),
-// an explicit parameter set (NULL = the device's default set), an optional
-// KSEG workspace record (NULL = zero the workspace before every KSEG launch)
-// and optional events timing the physics kernel (NULL = none); tend_planes != 0:
-// the tendency members of f are planes of packed buffers (cloudsc_gpu_run_tendbuf); outputs: CLOUDSC_OUTPUTS_*
-// (cloudsc_gpu_run_outputs); cml: the cumulative tendency form (cloudsc_gpu_run_tendbuf_cml)
-int gpu_run_impl(int device, void* stream, int precision, int variant, int ngptot, int nproma, int klev,
-                 const cloudsc_fields_t* f, void* scratch, const void* plude_in, const ParamSet* ps,
-                 KsegEpoch* ep = nullptr, const LaunchEvents* lev = nullptr, int tend_planes = 0,
-                 int outputs = CLOUDSC_OUTPUTS_ALL, const cloudsc_tend_cml_t* cml = nullptr);
+// The shape arguments of a run entry; `variant` may carry option bits (CLOUDSC_FP32_EXACT_LIBM)
+struct StepShape {
+  int precision, variant, ngptot, nproma, klev;
+};
+// What the library's own callers add to a run: a separate source of plude (NULL = in place, the reference INOUT
+// semantics; otherwise plude is read from there and the result written to f->plude), an explicit parameter set
+// (NULL = the device's default set), a KSEG workspace record (NULL = zero the workspace before every KSEG launch)
+// and events timing the physics kernel (NULL = none)
+struct RunContext {
+  const void* plude_in = nullptr;
+  const ParamSet* ps = nullptr;
+  KsegEpoch* ep = nullptr;
+  const LaunchEvents* lev = nullptr;
+};
+// cloudsc_gpu_run in the form `form`: the device checks, the argument rules, the launch
+int gpu_run_impl(int device, void* stream, const StepShape& shape, const cloudsc_fields_t* f, void* scratch,
+                 const StepForm& form, const RunContext& ctx);
 // the kernel variant of a `variant` argument without its option bits (CLOUDSC_FP32_EXACT_LIBM)
 inline int variant_kind(int variant) { return variant & 0xff; }
 // waits for `stream` and returns CLOUDSC_EHANDOFF if the last KSEG launch on

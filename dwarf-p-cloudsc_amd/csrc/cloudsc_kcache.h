@@ -27,6 +27,7 @@
 // fp64 output is the reference kernel's, bit for bit.
 #pragma once
 #include "cloudsc_dev.h"
+#include "cloudsc_internal.h"
 #define CLOUDSC_PARAMS_HERE const PT& c = *(const PT*)launder_uniform(cpar)
 
 namespace cloudsc {
@@ -80,8 +81,8 @@ struct KArgsCML : KArgsTB<real, store> {
 //              stored once, after the last level, as surface fields
 //   kFormCml   the cumulative tendency form (KArgsCML, load_cml, store_level_cml): kFormTb and kFormProg
 // The kernel entries, the bodies below and the host's launch path all take the
-// descriptor and read its members by name.
-enum : unsigned { kFormPack = 1u, kFormTb = 2u, kFormProg = 4u, kFormSurf = 8u, kFormCml = 16u };
+// descriptor and read its members by name.  (The bits themselves are in cloudsc_internal.h, beside the
+// support matrix that the GPU and the CPU entries share.)
 template <typename Real, typename Store, int WAVES, int PF, bool AER, bool LDSC, bool FAST, unsigned FORM = 0u>
 struct KForm {
   using real = Real;

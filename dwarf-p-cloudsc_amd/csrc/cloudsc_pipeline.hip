@@ -476,8 +476,8 @@ int run_on_engines(cloudsc_host_pipeline* p, int variant, int vk, double* ms) {
     const long long col0 = (long long)b0 * p->nproma;
     const int ncols = (int)((col0 + (long long)nb * p->nproma <= p->ngptot) ? (long long)nb * p->nproma
                                                                             : p->ngptot - col0);
-    if ((rc = gpu_run_impl(p->device, p->st_k, p->precision, variant, ncols, p->nproma, p->klev, &s.dev, s.scratch,
-                           nullptr, &p->params)))
+    if ((rc = gpu_run_impl(p->device, p->st_k, {p->precision, variant, ncols, p->nproma, p->klev}, &s.dev, s.scratch,
+                           {}, {nullptr, &p->params})))
       break;
     if (hipEventRecord(s.k_done, p->st_k) != hipSuccess) { rc = CLOUDSC_EHIP; break; }
   }
@@ -697,8 +697,8 @@ int cloudsc_host_pipeline_run(cloudsc_host_pipeline_t* p, int variant, double* m
     // kernel: after its inputs are in and the slot's previous outputs are out
     HIPCHK(hipStreamWaitEvent(p->st_k, s.in_done, 0));
     if (reuse) HIPCHK(hipStreamWaitEvent(p->st_k, s.out_done, 0));
-    rc = gpu_run_impl(p->device, p->st_k, p->precision, variant, ncols, p->nproma, p->klev, &s.dev, s.scratch,
-                      nullptr, &p->params);
+    rc = gpu_run_impl(p->device, p->st_k, {p->precision, variant, ncols, p->nproma, p->klev}, &s.dev, s.scratch, {},
+                      {nullptr, &p->params});
     if (rc) break;
     HIPCHK(hipEventRecord(s.k_done, p->st_k));
     // outputs (and plude): after the kernel
@@ -1024,8 +1024,8 @@ extern "C" int cloudsc_host_run(int device, int precision, int variant, int ngpt
       }
     }
   }
-  rc = gpu_run_impl(device, ctx->st, precision, variant, ngptot, nproma, klev, &dev, ctx->scratch, nullptr,
-                    &ctx->params);
+  rc = gpu_run_impl(device, ctx->st, {precision, variant, ngptot, nproma, klev}, &dev, ctx->scratch, {},
+                    {nullptr, &ctx->params});
   if (rc) {
     (void)hipStreamSynchronize(ctx->st);
     return rc;

@@ -193,9 +193,10 @@ constexpr int kPlaceInputSets = 4;               // input sets (place_inputs): t
 float probe_kernel(cloudsc_gpu_state* s, const cloudsc_fields_t& f, const void* plude_in = nullptr) {
   float best = -1.f;
   const LaunchEvents lev{s->ev0, s->ev1};
+  const RunContext ctx{plude_in ? plude_in : s->plude_pristine, &s->params, &s->kseg_epoch, &lev};
   for (int r = 0; r < 3; r++) {
-    if (gpu_run_impl(s->device, s->stream, s->precision, CLOUDSC_VARIANT_KSEG, s->ngptot, s->nproma, s->klev, &f,
-                     s->kseg_ws, plude_in ? plude_in : s->plude_pristine, &s->params, &s->kseg_epoch, &lev) != CLOUDSC_OK ||
+    if (gpu_run_impl(s->device, s->stream, {s->precision, CLOUDSC_VARIANT_KSEG, s->ngptot, s->nproma, s->klev}, &f,
+                     s->kseg_ws, {}, ctx) != CLOUDSC_OK ||
         hipEventSynchronize(s->ev1) != hipSuccess)
       return -1.f;
     float t = 0.f;
@@ -653,8 +654,8 @@ int cloudsc_debug_launch_forms(cloudsc_gpu_state_t* s, int variant, int reps, in
     int r0 = CLOUDSC_OK;
     for (int r = 0; r < reps && r0 == CLOUDSC_OK; r++) {
       const LaunchEvents lev{ev[2 * r], ev[2 * r + 1]};
-      r0 = gpu_run_impl(s->device, s->stream, s->precision, variant, s->ngptot, s->nproma, s->klev, &s->f, scratch,
-                        s->plude_pristine, &s->params, &s->kseg_epoch, events ? &lev : nullptr);
+      r0 = gpu_run_impl(s->device, s->stream, {s->precision, variant, s->ngptot, s->nproma, s->klev}, &s->f, scratch, {},
+                        {s->plude_pristine, &s->params, &s->kseg_epoch, events ? &lev : nullptr});
     }
     return r0;
   };
@@ -729,8 +730,8 @@ static int state_launches(cloudsc_gpu_state_t* s, int variant, int reps, float* 
     // out of place: every step reads the pristine plude and writes the INOUT
     // result to f.plude, so repeated steps see the same input with no restore copy
     const LaunchEvents lev{ms ? ev[2 * r] : nullptr, ms ? ev[2 * r + 1] : nullptr};
-    rc = gpu_run_impl(s->device, s->stream, s->precision, variant, s->ngptot, s->nproma, s->klev, &s->f, scratch,
-                      s->plude_pristine, &s->params, &s->kseg_epoch, ms ? &lev : nullptr);
+    rc = gpu_run_impl(s->device, s->stream, {s->precision, variant, s->ngptot, s->nproma, s->klev}, &s->f, scratch, {},
+                      {s->plude_pristine, &s->params, &s->kseg_epoch, ms ? &lev : nullptr});
   }
   if (rc == CLOUDSC_OK && span_ms) {
     hipError_t re = hipEventRecord(ev[1], s->stream);
