@@ -147,6 +147,15 @@ class TendCml(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("t", "q", "a", "cld")]
 
 
+SPP_SLOTS = ("ramid", "rcldiff", "rclcrit", "rlcritsnow", "rpecons")
+
+
+class Spp(C.Structure):
+    """cloudsc_spp_t: per-column parameter multipliers, each a surface field [nblocks][nproma] in the storage
+    type (the layout of plsm), or None where the parameter is not perturbed."""
+    _fields_ = [(n, C.c_void_p) for n in SPP_SLOTS]
+
+
 class Placement(C.Structure):
     """cloudsc_placement_t: what a placement search cost and found."""
     _fields_ = [("probe_first_ms", C.c_float), ("probe_final_ms", C.c_float), ("tries", C.c_int),
@@ -567,6 +576,10 @@ def gpu_lib(path: Optional[str] = None):
             C.POINTER(Fields), C.c_int, C.POINTER(TendCml)]
         lib.cloudsc_cpu_fields_accumulate_tendbuf.argtypes = [C.c_int] * 6 + [C.POINTER(Fields), C.c_int,
                                                                               C.POINTER(TendCml)]
+    if hasattr(lib, "cloudsc_gpu_run_spp"):   # (likewise: the per-column parameter multipliers)
+        lib.cloudsc_gpu_run_spp.argtypes = [C.c_int, C.c_void_p] + [C.c_int] * 6 + [C.POINTER(Fields), C.POINTER(Spp),
+                                                                                    C.c_void_p]
+        lib.cloudsc_cpu_run_spp.argtypes = [C.c_int] * 6 + [C.POINTER(Params), C.POINTER(Fields), C.POINTER(Spp)]
     if hasattr(lib, "cloudsc_fields_compare_outputs"):   # (likewise: the forms for a set of one output selection)
         lib.cloudsc_fields_convert_outputs.argtypes = [C.c_int, C.c_void_p] + [C.c_int] * 5 + [
             C.POINTER(Fields), C.c_int, C.c_int, C.POINTER(Fields)]
@@ -838,6 +851,25 @@ def cpu_run_tendbuf_cml(params: "Params", f: "Fields", cml: "TendCml", precision
                                                 C.byref(params), C.byref(f), C.byref(cml)))
 
 
+def gpu_run_spp(f: "Fields", spp: "Spp", precision: int, variant: int, outputs: int, ngptot: int, nproma: int,
+                klev: int, scratch=None, device: int = 0, stream=None) -> None:
+    """cloudsc_gpu_run_spp: gpu_run_outputs (OUTPUTS_ALL or OUTPUTS_PROGNOSTIC) with per-column multipliers of
+    RAMID, RCLDIFF, RCLCRIT_SEA/LAND, RLCRITSNOW and RPECONS: `spp` holds DEVICE surface fields [nblocks][nproma]
+    in the storage type, or None where a parameter is not perturbed (at least one is set).  Each column
+    has the bits of the ordinary step under its own host-scaled parameter set.  Asynchronous."""
+    require_blocked(f, "gpu_run_spp")
+    check(gpu_lib().cloudsc_gpu_run_spp(device, stream, precision, variant, outputs, ngptot, nproma, klev, C.byref(f),
+                                        C.byref(spp), scratch))
+
+
+def cpu_run_spp(params: "Params", f: "Fields", spp: "Spp", precision: int, outputs: int, ngptot: int, nproma: int,
+                klev: int, nthreads: int = 0) -> None:
+    """cloudsc_cpu_run_spp: the same on HOST memory (fp64 and mixed)."""
+    require_blocked(f, "cpu_run_spp")
+    check(gpu_lib().cloudsc_cpu_run_spp(nthreads, precision, outputs, ngptot, nproma, klev, C.byref(params),
+                                        C.byref(f), C.byref(spp)))
+
+
 def accumulate_tendbuf(loc: "Fields", cml: "TendCml", precision: int, ngptot: int, nproma: int, klev: int,
                        loc_tend_planes: int, cml_tend_planes: int, device: int = 0, stream=None) -> None:
     """cloudsc_fields_accumulate_tendbuf: cml += tendency_loc_* of `loc` over the seven planes on the device,
@@ -986,8 +1018,8 @@ def validate_host_state(ds: "Dataset", st: "HostState") -> float:
 
 
 # the translation unit of the CLOUDSC kernels (cloudsc_gpu.hip and what it includes)
-KERNEL_SOURCES = ("cloudsc_gpu.hip", "cloudsc_kcache.h", "cloudsc_scc.h", "cloudsc_dev.h", "cloudsc_params.h",
-                  "cloudsc_libm.h", "cloudsc_libm_tab.h", "cloudsc_internal.h", "cloudsc_fields.def")
+KERNEL_SOURCES = ("cloudsc_gpu.hip", "cloudsc_kcache.h", "cloudsc_physics_level.inc", "cloudsc_scc.h", "cloudsc_dev.h",
+                  "cloudsc_params.h", "cloudsc_libm.h", "cloudsc_libm_tab.h", "cloudsc_internal.h", "cloudsc_fields.def")
 
 
 def kernel_source_hash() -> str:

@@ -41,9 +41,10 @@ struct HostColumn {
 // TB: the tendency members are planes of packed buffers and A is a KArgsTB (cloudsc_kcache.h);
 // PROG: the prognostic-outputs form, the ten diagnostic flux members of A never touched (flux_level);
 // SURF: the surface-fluxes form, the other four flux members surface fields written after the last level;
-// CML: the cumulative tendency form, A a KArgsCML and the local tendencies added to its planes (load_cml, store_level_cml)
-template <typename real, bool AER, bool TB, bool PROG, bool SURF, bool CML, typename S>
-void run_block(const DevParams<real>& c, const KArgs<real, S>& A, int b, std::vector<HostColumn<real>>& col) {
+// CML: the cumulative tendency form, A a KArgsCML and the local tendencies added to its planes (load_cml, store_level_cml);
+// SPP: the per-column multiplier form, A a KArgsSPP (SppCol: the multipliers read from the host fields where they are used)
+template <typename real, bool AER, bool TB, bool PROG, bool SURF, bool CML, bool SPP, typename S>
+void run_block(const DevParamsSpp<real>& c, const KArgs<real, S>& A, int b, std::vector<HostColumn<real>>& col) {
   const int nproma = A.nproma, klev = A.klev;
   const int bsize = std::min(nproma, A.ngptot - b * nproma);
   const size_t u1 = (size_t)b * nproma;
@@ -52,12 +53,19 @@ void run_block(const DevParams<real>& c, const KArgs<real, S>& A, int b, std::ve
   const size_t u3 = (size_t)b * 5 * klev * nproma;
   const int ncldtop0 = c.ncldtop - 1;
   const int l1 = 1 < klev ? 1 : klev - 1;
+  using Spp = typename std::conditional<SPP, SppCol<real, S, const KArgs<real, S>*, unsigned>, NoSpp>::type;
+  const auto spp_of = [&](unsigned lo) {   // the column's own parameters (nothing of them is kept: formed where asked for)
+    Spp spp;
+    if constexpr (SPP) { spp.ka = &A; spp.u1 = u1; spp.lane = lo; }
+    return spp;
+  };
   for (int jl = 0; jl < bsize; jl++) {
     const unsigned lo = (unsigned)jl * (unsigned)sizeof(S);
     HostColumn<real>& h = col[jl];
     init_carry<real, PROG>(h.cs);
     flux_top<PROG, SURF>(c, A, uh, lo);
     h.cc = column_constants(c, A, u1, uh, lo);
+    if constexpr (SPP) h.cc.kk_lcrit = h.cc.kk_lcrit * spp_of(lo).mult(SPP_RCLCRIT);
     h.nb.paph_k = ldg(A.paph, uh, lo);
     h.nb.paph_n = ldg(A.paph, uh + (size_t)nproma, lo);
     h.nb.pmfu_k = ldg(A.pmfu, u2, lo);
@@ -82,7 +90,11 @@ void run_block(const DevParams<real>& c, const KArgs<real, S>& A, int b, std::ve
       po.plude_k = cur.plude;
       po.atend = R(0.0);
       po.zcovptot_out = R(0.0);
-      if (physics) physics_level(c, k, klev, ncldtop0, cur, h.nb, h.cc, ls, h.cs, po);
+      if constexpr (SPP) {
+        if (physics) physics_level_spp(c, k, klev, ncldtop0, cur, h.nb, h.cc, ls, h.cs, po, NoMidHook{}, spp_of(lo));
+      } else {
+        if (physics) physics_level(c, k, klev, ncldtop0, cur, h.nb, h.cc, ls, h.cs, po);
+      }
       if constexpr (CML) {
         CmlIn<real> cm;
         load_cml(cm, A, u2, k, klev, nproma, lo);
@@ -130,13 +142,22 @@ int cpu_run(int ngptot, int nproma, int klev, const cloudsc_params_t* params, co
   const bool aer = params->laericesed || params->laericeauto;
   if (aer && (!f->pre_ice || !f->picrit_aer || !f->pnice)) return CLOUDSC_EINVAL;
   if (nthreads <= 0 && (th.thread_seconds || th.thread_blocks || th.thread_columns)) return CLOUDSC_EINVAL;
-  const DevParams<double> c = fold_params<double>(*params);
+  const DevParamsSpp<double> c = fold_params<double>(*params);
   KArgsCML<double, S> A;
   static_cast<KArgs<double, S>&>(A) = make_kargs<double, S>(f, ngptot, nproma, klev, nullptr);
   A.tend_planes = form.tend_planes;   // 0: separate arrays
   A.cml_t = A.cml_q = A.cml_a = A.cml_cld = nullptr;
   if (const cloudsc_tend_cml_t* cml = form.cml) {
     A.cml_t = (S*)cml->t; A.cml_q = (S*)cml->q; A.cml_a = (S*)cml->a; A.cml_cld = (S*)cml->cld;
+  }
+  // the per-column multiplier form has its own argument block (never together with the tendency buffer forms)
+  KArgsSPP<double, S> M;
+  static_cast<KArgs<double, S>&>(M) = A;
+  for (const S*& m : M.mult) m = nullptr;
+  if (const cloudsc_spp_t* spp = form.spp) {
+    M.mult[SPP_RAMID] = (const S*)spp->ramid; M.mult[SPP_RCLDIFF] = (const S*)spp->rcldiff;
+    M.mult[SPP_RCLCRIT] = (const S*)spp->rclcrit; M.mult[SPP_RLCRITSNOW] = (const S*)spp->rlcritsnow;
+    M.mult[SPP_RPECONS] = (const S*)spp->rpecons;
   }
   const int nblocks = ngptot / nproma + (ngptot % nproma ? 1 : 0);
   if (nthreads <= 0) nthreads = (int)std::max(1u, std::thread::hardware_concurrency());
@@ -156,14 +177,17 @@ int cpu_run(int ngptot, int nproma, int klev, const cloudsc_params_t* params, co
     std::vector<HostColumn<double>> col((size_t)nproma);
     int icalls = 0, igpc = 0;
     for (int b = next.fetch_add(1); b < nblocks; b = next.fetch_add(1)) {
-      // the run_block of the form: the sixteen whose bits go together (form_bits_consistent), as on the GPU
+      // the run_block of the form: those whose bits go together (form_bits_consistent), as on the GPU
       dispatch_bools(
-          [&](auto AER, auto TB, auto PROG, auto SURF, auto CML) {
-            if constexpr (form_bits_consistent(form_bits(TB, PROG, SURF, CML)))
-              run_block<double, AER, TB, PROG, SURF, CML>(c, A, b, col);
+          [&](auto AER, auto TB, auto PROG, auto SURF, auto CML, auto SPP) {
+            if constexpr (form_bits_consistent(form_bits(TB, PROG, SURF, CML, SPP))) {
+              if constexpr (SPP) run_block<double, AER, TB, PROG, SURF, CML, SPP>(c, M, b, col);
+              else run_block<double, AER, TB, PROG, SURF, CML, SPP>(c, A, b, col);
+            }
             return 0;
           },
-          aer, (bits & kFormTb) != 0, (bits & kFormProg) != 0, (bits & kFormSurf) != 0, (bits & kFormCml) != 0);
+          aer, (bits & kFormTb) != 0, (bits & kFormProg) != 0, (bits & kFormSurf) != 0, (bits & kFormCml) != 0,
+          (bits & kFormSpp) != 0);
       icalls++;
       igpc += std::min(nproma, ngptot - b * nproma);
     }
@@ -245,4 +269,10 @@ extern "C" int cloudsc_cpu_run_tendbuf_cml(int nthreads, int precision, int outp
                                            const cloudsc_tend_cml_t* cml) {
   return cpu_run_form(precision, ngptot, nproma, klev, params, f, {tend_planes, outputs, cml},
                       kFormCml | kFormTb | kFormProg, {nthreads});
+}
+
+extern "C" int cloudsc_cpu_run_spp(int nthreads, int precision, int outputs, int ngptot, int nproma, int klev,
+                                   const cloudsc_params_t* params, const cloudsc_fields_t* f,
+                                   const cloudsc_spp_t* spp) {
+  return cpu_run_form(precision, ngptot, nproma, klev, params, f, {0, outputs, nullptr, spp}, kFormSpp, {nthreads});
 }

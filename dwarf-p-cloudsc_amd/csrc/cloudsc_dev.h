@@ -60,6 +60,13 @@ struct DevParams {
   real rd_rcp, rtaumel_rcp, rdepliqrefdepth_rcp, rvrfactor_rcp;
   int nssopt, ncldtop, laericesed, laericeauto;
 };
+// The block in memory: DevParams, and appended at its end (every member above keeps its offset) the raw parameters
+// behind zldifdt0, zldifdt_conv and rg_rpecons, for the per-column multiplier form (SppCol, cloudsc_kcache.h), which
+// folds them per column.  Only that form's kernels see this type: every other kernel reads a DevParams, as before.
+template <typename real>
+struct DevParamsSpp : DevParams<real> {
+  real rcldiff, rcldiff_convi, rpecons;
+};
 
 // The parameter block as the kernels see it: the same memory, with the choice
 // of the single-precision exp/pow forms carried in the type (FAST = the
@@ -69,29 +76,30 @@ struct DevParams {
 // the reference's algorithms (FAST is only instantiated for float).
 // VREG: the block copied into VGPRs for the level loop (fp32 k-caching kernels,
 // kcache_levels) instead of being read with a scalar load at each use.
-template <typename real, bool FAST, bool VREG = false>
-struct DevParamsT : DevParams<real> {};
+// SPP: the block with its appended raw parameters (DevParamsSpp).
+template <typename real, bool FAST, bool VREG = false, bool SPP = false>
+struct DevParamsT : std::conditional<SPP, DevParamsSpp<real>, DevParams<real>>::type {};
 template <typename P>
 struct LibmFast {
   static constexpr bool value = false;
 };
-template <bool VREG>
-struct LibmFast<DevParamsT<float, true, VREG>> {
+template <bool VREG, bool SPP>
+struct LibmFast<DevParamsT<float, true, VREG, SPP>> {
   static constexpr bool value = true;
 };
 template <typename P>
 struct ParamsInVgprs {
   static constexpr bool value = false;
 };
-template <typename real, bool FAST>
-struct ParamsInVgprs<DevParamsT<real, FAST, true>> {
+template <typename real, bool FAST, bool SPP>
+struct ParamsInVgprs<DevParamsT<real, FAST, true, SPP>> {
   static constexpr bool value = true;
 };
 template <typename P>
 struct WithVgprParams;
-template <typename real, bool FAST, bool VREG>
-struct WithVgprParams<DevParamsT<real, FAST, VREG>> {
-  using type = DevParamsT<real, FAST, true>;
+template <typename real, bool FAST, bool VREG, bool SPP>
+struct WithVgprParams<DevParamsT<real, FAST, VREG, SPP>> {
+  using type = DevParamsT<real, FAST, true, SPP>;
 };
 
 // The phase functions of the physics (cloudsc_kcache.h) and the helpers below

@@ -53,8 +53,8 @@ void set_error_text(const char* text) { snprintf(g_hip_err, sizeof(g_hip_err), "
 namespace {
 
 // device layout of one parameter set: the fp64 mirror, then the fp32 one
-constexpr size_t kSpOffset = (sizeof(DevParams<double>) + 255) & ~(size_t)255;
-constexpr size_t kParamBlockBytes = kSpOffset + sizeof(DevParams<float>);
+constexpr size_t kSpOffset = (sizeof(DevParamsSpp<double>) + 255) & ~(size_t)255;
+constexpr size_t kParamBlockBytes = kSpOffset + sizeof(DevParamsSpp<float>);
 
 // the per-device default parameter sets (cloudsc_gpu_init)
 std::mutex g_default_mu;
@@ -81,8 +81,8 @@ int param_set_upload(ParamSet* ps, int device, const cloudsc_params_t* p) {
     if (e != hipSuccess) { ps->dev = nullptr; hip_fail(e, "hipMalloc(params)"); return CLOUDSC_ENOMEM; }
   }
   std::vector<char> blk(kParamBlockBytes, 0);
-  const DevParams<double> dp = fold_params<double>(*p);
-  const DevParams<float> sp = fold_params<float>(*p);
+  const DevParamsSpp<double> dp = fold_params<double>(*p);
+  const DevParamsSpp<float> sp = fold_params<float>(*p);
   std::memcpy(blk.data(), &dp, sizeof(dp));
   std::memcpy(blk.data() + kSpOffset, &sp, sizeof(sp));
   // hipMemcpy from pageable memory may return before the bytes have reached the
@@ -147,15 +147,27 @@ int check_step_form(const StepForm& form, unsigned need, const cloudsc_fields_t*
   if (!outputs_known(form.outputs) || (bits & need) != need || !form_bits_consistent(bits)) return CLOUDSC_EINVAL;
   if (form.tend_planes && (form.tend_planes < CLOUDSC_TENDBUF_PLANES_MIN || form.tend_planes > CLOUDSC_TENDBUF_PLANES_MAX))
     return CLOUDSC_EINVAL;
-  const cloudsc_tend_cml_t* cml = form.cml;
-  if (!cml) return CLOUDSC_OK;
-  if (!f || !cml->t || !cml->q || !cml->a || !cml->cld) return CLOUDSC_EINVAL;
-  const void* const mine[4] = {cml->t, cml->q, cml->a, cml->cld};
-  const void* const theirs[8] = {f->tendency_tmp_t,   f->tendency_tmp_q, f->tendency_tmp_a, f->tendency_tmp_cld,
-                                 f->tendency_loc_t,   f->tendency_loc_q, f->tendency_loc_a, f->tendency_loc_cld};
-  for (const void* a : mine)
-    for (const void* b : theirs)
-      if (a == b) return CLOUDSC_EINVAL;
+  if (const cloudsc_tend_cml_t* cml = form.cml) {
+    if (!f || !cml->t || !cml->q || !cml->a || !cml->cld) return CLOUDSC_EINVAL;
+    const void* const mine[4] = {cml->t, cml->q, cml->a, cml->cld};
+    const void* const theirs[8] = {f->tendency_tmp_t,   f->tendency_tmp_q, f->tendency_tmp_a, f->tendency_tmp_cld,
+                                   f->tendency_loc_t,   f->tendency_loc_q, f->tendency_loc_a, f->tendency_loc_cld};
+    for (const void* a : mine)
+      for (const void* b : theirs)
+        if (a == b) return CLOUDSC_EINVAL;
+  }
+  if (const cloudsc_spp_t* spp = form.spp) {
+    const void* const mine[5] = {spp->ramid, spp->rcldiff, spp->rclcrit, spp->rlcritsnow, spp->rpecons};
+    const void* const* theirs = (const void* const*)f;
+    bool any = false;
+    for (const void* a : mine) {
+      if (!a) continue;
+      any = true;
+      for (int m = 0; f && m < kNumFields; m++)
+        if (a == theirs[m]) return CLOUDSC_EINVAL;
+    }
+    if (!f || !any) return CLOUDSC_EINVAL;
+  }
   return CLOUDSC_OK;
 }
 
@@ -171,7 +183,7 @@ __device__ __forceinline__ cptr<DevParamsT<real, FAST>> params_of(cptr<KArgs<rea
 }
 template <typename F>
 __device__ __forceinline__ cptr<typename F::params> params_of(cptr<typename F::fields> ka) {
-  return params_of<typename F::real, F::fast>(ka);
+  return (cptr<typename F::params>)((const typename F::fields*)ka)->par;
 }
 
 }  // namespace
@@ -198,6 +210,9 @@ __device__ __forceinline__ cptr<typename F::params> params_of(cptr<typename F::f
 //   F::cml   the cumulative tendency form (cloudsc_gpu_run_tendbuf_cml): F::tb and
 //            F::prog, the first argument a KArgsCML, the four BUFFER_CML plane starts
 //            behind tend_planes; the tendency_loc_* members are never read;
+//   F::spp   the per-column multiplier form (cloudsc_gpu_run_spp): alone or with
+//            F::prog, the first argument a KArgsSPP, the five multiplier fields
+//            behind the KArgs;
 //   F::pack  narrow blocks (NPROMA <= 32) packed into full waves: a workgroup
 //            is one wave that walks PackArgs::pack consecutive blocks.
 // A kernel has exactly the arguments its form needs: Pack is PackArgs for
@@ -297,7 +312,7 @@ constexpr int kPrecisionOf = !std::is_same<real, S>::value ? CLOUDSC_MIXED : siz
 template <typename real, typename S, bool FAST>
 constexpr bool kernel_kept(int kind, bool aer, unsigned form = 0u) {
 #ifdef CLOUDSC_ONLY_KSEG
-  if (kind != CLOUDSC_VARIANT_KSEG || aer || (form & (kFormTb | kFormProg | kFormSurf | kFormCml)) || sizeof(real) != CLOUDSC_ONLY_KSEG ||
+  if (kind != CLOUDSC_VARIANT_KSEG || aer || (form & (kFormTb | kFormProg | kFormSurf | kFormCml | kFormSpp)) || sizeof(real) != CLOUDSC_ONLY_KSEG ||
       sizeof(S) != CLOUDSC_ONLY_KSEG)
     return false;
 #endif
@@ -318,7 +333,8 @@ struct LaunchForm {
   using product = cfg<DefaultCfg<real>::waves, DefaultCfg<real>::pf, false>;
 };
 constexpr bool cfg_table_applies(int kind, unsigned form) {
-  return !(form & (kFormTb | kFormProg | kFormSurf | kFormCml)) && (kind == CLOUDSC_VARIANT_KSEG || !(form & kFormPack));
+  return !(form & (kFormTb | kFormProg | kFormSurf | kFormCml | kFormSpp)) &&
+         (kind == CLOUDSC_VARIANT_KSEG || !(form & kFormPack));
 }
 template <typename LF, bool TABLE, typename Fn>
 int with_cfg(Fn&& f) {
@@ -337,10 +353,20 @@ int with_cfg(Fn&& f) {
 }
 
 // the kernel arguments of a launch: a's, with tend_planes behind them in the tendency buffer form and the
-// BUFFER_CML plane starts behind that in the cumulative tendency form
+// BUFFER_CML plane starts behind that in the cumulative tendency form, or the five multiplier fields behind them
+// in the per-column multiplier form
 template <typename F>
 typename F::kargs kernel_args(const typename F::fields& a, const StepForm& form) {
-  if constexpr (F::tb) {
+  if constexpr (F::spp) {
+    using S = typename F::store;
+    typename F::kargs t;
+    static_cast<typename F::fields&>(t) = a;
+    const cloudsc_spp_t* spp = form.spp;
+    t.mult[SPP_RAMID] = (const S*)spp->ramid; t.mult[SPP_RCLDIFF] = (const S*)spp->rcldiff;
+    t.mult[SPP_RCLCRIT] = (const S*)spp->rclcrit; t.mult[SPP_RLCRITSNOW] = (const S*)spp->rlcritsnow;
+    t.mult[SPP_RPECONS] = (const S*)spp->rpecons;
+    return t;
+  } else if constexpr (F::tb) {
     typename F::kargs t;
     static_cast<typename F::fields&>(t) = a;
     t.tend_planes = form.tend_planes;
@@ -663,14 +689,15 @@ int launch_v(const LaunchRequest& rq) {
   // conditions become F's members here, and only kernels that exist are instantiated
   const auto with_form = [&](auto kind_c, auto&& go) {
     return dispatch_bools(
-        [&](auto AER, auto PACK, auto TB, auto PROG, auto SURF, auto CML) {
-          constexpr unsigned form = form_bits(TB, PROG, SURF, CML) | (PACK ? kFormPack : 0u);
+        [&](auto AER, auto PACK, auto TB, auto PROG, auto SURF, auto CML, auto SPP) {
+          constexpr unsigned form = form_bits(TB, PROG, SURF, CML, SPP) | (PACK ? kFormPack : 0u);
           if constexpr (kernel_kept<real, ST, FAST>(kind_c, AER, form))
             return with_cfg<LaunchForm<real, ST, AER, FAST, form>, cfg_table_applies(kind_c, form)>(go);
           else
             return (int)CLOUDSC_EINVAL;
         },
-        aer, pack > 1, (bits & kFormTb) != 0, (bits & kFormProg) != 0, (bits & kFormSurf) != 0, (bits & kFormCml) != 0);
+        aer, pack > 1, (bits & kFormTb) != 0, (bits & kFormProg) != 0, (bits & kFormSurf) != 0, (bits & kFormCml) != 0,
+        (bits & kFormSpp) != 0);
   };
   if (kind == CLOUDSC_VARIANT_KCACHE) {
     rc = with_form(std::integral_constant<int, CLOUDSC_VARIANT_KCACHE>{}, [&](auto form) {
@@ -916,6 +943,13 @@ int cloudsc_gpu_run_tendbuf_cml(int device, void* stream, int precision, int var
                                 const cloudsc_tend_cml_t* cml, void* scratch) {
   return gpu_run_form(device, stream, {precision, variant, ngptot, nproma, klev}, f, scratch,
                       {tend_planes, outputs, cml}, kFormCml | kFormTb | kFormProg);
+}
+
+// (every rule before the first HIP call, CLOUDSC_OUTPUTS_ALL included: the form has no cloudsc_gpu_run behind it)
+int cloudsc_gpu_run_spp(int device, void* stream, int precision, int variant, int outputs, int ngptot, int nproma,
+                        int klev, const cloudsc_fields_t* f, const cloudsc_spp_t* spp, void* scratch) {
+  return gpu_run_form(device, stream, {precision, variant, ngptot, nproma, klev}, f, scratch, {0, outputs, nullptr, spp},
+                      kFormSpp);
 }
 
 int cloudsc_gpu_check(int device, void* stream, int variant, void* scratch) {

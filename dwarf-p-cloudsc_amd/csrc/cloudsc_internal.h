@@ -13,7 +13,7 @@
 
 namespace cloudsc {
 // the bits of a k-caching kernel's form (KForm, cloudsc_kcache.h)
-enum : unsigned { kFormPack = 1u, kFormTb = 2u, kFormProg = 4u, kFormSurf = 8u, kFormCml = 16u };
+enum : unsigned { kFormPack = 1u, kFormTb = 2u, kFormProg = 4u, kFormSurf = 8u, kFormCml = 16u, kFormSpp = 32u };
 }  // namespace cloudsc
 
 namespace cloudsc_impl {
@@ -113,20 +113,25 @@ struct StepForm {
   int tend_planes = 0;                      // != 0: tendency members are planes of packed buffers
   int outputs = CLOUDSC_OUTPUTS_ALL;        // CLOUDSC_OUTPUTS_*
   const cloudsc_tend_cml_t* cml = nullptr;  // the cumulative tendency planes
+  const cloudsc_spp_t* spp = nullptr;       // the per-column parameter multipliers
 };
 // a form's kForm* bits (kFormPack is the launch's own, not a form's)
-constexpr unsigned form_bits(bool tb, bool prog, bool surf, bool cml) {
+constexpr unsigned form_bits(bool tb, bool prog, bool surf, bool cml, bool spp = false) {
   using namespace cloudsc;
-  return (tb ? kFormTb : 0u) | (prog ? kFormProg : 0u) | (surf ? kFormSurf : 0u) | (cml ? kFormCml : 0u);
+  return (tb ? kFormTb : 0u) | (prog ? kFormProg : 0u) | (surf ? kFormSurf : 0u) | (cml ? kFormCml : 0u) |
+         (spp ? kFormSpp : 0u);
 }
 constexpr unsigned form_bits(const StepForm& s) {
-  return form_bits(s.tend_planes != 0, outputs_prognostic(s.outputs), outputs_surface(s.outputs), s.cml != nullptr);
+  return form_bits(s.tend_planes != 0, outputs_prognostic(s.outputs), outputs_surface(s.outputs), s.cml != nullptr,
+                   s.spp != nullptr);
 }
 // The support matrix, the part the bits alone decide: the surface-fluxes form is a prognostic-outputs form, the
-// cumulative tendency form a tendency buffer, prognostic-outputs form (KForm's static_asserts)
+// cumulative tendency form a tendency buffer, prognostic-outputs form, the per-column multiplier form stands alone or
+// with the prognostic-outputs form only (KForm's static_asserts)
 constexpr bool form_bits_consistent(unsigned form) {
   using namespace cloudsc;
-  return (!(form & kFormSurf) || (form & kFormProg)) && (!(form & kFormCml) || ((form & kFormTb) && (form & kFormProg)));
+  return (!(form & kFormSurf) || (form & kFormProg)) && (!(form & kFormCml) || ((form & kFormTb) && (form & kFormProg))) &&
+         (!(form & kFormSpp) || !(form & (kFormTb | kFormSurf | kFormCml)));
 }
 // The support matrix: whether (variant kind, precision, fp32 exact-libm, form bits) has a GPU kernel.  MIXED runs on the
 // k-caching variants only; so do the forms, alone or combined, which fp32 has with its default exp/pow only; the SCC
@@ -158,7 +163,9 @@ bool fields_complete(const cloudsc_fields_t* f, const StepForm& form = {});
 // The rules of a form that need neither a shape nor a device, the same for the GPU and the CPU entries: a known
 // selection, the bits `need` that the entry stands for, bits that go together, a plane count in range, and the
 // pointer rules of the cumulative planes -- cml's four members set, none of them a tendency_tmp_* or
-// tendency_loc_* member of f (pointer equality only).  CLOUDSC_EINVAL or CLOUDSC_OK.
+// tendency_loc_* member of f (pointer equality only) -- and of the multipliers -- at least one member of spp set,
+// none of them a member of f.  A form the entry does not stand for (bits outside `need`: a cml or an spp the
+// entry never passes) cannot occur.  CLOUDSC_EINVAL or CLOUDSC_OK.
 int check_step_form(const StepForm& form, unsigned need, const cloudsc_fields_t* f);
 // Host record of one KSEG workspace owned by a caller that launches on it in
 // stream order (a state): after the first launch zeroes it, later launches

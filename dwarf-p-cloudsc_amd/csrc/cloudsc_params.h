@@ -15,8 +15,8 @@
 namespace cloudsc {
 
 template <typename real>
-inline DevParams<real> fold_params(const cloudsc_params_t& p) {
-  DevParams<real> d;
+inline DevParamsSpp<real> fold_params(const cloudsc_params_t& p) {
+  DevParamsSpp<real> d;
   std::memset(&d, 0, sizeof(d));
 #define CP(n) d.n = (real)p.n
   CP(ptsphy); CP(rg); CP(rd); CP(retv); CP(rlvtt); CP(rlstt); CP(rtt); CP(rv);
@@ -29,7 +29,6 @@ inline DevParams<real> fold_params(const cloudsc_params_t& p) {
   CP(rcl_kk_cloud_num_land); CP(rcl_const1s); CP(rcl_const7s); CP(rcl_const8s); CP(rdensref);
   CP(rcl_cdenom1); CP(rcl_cdenom2); CP(rcl_cdenom3); CP(rcl_const1r); CP(rcl_const2r); CP(rcl_const3r);
   CP(rcl_const4r); CP(rcl_fac1); CP(rcl_fac2); CP(rcl_const5r); CP(rcl_const6r); CP(rcl_fzrab);
-#undef CP
   // Host folding in the working precision: the same single IEEE operation the
   // reference evaluates per point (x86-64 host float/double arithmetic is IEEE).
   const real ptsphy = (real)p.ptsphy, rg = (real)p.rg, rd = (real)p.rd, rcpd = (real)p.rcpd;
@@ -55,6 +54,8 @@ inline DevParams<real> fold_params(const cloudsc_params_t& p) {
   d.ncldtop = p.ncldtop;
   d.laericesed = p.laericesed;
   d.laericeauto = p.laericeauto;
+  CP(rcldiff); CP(rcldiff_convi); CP(rpecons);   // raw, for the per-column multiplier form
+#undef CP
   return d;
 }
 

@@ -62,6 +62,7 @@ typedef struct {
   int fields_caller;              /* --fields caller | tendbuf | tendbuf-inplace | tendbuf-cml (1 | 2 | 3 | 4): caller-owned field sets */
   int tend_planes;                /* --fields tendbuf: planes per block of the two tendency buffers (0: not tendbuf) */
   int outputs, outputs_given;     /* --outputs all|prognostic|surface: CLOUDSC_OUTPUTS_* */
+  int spp;                        /* --spp unit: the step through the SPP form, five all-ones multiplier fields */
   int place;                      /* placement search: 1 on, 0 off, -1 auto (on when reps > 1) */
   int narrow_pack;                /* NPROMA <= 32 packed into full waves: 1 on, 0 off, -1 the library's default */
   double energy_s;                /* --energy: seconds of back-to-back launches sampled for board power */
@@ -79,6 +80,7 @@ typedef struct {
   int inplace;                    /* --fields tendbuf-inplace: fill, step and validation on the buffers themselves */
   int cml;                        /* --fields tendbuf-cml: inplace, the step adding its tendencies to a zeroed BUFFER_CML (no BUFFER_LOC) */
   int outputs;                    /* --outputs: CLOUDSC_OUTPUTS_* */
+  int spp;                        /* --spp unit: cloudsc_gpu_run_spp with five all-ones multiplier fields */
   double energy_s;
   long long col_offset;
   const cloudsc_template_t *tmpl;
@@ -161,6 +163,9 @@ static void usage(const char *prog) {
           "  --outputs surface     prognostic, and PFPLSL, PFPLSN, PFHPSL, PFHPSN held at the surface only: their rows\n"
           "                        are validated against the last half level of the reference profiles (kseg and\n"
           "                        kcache as above; also --variant cpu, fp64 or mixed, without --fields)\n"
+          "  --spp unit            the step through the per-column multiplier form (cloudsc_gpu_run_spp with --fields\n"
+          "                        caller|levels, kseg or kcache, --outputs all|prognostic; cloudsc_cpu_run_spp with\n"
+          "                        --variant cpu) on five all-ones fields: the bits of the step without the flag\n"
           "  --transfer            host-buffer path: block-layout arrays in host memory,\n"
           "                        H2D -> kernel -> D2H per chunk, overlapped on streams\n"
           "                        (TOTAL includes the transfers, like cloudsc_driver.cu)\n"
@@ -251,6 +256,11 @@ static int parse(int argc, char **argv, options_t *o) {
       else if (!strcmp(v, "prognostic")) o->outputs = CLOUDSC_OUTPUTS_PROGNOSTIC;
       else if (!strcmp(v, "surface")) o->outputs = CLOUDSC_OUTPUTS_SURFACE;
       else { fprintf(stderr, "bad --outputs %s\n", v); return -1; }
+    }
+    else if (!strcmp(a, "--spp")) {
+      NEEDV();
+      if (!strcmp(v, "unit")) o->spp = 1;
+      else { fprintf(stderr, "bad --spp %s\n", v); return -1; }
     }
     else if (!strcmp(a, "--fp32-exact-libm")) o->exact_libm = 1;
     else if (!strcmp(a, "--chunk")) { NEEDV(); o->chunk_blocks = atoi(v); }
@@ -396,7 +406,10 @@ static void *hip_sym(const char *name) {
 
 /* one step of a --fields caller | tendbuf shard on the field set f (tendbuf: its tendencies in the buffers) */
 static int caller_step(const shard_t *s, int variant, int klev, const cloudsc_fields_t *f, void *ws,
-                       const cloudsc_tend_cml_t *cml) {
+                       const cloudsc_tend_cml_t *cml, const cloudsc_spp_t *spp) {
+  if (s->spp)                                            /* --spp unit */
+    return cloudsc_gpu_run_spp(s->device, NULL, s->precision, variant, s->outputs, s->ngptot, s->nproma, klev, f, spp,
+                               ws);
   if (s->cml)                                            /* --fields tendbuf-cml */
     return cloudsc_gpu_run_tendbuf_cml(s->device, NULL, s->precision, variant, s->outputs, s->ngptot, s->nproma, klev,
                                        s->tend_planes, f, cml, ws);
@@ -511,13 +524,31 @@ static void shard_caller(shard_t *s) {
       s->rc = cloudsc_fields_convert_tendbuf(s->device, NULL, s->ngptot, klev, s->precision, s->nproma, 0, &tmp_sep,
                                              s->precision, s->nproma, tp, &tmp_buf);
   }
+  /* --spp unit: one surface field of ones ([nblocks][nproma], the storage type) behind all five members */
+  void *spp_ones = NULL;
+  cloudsc_spp_t spp;
+  memset(&spp, 0, sizeof(spp));
+  if (!s->rc && s->spp) {
+    int (*h2d)(void *, const void *, size_t, int) = (int (*)(void *, const void *, size_t, int))hip_sym("hipMemcpy");
+    const size_t es = s->precision == CLOUDSC_FP64 ? 8 : 4;
+    const size_t n = (size_t)(s->ngptot / s->nproma + (s->ngptot % s->nproma ? 1 : 0)) * (size_t)s->nproma;
+    void *host = malloc(n * es);
+    for (size_t i = 0; host && i < n; i++) {
+      if (es == 8) ((double *)host)[i] = 1.0;
+      else ((float *)host)[i] = 1.0f;
+    }
+    if (!host || !h2d || set_device(s->device) || dmalloc(&spp_ones, n * es) || h2d(spp_ones, host, n * es, 1))
+      s->rc = CLOUDSC_ENOMEM;
+    free(host);
+    spp.ramid = spp.rcldiff = spp.rclcrit = spp.rlcritsnow = spp.rpecons = spp_ones;
+  }
   plude.plude = f.plude;
   /* plude is INOUT: expanded again before every step, outside the timing */
   for (int r = 0; r < s->warmup && !s->rc; r++) {
     if (r) s->rc = cloudsc_fields_expand(s->device, NULL, s->precision, s->ngptot, s->nproma, s->col_offset, s->tmpl, &plude);
     /* a launch adds once: BUFFER_CML is zeroed again before every step, outside the timing */
     if (!s->rc && s->cml && dmemset(buf_cml, 0, buf_bytes)) s->rc = CLOUDSC_EHIP;
-    if (!s->rc) s->rc = caller_step(s, variant, klev, &g, ws, &cml);
+    if (!s->rc) s->rc = caller_step(s, variant, klev, &g, ws, &cml, &spp);
     if (!s->rc) s->rc = cloudsc_gpu_check(s->device, NULL, s->variant, ws);
   }
   pthread_barrier_wait(s->barrier);
@@ -529,7 +560,7 @@ static void shard_caller(shard_t *s) {
     if (!s->rc && s->cml && dmemset(buf_cml, 0, buf_bytes)) s->rc = CLOUDSC_EHIP;
     if (!s->rc) s->rc = cloudsc_gpu_check(s->device, NULL, CLOUDSC_VARIANT_KCACHE, NULL);   /* the expansion is done */
     const double k0 = now();
-    if (!s->rc) s->rc = caller_step(s, variant, klev, &g, ws, &cml);
+    if (!s->rc) s->rc = caller_step(s, variant, klev, &g, ws, &cml, &spp);
     if (!s->rc) s->rc = cloudsc_gpu_check(s->device, NULL, s->variant, ws);
     s->kernel_ms[r] = (float)(1e3 * (now() - k0));   /* launch to the check's return, on the host clock */
     timed += now() - k0;
@@ -565,6 +596,7 @@ static void shard_caller(shard_t *s) {
   if (buf_tmp) dfree(buf_tmp);
   if (buf_loc) dfree(buf_loc);
   if (buf_cml) dfree(buf_cml);
+  if (spp_ones) dfree(spp_ones);
   cloudsc_fields_free(s->device, &f);
   cloudsc_fields_free(s->device, &stage);
   cloudsc_fields_free(s->device, &lev);
@@ -632,7 +664,7 @@ static int run_host(const options_t *o, const cloudsc_dataset_t *ds) {
   const int cpu = o->variant == VARIANT_CPU;
   const int es = precision_bytes(o->precision);
   /* the zinfo record: cloudsc_cpu_run_threads, fp64 (cloudsc_cpu_run_outputs, --outputs surface, keeps none) */
-  const int per_thread = cpu && o->precision == CLOUDSC_FP64 && o->outputs != CLOUDSC_OUTPUTS_SURFACE;
+  const int per_thread = cpu && o->precision == CLOUDSC_FP64 && o->outputs != CLOUDSC_OUTPUTS_SURFACE && !o->spp;
   const int nb = o->ngptot / o->nproma + (o->ngptot % o->nproma ? 1 : 0);
   const int aer = ds->params.laericesed || ds->params.laericeauto;
   cloudsc_fields_t f;
@@ -674,6 +706,20 @@ static int run_host(const options_t *o, const cloudsc_dataset_t *ds) {
     host_bytes += bytes;
   }
   const size_t plude_bytes = (size_t)nb * ds->klev * o->nproma * es;
+  /* --spp unit (--variant cpu): one surface field of ones behind all five members */
+  void *spp_ones = NULL;
+  cloudsc_spp_t spp;
+  memset(&spp, 0, sizeof(spp));
+  if (!rc && cpu && o->spp) {
+    const size_t n = (size_t)nb * (size_t)o->nproma;
+    spp_ones = malloc(n * (size_t)es);
+    if (!spp_ones) rc = CLOUDSC_ENOMEM;
+    for (size_t i = 0; spp_ones && i < n; i++) {
+      if (es == 8) ((double *)spp_ones)[i] = 1.0;
+      else ((float *)spp_ones)[i] = 1.0f;
+    }
+    spp.ramid = spp.rcldiff = spp.rclcrit = spp.rlcritsnow = spp.rpecons = spp_ones;
+  }
   cloudsc_host_pipeline_t *pipe = NULL;
   if (!rc && !cpu) rc = cloudsc_gpu_init(0, &ds->params);
   if (!rc && !cpu) rc = cloudsc_host_pipeline_create(&pipe, 0, o->precision, o->ngptot, o->nproma, ds->klev,
@@ -693,7 +739,11 @@ static int run_host(const options_t *o, const cloudsc_dataset_t *ds) {
     double ms = 0.0;
     if (cpu) {
       double secs = 0.0;
-      if (surface)
+      if (o->spp) {
+        const double t0 = now();
+        rc = cloudsc_cpu_run_spp(nth, o->precision, o->outputs, o->ngptot, o->nproma, ds->klev, &ds->params, &f, &spp);
+        secs = now() - t0;
+      } else if (surface)
         rc = cloudsc_cpu_run_outputs(nth, o->precision, o->outputs, o->ngptot, o->nproma, ds->klev, &ds->params, &f);
       else if (per_thread)
         rc = cloudsc_cpu_run_threads(nth, o->ngptot, o->nproma, ds->klev, &ds->params, &f, &secs, th_step,
@@ -769,6 +819,7 @@ static int run_host(const options_t *o, const cloudsc_dataset_t *ds) {
   }
   for (int i = 0; i < CLOUDSC_NFIELDS; i++) free(fp[i]);
   free(plude0);
+  free(spp_ones);
   free(th_s); free(th_step); free(th_blk); free(th_col); free(th_blk_step); free(th_col_step);
   return rc ? EXIT_FAILURE : (bad ? EXIT_FAILURE : EXIT_SUCCESS);
 }
@@ -855,6 +906,18 @@ int main(int argc, char **argv) {
                     "no cpu, scc or scc-private)\n");
     cloudsc_io_free(&ds);
     return EXIT_FAILURE;
+  }
+  /* --spp: the per-column multiplier form exists for --fields caller|levels on kseg|kcache and for --variant cpu,
+   * with --outputs all|prognostic: everything else is a usage error, never another step in its place */
+  if (o.spp) {
+    const int cpu = o.variant == VARIANT_CPU;
+    const int gpu_ok = o.fields_caller == 1 && (o.variant == CLOUDSC_VARIANT_KSEG || o.variant == CLOUDSC_VARIANT_KCACHE);
+    if (o.transfer || o.exact_libm || o.outputs == CLOUDSC_OUTPUTS_SURFACE || (cpu ? o.fields_caller != 0 : !gpu_ok)) {
+      fprintf(stderr, "dwarf-cloudsc-amd: --spp goes with --fields caller|levels and --variant kseg|kcache, or with "
+                      "--variant cpu (no --transfer, no --fp32-exact-libm, no --outputs surface, no tendency buffers)\n");
+      cloudsc_io_free(&ds);
+      return EXIT_FAILURE;
+    }
   }
   if (o.fields_caller >= 2 && !o.tend_planes) o.tend_planes = CLOUDSC_TENDBUF_PLANES_MIN;
   if (o.fields_caller && (o.transfer || o.variant == VARIANT_CPU)) {
@@ -948,6 +1011,7 @@ int main(int argc, char **argv) {
     s->inplace = o.fields_caller == 3 || o.fields_caller == 4;
     s->cml = o.fields_caller == 4;
     s->outputs = o.outputs;
+    s->spp = o.spp;
     s->aerosols = ds.params.laericesed || ds.params.laericeauto;
     s->tmpl = &tmpl; s->params = &ds.params; s->ref = ds.has_reference ? &ref : NULL; s->barrier = &bar;
     s->kernel_ms = (float *)calloc((size_t)o.reps, sizeof(float));

@@ -680,6 +680,82 @@ int cloudsc_cpu_fields_accumulate_tendbuf(int nthreads, int precision, int ngpto
                                           int loc_tend_planes, const cloudsc_fields_t *loc_fields,
                                           int cml_tend_planes, const cloudsc_tend_cml_t *cml);
 
+/* ------------------------------------------------------------------------ */
+/* Per-column perturbed parameters (SPP)                                     */
+/* ------------------------------------------------------------------------ */
+/* An ensemble member under the IFS's stochastically perturbed parametrisations
+ * multiplies a handful of cloud-scheme parameters by a random pattern that
+ * differs from column to column (the PGP2DSPP(KLON, ...) arrays of the later
+ * cloudsc.F90 cycles).  The entry points below take such multipliers as five
+ * surface fields beside the launch's (device-wide) parameter set.
+ *
+ * Each member is a field [nblocks][nproma] in the precision's storage type,
+ * with the layout of plsm: element [b][l] is the multiplier of column
+ * b * nproma + l.  A NULL member means that parameter is not perturbed.  Padding
+ * lanes of a partial last block are never read.  The fields are only read. */
+typedef struct cloudsc_spp {
+  const void *ramid;        /* RAMID: the critical relative humidity of new clouds (zrhc, both places)  */
+  const void *rcldiff;      /* RCLDIFF: erosion of clouds by turbulent mixing (zldifdt)                  */
+  const void *rclcrit;      /* RCLCRIT_SEA and RCLCRIT_LAND, whichever the column's PLSM selects          */
+  const void *rlcritsnow;   /* RLCRITSNOW: snow autoconversion (zlcrit; not read under LAERICEAUTO)      */
+  const void *rpecons;      /* RPECONS: evaporation of snow (zbeta)                                      */
+} cloudsc_spp_t;
+
+/* cloudsc_gpu_run_outputs with per-column multipliers.  The arithmetic is part
+ * of the contract, so that a host can reproduce it with one multiply: with x
+ * the column's multiplier as stored, `real` the compute type and p the
+ * parameter of the launch's set converted to `real` as the ordinary step does,
+ *   ramid'        = p.ramid * x                       (used at both places of zrhc)
+ *   r             = p.rcldiff * x
+ *   zldifdt0'     = r * ptsphy
+ *   zldifdt_conv' = p.rcldiff_convi * zldifdt0'
+ *   kk_lcrit'     = (land ? p.rclcrit_land : p.rclcrit_sea) * x
+ *   rlcritsnow'   = p.rlcritsnow * x     (under LAERICEAUTO the aerosol value replaces it as in
+ *                                         the ordinary step, and the member is not read)
+ *   rg_rpecons'   = p.rg * (p.rpecons * x)
+ * each a single IEEE operation of its own (no multiply-add is formed across
+ * these products and their consumers).  CLOUDSC_FP64: x is a double, every
+ * operation a double.  CLOUDSC_FP32: x is a float, every operation a float.
+ * CLOUDSC_MIXED: x is stored as float and widened exactly, every operation a
+ * double; the mixed identity extends to out = (float) fp64_spp_step((double)
+ * in, (double) x).  A NULL member takes x = 1 for every column.
+ * Hence, bit for bit on every output: with every multiplier exactly 1.0 the
+ * step is cloudsc_gpu_run_outputs on the same inputs; with one tuple for all
+ * columns it is the ordinary step under the cloudsc_params_t scaled on the host
+ * (p.n * x in double for fp64; (double)((float)p.n * (float)x) for fp32); with
+ * tuples that vary by column, each column is the ordinary step's under its own.
+ * There is no clamping and no range check of x: a non-finite or non-positive
+ * product is the caller's error, as a bad cloudsc_params_t value is.
+ *
+ * `outputs` is CLOUDSC_OUTPUTS_ALL or CLOUDSC_OUTPUTS_PROGNOSTIC.  KCACHE and
+ * KSEG, fp64, fp32 (default exp/pow) and mixed, with and without aerosols,
+ * packed and unpacked narrow blocks; everything else -- asynchrony, the
+ * workspace, cloudsc_gpu_check -- is cloudsc_gpu_run_outputs's, and one KSEG
+ * workspace serves SPP and other launches in any order (a later segment of a
+ * column reads the column's multipliers again; the hand-off record is as it was).
+ * CLOUDSC_EINVAL, all checked before the first HIP call: a NULL spp, an spp
+ * with no member set (such a caller uses cloudsc_gpu_run_outputs), a member
+ * equal to a member of device_fields (pointer equality only),
+ * CLOUDSC_OUTPUTS_SURFACE, CLOUDSC_VARIANT_SCC, CLOUDSC_VARIANT_SCC_PRIVATE,
+ * the option bit CLOUDSC_FP32_EXACT_LIBM and every argument error of
+ * cloudsc_gpu_run_outputs.
+ * The tendency-buffer and cumulative-tendency forms have no SPP twin (each
+ * further form bit doubles the kernel instantiations); the device-resident
+ * state (cloudsc_state_*), the host pipelines and the drop-in do not have the
+ * form either. */
+int cloudsc_gpu_run_spp(int device, void *stream, int precision, int variant, int outputs,
+                        int ngptot, int nproma, int klev,
+                        const cloudsc_fields_t *device_fields, const cloudsc_spp_t *spp, void *scratch);
+
+/* The host twin, on HOST memory through the same phase functions, fp64 and
+ * mixed as the other host forms (CLOUDSC_FP32: CLOUDSC_EINVAL): the same
+ * contract.  CLOUDSC_EINVAL: the spp rules above, CLOUDSC_OUTPUTS_SURFACE or an
+ * unknown `outputs` value and every argument error of cloudsc_cpu_run_outputs.
+ * Needs no GPU. */
+int cloudsc_cpu_run_spp(int nthreads, int precision, int outputs, int ngptot, int nproma, int klev,
+                        const cloudsc_params_t *params, const cloudsc_fields_t *host_fields,
+                        const cloudsc_spp_t *spp);
+
 /* cloudsc_fields_alloc for an output selection.  With CLOUDSC_OUTPUTS_ALL it is
  * cloudsc_fields_alloc.  With CLOUDSC_OUTPUTS_PROGNOSTIC the ten diagnostic
  * members are not allocated and stay NULL (10 * (klev + 1) elements per column

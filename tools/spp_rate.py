@@ -1,0 +1,110 @@
+#!/usr/bin/env python3
+"""Rate of the per-column multiplier form (SPP) on one MI355X: one JSON line per run.
+
+    spp_rate.py --what a|b [--precision fp64|mixed|fp32] [--variant kseg|kcache] [--ngptot N] [--nproma P]
+                [--steps K] [--warmup W] [--rounds R]
+
+  a  cloudsc_gpu_run_outputs(ALL): the ordinary step.  Run with CLOUDSC_AMD_LIB pointing at the parent commit's
+     library it is the baseline of every claim; run on this build it shows whether the ordinary step moved.
+  b  cloudsc_gpu_run_spp(ALL) with all five members set to seeded multipliers in [0.75, 1.25].
+
+Each round times `steps` back-to-back launches between two device synchronisations on the host clock; the line
+holds every round's ms per step and their median.  One process measures one thing; a caller alternates processes
+and swaps their order round by round (profiles/spp/rate.jsonl).  plude is INOUT and drifts over the steps: the
+bytes moved do not.
+
+EXPECTATION, written before the first run.  (a) on this build against (a) on the parent's library: the same
+kernels by the compiler's resource table, so any difference must lie inside the spread the parent shows against
+itself from process to process (placement of the field set varies from process to process).  (b)/(a): the form
+reads five surface fields more, 40 B per column in fp64 against about 56,036 B, so the byte model
+says 1 + 40/56036 = 1.0007: nothing.  What the form can cost beyond that is in the level loop: it reads a
+multiplier again at each of its four uses at every physics level (four vector loads from fields that stay in
+L2, each waited for where it is used, since nothing is carried in registers) and does five multiplies per level.
+With about 2.5 waves per SIMD to hide a load's latency behind, a few per cent would not surprise; more than
+that would say the waits are exposed.  fp32, whose level loop is bound by VALU issue and which keeps its
+parameter block in VGPRs, may pay more than fp64.  Nothing here is a pass/fail bound."""
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.join(os.path.dirname(HERE), "dwarf-p-cloudsc_amd"))
+import cloudsc_amd as ca  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--what", choices="ab", required=True)
+    ap.add_argument("--precision", default="fp64", choices=["fp64", "mixed", "fp32"])
+    ap.add_argument("--variant", default="kseg", choices=["kseg", "kcache"])
+    ap.add_argument("--ngptot", type=int, default=163840)
+    ap.add_argument("--nproma", type=int, default=64)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--seed", type=int, default=1)
+    o = ap.parse_args()
+    prec = {"fp64": ca.FP64, "mixed": ca.MIXED, "fp32": ca.FP32}[o.precision]
+    variant = {"kseg": ca.VARIANT_KSEG, "kcache": ca.VARIANT_KCACHE}[o.variant]
+    lib, hip = ca.gpu_lib(), ca._hip()
+    hip.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
+    if o.what == "b" and not hasattr(lib, "cloudsc_gpu_run_spp"):
+        sys.exit("this library has no per-column multiplier form (only --what a runs on it)")
+    ds = ca.load_dataset()
+    p = ca.Params.from_dict(ds.params)
+    ca.check(lib.cloudsc_gpu_init(0, C.byref(p)))
+    d = ca.DeviceFields(o.ngptot, o.nproma, ds.klev, prec)
+    mult, ws = [], C.c_void_p()
+    try:
+        d.expand(ds)
+        wsb = lib.cloudsc_gpu_scratch_bytes(prec, variant, o.ngptot, o.nproma, ds.klev)
+        if wsb > 0:
+            assert hip.hipMalloc(C.byref(ws), C.c_size_t(wsb)) == 0 and hip.hipMemset(ws, 0, C.c_size_t(256)) == 0
+        args = (prec, variant, ca.OUTPUTS_ALL, o.ngptot, o.nproma, ds.klev)
+        if o.what == "a":
+            def step():
+                ca.gpu_run_outputs(d.f, *args, scratch=ws)
+        else:
+            rng = np.random.default_rng(o.seed)
+            n = ca.nblocks_of(o.ngptot, o.nproma) * o.nproma
+            for _ in ca.SPP_SLOTS:
+                a = rng.uniform(0.75, 1.25, n).astype(ca.storage_dtype(prec))
+                q = C.c_void_p()
+                assert hip.hipMalloc(C.byref(q), C.c_size_t(a.nbytes)) == 0
+                assert hip.hipMemcpy(q, a.ctypes.data, a.nbytes, 1) == 0
+                mult.append(q)
+            spp = ca.Spp(*[q.value for q in mult])
+
+            def step():
+                ca.gpu_run_spp(d.f, spp, *args, scratch=ws)
+        for _ in range(o.warmup):
+            step()
+        ca.check(lib.cloudsc_gpu_check(0, None, variant, ws))
+        ms = []
+        for _ in range(o.rounds):
+            hip.hipDeviceSynchronize()
+            t0 = time.perf_counter()
+            for _ in range(o.steps):
+                step()
+            hip.hipDeviceSynchronize()
+            ms.append(1e3 * (time.perf_counter() - t0) / o.steps)
+        ca.check(lib.cloudsc_gpu_check(0, None, variant, ws))
+        print(json.dumps({"what": o.what, "precision": o.precision, "variant": o.variant, "ngptot": o.ngptot,
+                          "nproma": o.nproma, "steps": o.steps, "rounds": o.rounds,
+                          "lib": "CLOUDSC_AMD_LIB" if os.environ.get("CLOUDSC_AMD_LIB") else "this build",
+                          "ms_per_step": [round(x, 4) for x in ms], "median_ms": round(statistics.median(ms), 4)}))
+    finally:
+        for q in mult + [ws]:
+            if q.value:
+                hip.hipFree(q)
+        d.close()
+
+
+if __name__ == "__main__":
+    main()
