@@ -558,14 +558,11 @@ extern "C" int cloudsc_fields_compare_tendbuf(int device, void* stream, int ngpt
   return CLOUDSC_OK;
 }
 
-extern "C" int cloudsc_fields_validate_tendbuf(int device, void* stream, int precision, int ngptot, int nproma,
-                                               int klev, int tend_planes, int outputs, long long col_offset,
-                                               const cloudsc_fields_t* fields, const cloudsc_reference_t* ref,
-                                               cloudsc_stats_t* stats) {
-  if (!fs_tend_planes_ok(tend_planes)) return CLOUDSC_EINVAL;
-  if (!outputs_known(outputs)) return CLOUDSC_EINVAL;
-  if (!tend_planes && outputs == CLOUDSC_OUTPUTS_ALL)   // cloudsc_fields_validate itself
-    return cloudsc_fields_validate(device, stream, precision, ngptot, nproma, klev, col_offset, fields, ref, stats);
+// the validation; tend_planes: the tendency members of `fields` are planes of a packed buffer with so many
+// planes per block (0: separate arrays); outputs: the selection the set was allocated for
+static int validate_impl(int device, void* stream, int precision, int ngptot, int nproma, int klev, int tend_planes,
+                         int outputs, long long col_offset, const cloudsc_fields_t* fields,
+                         const cloudsc_reference_t* ref, cloudsc_stats_t* stats) {
   if (!fields || !ref || !stats || col_offset < 0) return CLOUDSC_EINVAL;
   if (!precision_storage_bytes(precision)) return CLOUDSC_EINVAL;
   if (ngptot < 1 || klev < 1 || nproma < 1 || nproma > kFsMaxNproma) return CLOUDSC_EINVAL;
@@ -604,49 +601,34 @@ extern "C" int cloudsc_fields_validate_tendbuf(int device, void* stream, int pre
                           (size_t)a.e[i].rows * ref->klon * sizeof(double), hipMemcpyHostToDevice, st));
     a.e[i].b = ws->stage + off[i];
   }
-  rc = cmp_launch<true, CmpTendItem>(*ws, ncu, st, a, precision_storage_bytes(precision) == 8, true);
+  const bool a8 = precision_storage_bytes(precision) == 8;
+  if (!tend_planes && outputs == CLOUDSC_OUTPUTS_ALL) {   // every member's own rows: the kernel without the strides
+    CmpArgs& plain = a;
+    rc = cmp_launch<true>(*ws, ncu, st, plain, a8, true);
+  } else {
+    rc = cmp_launch<true, CmpTendItem>(*ws, ncu, st, a, a8, true);
+  }
   if (rc) return rc;
   for (int id = 0; id < CLOUDSC_NVALID; id++) stats[id] = {__DBL_MAX__, -__DBL_MAX__, 0.0, 0.0, 0.0, 0.0, 0.0};
   for (int i = 0; i < a.n; i++) stats[id_of[i]] = rec_stats(ws->hres[i]);
   return CLOUDSC_OK;
 }
 
+extern "C" int cloudsc_fields_validate_tendbuf(int device, void* stream, int precision, int ngptot, int nproma,
+                                               int klev, int tend_planes, int outputs, long long col_offset,
+                                               const cloudsc_fields_t* fields, const cloudsc_reference_t* ref,
+                                               cloudsc_stats_t* stats) {
+  if (!fs_tend_planes_ok(tend_planes)) return CLOUDSC_EINVAL;
+  if (!outputs_known(outputs)) return CLOUDSC_EINVAL;
+  return validate_impl(device, stream, precision, ngptot, nproma, klev, tend_planes, outputs, col_offset, fields, ref,
+                       stats);
+}
+
 extern "C" int cloudsc_fields_validate(int device, void* stream, int precision, int ngptot, int nproma, int klev,
                                        long long col_offset, const cloudsc_fields_t* fields,
                                        const cloudsc_reference_t* ref, cloudsc_stats_t* stats) {
-  if (!fields || !ref || !stats || col_offset < 0) return CLOUDSC_EINVAL;
-  if (!precision_storage_bytes(precision)) return CLOUDSC_EINVAL;
-  if (ngptot < 1 || klev < 1 || nproma < 1 || nproma > kFsMaxNproma) return CLOUDSC_EINVAL;
-  if (ref->klon <= 0 || ref->klev != klev) return CLOUDSC_EINVAL;
-  int member[CLOUDSC_NVALID];
-  valid_members(member);
-  CmpArgs a = {};
-  size_t off[CLOUDSC_NVALID], total = 0;   // bytes of each reference array in the stage
-  for (int id = 0; id < CLOUDSC_NVALID; id++) {
-    const void* p = ((const void* const*)fields)[member[id]];
-    if (!p || !ref->field[id]) return CLOUDSC_EINVAL;
-    fs_add<const void>(&a, member[id], klev, p, nullptr);   // entry id; b: the staged reference, below
-    off[id] = total;
-    total += (size_t)a.e[id].rows * ref->klon * sizeof(double);
-  }
-  fs_shape(&a, ngptot, nproma, 1);
-  a.klon = ref->klon;
-  a.col_offset = col_offset % ref->klon;
-  CmpWorkspace* ws = nullptr;
-  std::unique_lock<std::mutex> lock;
-  int ncu = 0, rc = ws_open(device, lock, &ws, &ncu);
-  if (rc || (rc = ws_grow_stage(*ws, total, false))) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  for (int id = 0; id < CLOUDSC_NVALID; id++) {
-    // on `stream`, ordered before the kernel that reads it
-    HIPCHK(hipMemcpyAsync(ws->stage + off[id], ref->field[id], (size_t)a.e[id].rows * ref->klon * sizeof(double),
-                          hipMemcpyHostToDevice, st));
-    a.e[id].b = ws->stage + off[id];
-  }
-  rc = cmp_launch<true>(*ws, ncu, st, a, precision_storage_bytes(precision) == 8, true);
-  if (rc) return rc;
-  for (int id = 0; id < CLOUDSC_NVALID; id++) stats[id] = rec_stats(ws->hres[id]);
-  return CLOUDSC_OK;
+  return validate_impl(device, stream, precision, ngptot, nproma, klev, 0, CLOUDSC_OUTPUTS_ALL, col_offset, fields,
+                       ref, stats);
 }
 
 // the expansion; tend_planes: the tendency members of `fields` are planes of a packed buffer with so many

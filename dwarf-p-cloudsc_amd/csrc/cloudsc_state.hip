@@ -1,7 +1,7 @@
 // cloudsc_state.hip -- the device-resident dwarf state of include/cloudsc_amd.h
 // (cloudsc_state_*): on-device expansion of the KLON-column template (g % klon
-// of the GLOBAL column index), timed runs on the state's stream, and on-device
-// validation statistics against the KLON-column reference.
+// of the GLOBAL column index), timed runs on the state's stream, and validation
+// against the KLON-column reference through cloudsc_fields_validate.
 #include <algorithm>
 #include <atomic>
 #include <hip/hip_runtime.h>
@@ -18,7 +18,7 @@
 using namespace cloudsc_impl;
 
 // ---------------------------------------------------------------------------
-// plumbing kernels: expansion and validation statistics
+// plumbing kernel: expansion
 // ---------------------------------------------------------------------------
 // dst[b][L][i] = src[L][(col_offset + b*nproma + i) % klon], L < nlev.
 // A 1-D grid strides over all nblocks*nlev*nproma elements with 64-bit
@@ -37,50 +37,6 @@ __global__ void expand_kernel(T* __restrict__ dst, const S* __restrict__ src, in
     const long long g = col_offset + b * nproma + i;
     dst[e] = (T)src[L * klon + g % klon];
   }
-}
-
-// DD and dd_add are in cloudsc_internal.h (shared with cloudsc_compare.hip)
-
-// One workgroup per NPROMA block: min/max of the field, max|d|, sum|d|, sum|ref|
-// over the active lanes of that block (validate_mod.F90:136-146, with fabs);
-// the sums as double-doubles.  part[b] = {min, max, max|d|, es.hi, rs.hi, es.lo, rs.lo}.
-constexpr int kStatsPer = 7;
-template <typename real>
-__global__ void __launch_bounds__(256) stats_kernel(const real* __restrict__ fld, const double* __restrict__ ref,
-                                                    int nlev, int klon, int nproma, long long ngptot,
-                                                    long long col_offset, double* __restrict__ part) {
-  const long long b = blockIdx.x;
-  const long long bsize = (ngptot - b * nproma) < nproma ? (ngptot - b * nproma) : nproma;
-  double mn = __DBL_MAX__, mx = -__DBL_MAX__, me = 0.0;
-  DD es = {0.0, 0.0}, rs = {0.0, 0.0};
-  const long long per = (long long)nlev * nproma;   // 64-bit: may exceed 2^31 at large NPROMA
-  for (long long e = threadIdx.x; e < per; e += blockDim.x) {
-    const long long L = e / nproma, i = e - L * nproma;
-    if (i >= bsize) continue;
-    const long long g = col_offset + b * nproma + i;
-    const double v = (double)fld[b * per + e];
-    const double r = ref[L * klon + g % klon];
-    const double d = fabs(v - r);
-    mn = fmin(mn, v); mx = fmax(mx, v); me = fmax(me, d);
-    es = dd_add(es, DD{d, 0.0});
-    rs = dd_add(rs, DD{fabs(r), 0.0});
-  }
-  __shared__ double s[kStatsPer][256];
-  const int t = threadIdx.x;
-  s[0][t] = mn; s[1][t] = mx; s[2][t] = me; s[3][t] = es.hi; s[4][t] = rs.hi; s[5][t] = es.lo; s[6][t] = rs.lo;
-  __syncthreads();
-  for (int w = blockDim.x / 2; w > 0; w >>= 1) {
-    if (t < w) {
-      s[0][t] = fmin(s[0][t], s[0][t + w]); s[1][t] = fmax(s[1][t], s[1][t + w]);
-      s[2][t] = fmax(s[2][t], s[2][t + w]);
-      const DD a = dd_add(DD{s[3][t], s[5][t]}, DD{s[3][t + w], s[5][t + w]});
-      const DD c = dd_add(DD{s[4][t], s[6][t]}, DD{s[4][t + w], s[6][t + w]});
-      s[3][t] = a.hi; s[5][t] = a.lo; s[4][t] = c.hi; s[6][t] = c.lo;
-    }
-    __syncthreads();
-  }
-  if (t == 0)
-    for (int q = 0; q < kStatsPer; q++) part[b * kStatsPer + q] = s[q][0];
 }
 
 // ---------------------------------------------------------------------------
@@ -111,13 +67,12 @@ size_t field_elems(const cloudsc_gpu_state* s, int kind) {
   return (size_t)s->nblocks * per_block_elems(kind, s->nproma, s->klev);
 }
 
-// pointer slot and shape kind of a validated field (cloudsc_field_id), from the inventory
-void* const* valid_slot(const cloudsc_gpu_state* s, int id, int* kind) {
+// the cloudsc_fields_t position of a validated field (cloudsc_field_id), from the inventory
+int valid_member(int id) {
   int member[CLOUDSC_NVALID];
 #define VALID_MEMBER(n, N, k, d, i) CLOUDSC_IF_VALIDATED_##d(member[CLOUDSC_F_##N] = CLOUDSC_M_##n;)
   CLOUDSC_FIELDS(VALID_MEMBER)
-  *kind = kFieldTable[member[id]].kind;
-  return (void* const*)&s->f + member[id];
+  return member[id];
 }
 
 #ifdef CLOUDSC_DEBUG_KNOBS
@@ -788,23 +743,21 @@ int cloudsc_state_sync(cloudsc_gpu_state_t* s) {
 
 long long cloudsc_state_field_elems(const cloudsc_gpu_state_t* s, int id) {
   if (!s || id < 0 || id >= CLOUDSC_NVALID) return -1;
-  int kind;
-  valid_slot(s, id, &kind);
-  return (long long)field_elems(s, kind);
+  return (long long)field_elems(s, kFieldTable[valid_member(id)].kind);
 }
 
 int cloudsc_state_download(cloudsc_gpu_state_t* s, int id, double* host) {
   if (!s || !host || id < 0 || id >= CLOUDSC_NVALID) return CLOUDSC_EINVAL;
   HIPCHK(hipSetDevice(s->device));
-  int kind;
-  void* const* slot = valid_slot(s, id, &kind);
-  const size_t n = field_elems(s, kind);
+  const int m = valid_member(id);
+  const void* src = ((void* const*)&s->f)[m];
+  const size_t n = field_elems(s, kFieldTable[m].kind);
   HIPCHK(hipStreamSynchronize(s->stream));
   if (s->es == sizeof(double)) {
-    HIPCHK(hipMemcpy(host, *slot, n * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(host, src, n * sizeof(double), hipMemcpyDeviceToHost));
   } else {
     std::vector<float> tmp(n);
-    HIPCHK(hipMemcpy(tmp.data(), *slot, n * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(tmp.data(), src, n * sizeof(float), hipMemcpyDeviceToHost));
     for (size_t i = 0; i < n; i++) host[i] = tmp[i];
   }
   return CLOUDSC_OK;
@@ -812,46 +765,8 @@ int cloudsc_state_download(cloudsc_gpu_state_t* s, int id, double* host) {
 
 int cloudsc_state_validate(cloudsc_gpu_state_t* s, const cloudsc_reference_t* ref, cloudsc_stats_t* stats) {
   if (!s || !ref || !stats || ref->klon <= 0 || ref->klev != s->klev) return CLOUDSC_EINVAL;
-  HIPCHK(hipSetDevice(s->device));
-  HIPCHK(hipStreamSynchronize(s->stream));
-  double* part = nullptr;
-  double* dref = nullptr;
-  HIPCHK(hipMalloc(&part, (size_t)s->nblocks * kStatsPer * sizeof(double)));
-  const size_t max_ref = (size_t)5 * (s->klev + 1) * ref->klon;
-  hipError_t e = hipMalloc(&dref, max_ref * sizeof(double));
-  std::vector<double> h((size_t)s->nblocks * kStatsPer);
-  for (int id = 0; id < CLOUDSC_NVALID && e == hipSuccess; id++) {
-    int kind;
-    void* const* slot = valid_slot(s, id, &kind);
-    const int nlev = (int)per_block_elems(kind, 1, s->klev);   // rows per column
-    if (!ref->field[id]) { e = hipErrorInvalidValue; break; }
-    // on the state's stream, ordered before the kernel that reads it (a null-stream
-    // hipMemcpy from pageable memory can still be in flight when it returns)
-    e = hipMemcpyAsync(dref, ref->field[id], (size_t)nlev * ref->klon * sizeof(double), hipMemcpyHostToDevice,
-                       s->stream);
-    if (e != hipSuccess) break;
-    if (s->es == sizeof(double))
-      hipLaunchKernelGGL(stats_kernel<double>, dim3(s->nblocks), dim3(256), 0, s->stream, (const double*)*slot,
-                         dref, nlev, ref->klon, s->nproma, (long long)s->ngptot, s->col_offset, part);
-    else
-      hipLaunchKernelGGL(stats_kernel<float>, dim3(s->nblocks), dim3(256), 0, s->stream, (const float*)*slot,
-                         dref, nlev, ref->klon, s->nproma, (long long)s->ngptot, s->col_offset, part);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-    if (e == hipSuccess) e = hipMemcpy(h.data(), part, h.size() * sizeof(double), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) break;
-    cloudsc_stats_t t = {__DBL_MAX__, -__DBL_MAX__, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int b = 0; b < s->nblocks; b++) {            // double-double sums: order-independent to ~2^-100
-      const double* q = &h[(size_t)b * kStatsPer];
-      const cloudsc_stats_t pb = {q[0], q[1], q[2], q[3], q[4], q[5], q[6]};
-      cloudsc_stats_combine(&t, &pb);
-    }
-    stats[id] = t;
-  }
-  (void)hipFree(part);
-  (void)hipFree(dref);
-  if (e != hipSuccess) return hip_fail(e, "validate");
-  return CLOUDSC_OK;
+  return cloudsc_fields_validate(s->device, s->stream, s->precision, s->ngptot, s->nproma, s->klev, s->col_offset,
+                                 &s->f, ref, stats);
 }
 
 void cloudsc_stats_combine(cloudsc_stats_t* acc, const cloudsc_stats_t* p) {

@@ -1114,7 +1114,14 @@ int cloudsc_state_sync(cloudsc_gpu_state_t *state);
 int cloudsc_state_kseg_clock(cloudsc_gpu_state_t *state, int reset, double *ghz);
 
 /* Field-wise statistics vs a KLON-column reference, computed on the device
- * (modulo indexing; no expanded reference in host or device memory). */
+ * (modulo indexing; no expanded reference in host or device memory):
+ * cloudsc_fields_validate on the state's own fields, stream and column offset.
+ * Waits for the state's stream.  It uses the device's compare / validate /
+ * expand workspace (below) behind its mutex, so concurrent validations on one
+ * device serialise, and cloudsc_fields_compare_release frees what it grew.
+ * CLOUDSC_EINVAL: a NULL argument, a NULL array in ref->field[] (CLOUDSC_EHIP
+ * before the state validated through the field-set kernel), ref->klon < 1,
+ * ref->klev != the state's. */
 int cloudsc_state_validate(cloudsc_gpu_state_t *state, const cloudsc_reference_t *ref,
                            cloudsc_stats_t stats[CLOUDSC_NVALID]);
 

@@ -1,6 +1,6 @@
 """Field set comparison, validation and expansion on the device (cloudsc_fields_compare / _validate /
 _expand): the cases of tests/test_fields_compare_cpu.py against the host twin (itself held to the
-restatement there), expansion against ca.expand, validation against the state API, the physics kernels
+restatement there), expansion against ca.expand, validation against the state API and an exact host restatement, the physics kernels
 held against each other through the comparison, and the CLI's --fields caller."""
 import ctypes as C
 import os
@@ -251,6 +251,64 @@ def test_validate_matches_state(lib, hip, ds, ngptot, nproma, col_offset, precis
         n = fc.rows_of(key, ds.klev) * ngptot
         assert_sums_close(x[3], x[5], y[3], y[5], n, name + " errsum")
         assert_sums_close(x[4], x[6], y[4], y[6], n, name + " refsum")
+
+
+_TILED = {}   # (ngptot, col_offset): {key: (reference [rows][ngptot], exact sum of its magnitudes)}, computed once
+
+
+def tiled_reference(ds, ngptot, col_offset):
+    """Per validated field, ref[row][(col_offset + g) % klon] for g < ngptot and the exact sum of |ref|."""
+    if (ngptot, col_offset) not in _TILED:
+        cols = (col_offset + np.arange(ngptot)) % ds.klon
+        tiled = {}
+        for _, key in ca.VALIDATED:
+            r = np.asarray(ds.reference[key], dtype=np.float64)
+            r = np.ascontiguousarray(np.take(r.reshape(-1, r.shape[-1]), cols, axis=-1))
+            tiled[key] = (r, cc.exact_sum(np.abs(r)))
+        _TILED[(ngptot, col_offset)] = tiled
+    return _TILED[(ngptot, col_offset)]
+
+
+def restated_validation(v, r):
+    """min v, max v, max |v - r| as NumPy has them and the exact sum of |v - r| (fields_compare_cases.restate)."""
+    d = np.abs(v - r)
+    return (float(np.fmin.reduce(v, axis=None)), float(np.fmax.reduce(v, axis=None)),
+            float(np.fmax.reduce(d, axis=None, initial=0.0)), cc.exact_sum(d))
+
+
+@pytest.mark.parametrize("precision", PRECISIONS, ids=PRECISION_IDS)
+@pytest.mark.parametrize("col_offset", [0, 37])
+@pytest.mark.parametrize("ngptot,nproma", [(300, 64), (100, 100)])
+def test_validate_matches_host_restatement(lib, hip, ds, ngptot, nproma, col_offset, precision):
+    """GpuState.validate() and DeviceFields.validate() run the same device code, so both are held to a
+    restatement on the host from the downloaded outputs: min, max and max|d| bit for bit, the two sums
+    against the exact rational sums (fields_compare_cases.assert_sum, n = rows * ngptot)."""
+    g = ca.GpuState(ds, ngptot, nproma, precision, col_offset=col_offset)
+    df = ca.DeviceFields(ngptot, nproma, ds.klev, precision, place=False)
+    try:
+        g.run(ca.VARIANT_KSEG, 1)
+        state_stats = g.validate()
+        state_out = g.outputs()
+        df.expand(ds, col_offset)
+        run_on(lib, hip, ds, df, ca.VARIANT_KSEG)
+        fields_stats = df.validate(ds, col_offset)
+        fields_out = {k: ca.blocks_to_columns(df.download_raw(k), ngptot) for _, k in ca.VALIDATED}   # no padding lanes
+    finally:
+        g.close()
+        df.close()
+    ref = tiled_reference(ds, ngptot, col_offset)
+    for i, (name, key) in enumerate(ca.VALIDATED):
+        r, refsum = ref[key]
+        vs = np.ascontiguousarray(state_out[key], dtype=np.float64).reshape(r.shape)
+        vf = np.ascontiguousarray(fields_out[key], dtype=np.float64).reshape(r.shape)
+        assert r.shape == (fc.rows_of(key, ds.klev), ngptot)
+        want_s = restated_validation(vs, r)
+        want_f = want_s if np.array_equal(fc.bits(vs), fc.bits(vf)) else restated_validation(vf, r)
+        for what, got, want in (("state", state_stats[i], want_s), ("fields", fields_stats[i], want_f)):
+            assert want[3] is not None and refsum is not None, (what, name)
+            assert [cc.dbits(x) for x in got[:3]] == [cc.dbits(x) for x in want[:3]], (what, name, got, want)
+            cc.assert_sum(got[3], got[5], want[3], r.size, "%s %s errsum" % (what, name))
+            cc.assert_sum(got[4], got[6], refsum, r.size, "%s %s refsum" % (what, name))
 
 
 # ---------------------------------------------------------------------------
