@@ -16,7 +16,7 @@ import numpy as np
 
 import cloudsc_amd as ca
 import make_fixtures as mf
-from test_mixed_cpu import configured
+from host_harness import configured, uses_aerosols  # noqa: F401
 
 NGPTOT = 100                      # the template's columns, each once
 ORACLE_NPROMA = 64                # the oracle's columns do not depend on the blocking
@@ -104,6 +104,24 @@ ACTIVITY = {
 assert sorted(ACTIVITY) == sorted(BUILDERS)
 
 
+# the forms' launches on these states (tests/test_forms_states_gpu.py and its tendbuf-outputs companion)
+VARIANTS = (ca.VARIANT_KCACHE, ca.VARIANT_KSEG)
+TEND_PLANES, ORDER = 11, "permuted"
+
+
+def shapes(name, packed_form=False):
+    if packed_form:
+        return [(NGPTOT, 16)] if name == "klev274" else [(NGPTOT, 16), (NGPTOT, 5)]
+    return [(NGPTOT, 64), (NGPTOT, 16)]
+
+
+def schedules(name, variant):
+    """(segments, workgroups) of the form's launches: KSEG also with two hand-offs per column."""
+    if variant != ca.VARIANT_KSEG or name == "klev3":
+        return [(0, 0)]
+    return [(0, 0), (3, 3)]
+
+
 def base_of(name):
     return BUILDERS[name][0]
 
@@ -125,10 +143,6 @@ def dataset(name, ds, scenarios):
             a.setflags(write=False)
         _datasets[name] = s
     return _datasets[name]
-
-
-def uses_aerosols(s):
-    return bool(s.params.get("laericesed") or s.params.get("laericeauto"))
 
 
 _oracle = {}

@@ -11,20 +11,12 @@ import pytest
 
 import cloudsc_amd as ca
 import device_math_cases as dm
+from gpu_harness import lib  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
 needs_fma = pytest.mark.skipif(not dm.has_fma(),
                                reason="the host C library's non-FMA variant rounds differently in rare cases")
 BLOCKS = (64, 256)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import ctypes as C
-    lib = ca.gpu_lib()
-    n = C.c_int()
-    assert lib.cloudsc_gpu_device_count(C.byref(n)) == 0 and n.value > 0
-    return lib
 
 
 def run64(lib, which, block, x, y=None):

@@ -14,6 +14,7 @@ import pytest
 import cloudsc_amd as ca
 import fields_compare_cases as cc
 import fields_convert_cases as fc
+from gpu_harness import lib, hip, run_on  # noqa: F401  (lib, hip: fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -21,18 +22,6 @@ INPUTS = list(ca.INPUT_FIELDS) + list(ca.INOUT_FIELDS)
 OUTPUTS = cc.OUTPUTS
 PRECISIONS = [ca.FP64, ca.FP32, ca.MIXED]
 PRECISION_IDS = ["fp64", "fp32", "mixed"]
-
-
-@pytest.fixture(scope="module")
-def lib():
-    lib = ca.gpu_lib()
-    assert ca.device_count() > 0
-    return lib
-
-
-@pytest.fixture(scope="module")
-def hip():
-    return ca._hip()
 
 
 def host_compare(lib, a, b, names=None):
@@ -213,24 +202,6 @@ def test_expand(lib, ds, ngptot, nproma, col_offset, precision):
 # ---------------------------------------------------------------------------
 # validation of a caller-owned set against the state API
 # ---------------------------------------------------------------------------
-def run_on(lib, hip, ds, df, variant):
-    """cloudsc_gpu_run + cloudsc_gpu_check on a DeviceFields with the dataset's parameters."""
-    p = ca.Params.from_dict(ds.params)
-    ca.check(lib.cloudsc_gpu_init(0, C.byref(p)))
-    ws = C.c_void_p()
-    nbytes = lib.cloudsc_gpu_scratch_bytes(df.precision, variant, df.ngptot, df.nproma, df.klev)
-    assert nbytes >= 0
-    try:
-        if nbytes > 0:
-            assert hip.hipMalloc(C.byref(ws), C.c_size_t(nbytes)) == 0
-            assert hip.hipMemset(ws, 0, C.c_size_t(256)) == 0
-        ca.check(lib.cloudsc_gpu_run(0, None, df.precision, variant, df.ngptot, df.nproma, df.klev, C.byref(df.f), ws))
-        assert lib.cloudsc_gpu_check(0, None, variant, ws) == 0
-    finally:
-        if ws.value:
-            hip.hipFree(ws)
-
-
 @pytest.mark.parametrize("precision", PRECISIONS, ids=PRECISION_IDS)
 @pytest.mark.parametrize("col_offset", [0, 37])
 @pytest.mark.parametrize("ngptot,nproma", [(1000, 64), (300, 64), (100, 100)])

@@ -12,23 +12,12 @@ import cloudsc_amd as ca
 import fields_convert_cases as fc
 import fields_layout_cases as lc
 import mixed_expected as mx
+from gpu_harness import lib, hip, run_on  # noqa: F401  (lib, hip: fixtures)
 
 pytestmark = pytest.mark.gpu
 
 B, L = lc.B, lc.L
 VALIDATED = [k for _, k in ca.VALIDATED]
-
-
-@pytest.fixture(scope="module")
-def lib():
-    lib = ca.gpu_lib()
-    assert ca.device_count() > 0
-    return lib
-
-
-@pytest.fixture(scope="module")
-def hip():
-    return ca._hip()
 
 
 def cpu_expected(lib, src, dst_layout, dnp, dp, names=None):
@@ -157,24 +146,6 @@ def test_kernels_use_no_scratch(lib):
 # ---------------------------------------------------------------------------
 # the physics through level-contiguous arrays
 # ---------------------------------------------------------------------------
-def run_on(lib, hip, ds, df, variant):
-    """cloudsc_gpu_run + cloudsc_gpu_check on a DeviceFields with the dataset's parameters."""
-    p = ca.Params.from_dict(ds.params)
-    ca.check(lib.cloudsc_gpu_init(0, C.byref(p)))
-    ws = C.c_void_p()
-    nbytes = lib.cloudsc_gpu_scratch_bytes(df.precision, variant, df.ngptot, df.nproma, df.klev)
-    assert nbytes >= 0
-    try:
-        if nbytes > 0:
-            assert hip.hipMalloc(C.byref(ws), C.c_size_t(nbytes)) == 0
-            assert hip.hipMemset(ws, 0, C.c_size_t(256)) == 0
-        ca.check(lib.cloudsc_gpu_run(0, None, df.precision, variant, df.ngptot, df.nproma, df.klev, C.byref(df.f), ws))
-        assert lib.cloudsc_gpu_check(0, None, variant, ws) == 0
-    finally:
-        if ws.value:
-            hip.hipFree(ws)
-
-
 def levels_inputs(ds, n):
     """The dataset's inputs at n columns as [ngptot][rows] / [ngptot] float64 (int32 ktype) arrays."""
     host = ca.make_host_state(ds, n, n, ca.FP64)

@@ -11,8 +11,7 @@ import cloudsc_amd as ca
 import form_state_cases as fs
 import mixed_expected as mx
 import tendbuf_cases as tb
-import test_outputs_cpu as oc
-import test_tendbuf_cpu as tc
+import host_harness as oc
 
 N = fs.NGPTOT
 SHAPES = [(N, 64), (N, 16)]
@@ -93,5 +92,5 @@ def test_cpu_tendbuf_on_state(ds, scenarios, oracle_mod, name, precision):
     s = fs.dataset(name, ds, scenarios)
     exp = expected_bits(oracle_mod, name, s, PRECISIONS[precision])
     for ngptot, nproma in SHAPES:
-        got = tc.run_tendbuf_checked(s, ngptot, nproma, PRECISIONS[precision], 11, "permuted", key="forms:" + name)
+        got = oc.run_tendbuf_checked(s, ngptot, nproma, PRECISIONS[precision], 11, "permuted", key="forms:" + name)
         assert differing(got, exp, ngptot, fs.NAMES) == [], nproma

@@ -12,88 +12,19 @@ tests/test_outputs_gpu.py and tests/test_narrow_pack_gpu.py; the plain run itsel
 Shapes: 100 columns (each template column once) in blocks of 64 (unpacked, a last block of 36), of 16 (four
 blocks per wave, the last group three blocks, the last block four columns) and, for the packed form alone,
 of 5 (twelve blocks per wave, 60 lanes)."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import cloudsc_amd as ca
 import form_state_cases as fs
-import mixed_expected as mx
-import test_narrow_pack_gpu as npk
-from test_narrow_pack_gpu import Run
-from test_outputs_gpu import Sets, prognostic_parity
-from test_tendbuf_gpu import Pair
+from form_state_cases import ORDER, TEND_PLANES, schedules, shapes
+from gpu_harness import PRECISIONS, Pair, Run, Sets, columns, pattern_like, prognostic_parity, widened_bits
+from gpu_harness import form_knobs, pack_of, plain_is_pinned, plain_knobs
+from gpu_harness import lib, hip, restore_knobs  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
-N = fs.NGPTOT
-PRECISIONS = {"fp64": ca.FP64, "fp32": ca.FP32, "mixed": ca.MIXED}
-VARIANTS = (ca.VARIANT_KCACHE, ca.VARIANT_KSEG)
-TEND_PLANES, ORDER = 11, "permuted"
-
-
-@pytest.fixture(scope="module")
-def lib():
-    lib = ca.gpu_lib()
-    assert ca.device_count() > 0
-    return lib
-
-
-@pytest.fixture(scope="module")
-def hip():
-    h = ca._hip()
-    h.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
-    return h
-
-
-@pytest.fixture(autouse=True)
-def restore_knobs():
-    yield
-    ca.narrow_pack(-1)
-    ca.kseg_schedule(0, 0)
-
-
-def shapes(name, packed_form=False):
-    if packed_form:
-        return [(N, 16)] if name == "klev274" else [(N, 16), (N, 5)]
-    return [(N, 64), (N, 16)]
-
-
-def schedules(name, variant):
-    """(segments, workgroups) of the form's launches: KSEG also with two hand-offs per column."""
-    if variant != ca.VARIANT_KSEG or name == "klev3":
-        return [(0, 0)]
-    return [(0, 0), (3, 3)]
-
-
-def columns(blocks):
-    return np.ascontiguousarray(ca.blocks_to_columns(blocks, N))
-
-
-def pack_of(s, precision, variant, nproma):
-    return ca.launch_geometry(precision, variant, N, nproma, s.klev, laer=fs.uses_aerosols(s))["pack"]
-
-
-def plain_is_pinned(out, oracle_mod, name, s, precision):
-    """The plain unpacked run ({field: [..][N]}) against the oracle (fp64) / the contract (mixed)."""
-    if precision == ca.FP64:
-        ref = fs.oracle_outputs(oracle_mod, name, s)
-        assert [k for k in fs.NAMES if not np.array_equal(npk.bits(out[k]), npk.bits(ref[k]))] == []
-    elif precision == ca.MIXED:
-        assert mx.mismatches(out, mx.expected(oracle_mod, s, N, fs.ORACLE_NPROMA, key="forms:" + name)) == {}
-
-
-def plain_knobs():
-    """The reference launch: never packed, the default schedule."""
-    ca.narrow_pack(0)
-    ca.kseg_schedule(0, 0)
-
-
-def form_knobs(sched):
-    """The form's launch: packed where the library packs by default (NPROMA <= 16), the schedule under test."""
-    ca.narrow_pack(-1)
-    ca.kseg_schedule(*sched)
+VARIANTS = fs.VARIANTS
 
 
 @pytest.mark.parametrize("precision", sorted(PRECISIONS))
@@ -109,7 +40,7 @@ def test_tendbuf_form_on_state(lib, hip, ds, scenarios, oracle_mod, name, precis
                 plain_knobs()
                 assert pack_of(s, prec, variant, nproma) == 1
                 pr.run_both(variant, which=("plain",))
-                plain_is_pinned({k: columns(pr.plain.download_raw(k)) for k in fs.NAMES}, oracle_mod, name, s, prec)
+                plain_is_pinned({k: columns(pr.plain.download_raw(k), fs.NGPTOT) for k in fs.NAMES}, oracle_mod, name, s, prec)
                 for sched in schedules(name, variant):
                     pr.fill(("packed",))
                     form_knobs(sched)
@@ -135,7 +66,7 @@ def test_prognostic_form_on_state(lib, hip, ds, scenarios, oracle_mod, name, pre
                 plain_knobs()
                 assert pack_of(s, prec, variant, nproma) == 1
                 st.run("all", variant, None)
-                plain_is_pinned({k: columns(st.sets["all"].download_raw(k)) for k in fs.NAMES}, oracle_mod, name, s,
+                plain_is_pinned({k: columns(st.sets["all"].download_raw(k), fs.NGPTOT) for k in fs.NAMES}, oracle_mod, name, s,
                                 prec)
                 for sched in schedules(name, variant):
                     for w in ("null", "kept"):
@@ -145,7 +76,7 @@ def test_prognostic_form_on_state(lib, hip, ds, scenarios, oracle_mod, name, pre
                     prognostic_parity(st, variant, oracle, run_all=False)
                     if fs.rain_active(name):          # the carried rain flux reached its output
                         for w in ("null", "kept"):
-                            assert np.count_nonzero(columns(st.sets[w].download_raw("pfplsl"))) > 0, (nproma, w)
+                            assert np.count_nonzero(columns(st.sets[w].download_raw("pfplsl"), fs.NGPTOT)) > 0, (nproma, w)
         finally:
             st.close()
 
@@ -167,19 +98,16 @@ def test_packed_form_on_state(lib, ds, scenarios, oracle_mod, name, precision):
                 for sched in schedules(name, variant):
                     out = on.launch(variant, 1, sched)
                     assert pack_of(s, prec, variant, nproma) == 64 // nproma
-                    d = ca.compare_fields(ca.fields_subset(on.df.f, fs.NAMES), ca.fields_subset(off.df.f, fs.NAMES),
-                                          ngptot, s.klev, prec, nproma, prec, nproma)
-                    assert sorted(d) == sorted(fs.NAMES) and all(v["compared"] > 0 for v in d.values())
-                    assert {k: v["mismatches"] for k, v in d.items() if v["mismatches"]} == {}, (nproma, variant, sched)
+                    assert on.mismatches(on.df.f, off.df.f, fs.NAMES) == {}, (nproma, variant, sched)
                     for k in fs.NAMES:
                         where = (nproma, variant, sched, k)
-                        assert np.array_equal(npk.bits(out[k]), npk.bits(ref[k])), where
-                        a, pat = out[k], npk.pattern_like(on.host[k]).astype(np.float64)
+                        assert np.array_equal(widened_bits(out[k]), widened_bits(ref[k])), where
+                        a, pat = out[k], pattern_like(on.host[k]).astype(np.float64)
                         assert a.shape[0] == nb + 1
-                        assert np.array_equal(npk.bits(a[nb:]), npk.bits(pat[nb:])), where + ("past the last block",)
-                        assert np.array_equal(npk.bits(a[nb - 1, ..., tail:]), npk.bits(pat[nb - 1, ..., tail:])), \
+                        assert np.array_equal(widened_bits(a[nb:]), widened_bits(pat[nb:])), where + ("past the last block",)
+                        assert np.array_equal(widened_bits(a[nb - 1, ..., tail:]), widened_bits(pat[nb - 1, ..., tail:])), \
                             where + ("padding",)
-                        assert not np.array_equal(npk.bits(a[:nb - 1]), npk.bits(pat[:nb - 1])), where + ("not written",)
+                        assert not np.array_equal(widened_bits(a[:nb - 1]), widened_bits(pat[:nb - 1])), where + ("not written",)
         finally:
             off.close()
             on.close()

@@ -11,9 +11,9 @@ import pytest
 
 import cloudsc_amd as ca
 import form_state_cases as fs
-import test_forms_states_gpu as fg
-from test_forms_states_gpu import hip, lib, restore_knobs   # noqa: F401  (fixtures)
-from test_tendbuf_outputs_gpu import KEPT, PROG, ProgPair
+import gpu_harness as fg
+from gpu_harness import KEPT, ProgPair
+from gpu_harness import lib, hip, restore_knobs  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -22,25 +22,25 @@ pytestmark = pytest.mark.gpu
 @pytest.mark.parametrize("name", fs.STATES)
 def test_tendbuf_prognostic_form_on_state(lib, hip, ds, scenarios, oracle_mod, name, precision):
     s, prec = fs.dataset(name, ds, scenarios), fg.PRECISIONS[precision]
-    for ngptot, nproma in fg.shapes(name):
-        pr = ProgPair(lib, hip, s, ngptot, nproma, prec, fg.TEND_PLANES, fg.ORDER)
+    for ngptot, nproma in fs.shapes(name):
+        pr = ProgPair(lib, hip, s, ngptot, nproma, prec, fs.TEND_PLANES, fs.ORDER)
         try:
             assert pr.aer == (name == "aerosol_W")
-            for variant in fg.VARIANTS:
+            for variant in fs.VARIANTS:
                 pr.fill(("plain",))
                 fg.plain_knobs()
                 assert fg.pack_of(s, prec, variant, nproma) == 1
                 pr.run_both(variant, which=("plain",))
-                fg.plain_is_pinned({k: fg.columns(pr.plain.download_raw(k)) for k in fs.NAMES}, oracle_mod, name, s,
+                fg.plain_is_pinned({k: fg.columns(pr.plain.download_raw(k), ngptot) for k in fs.NAMES}, oracle_mod, name, s,
                                    prec)
-                for i, sched in enumerate(fg.schedules(name, variant)):
+                for i, sched in enumerate(fs.schedules(name, variant)):
                     pr.fill(("packed",))
                     fg.form_knobs(sched)
                     assert fg.pack_of(s, prec, variant, nproma) == (4 if nproma == 16 else 1)
-                    pr.run_form(variant, PROG, "kept" if i else "null")
+                    pr.run_form(variant, ca.OUTPUTS_PROGNOSTIC, "kept" if i else "null")
                     assert pr.device_mismatches_inplace(KEPT) == {}, (nproma, variant, sched)
                     assert pr.host_check_form() == [], (nproma, variant, sched)
                     if fs.rain_active(name):          # the carried rain flux reached its output
-                        assert np.count_nonzero(fg.columns(pr.packed.download_raw("pfplsl"))) > 0, (nproma, variant)
+                        assert np.count_nonzero(fg.columns(pr.packed.download_raw("pfplsl"), ngptot)) > 0, (nproma, variant)
         finally:
             pr.close()

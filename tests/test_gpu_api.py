@@ -17,16 +17,10 @@ import numpy as np
 import pytest
 
 import cloudsc_amd as ca
-from test_gpu_parity import bitwise_mismatches, field_report, oracle_outputs, rel_l1
+from gpu_harness import bitwise_mismatches, field_report, fp32_gates, init_params, kseg_workspace, oracle_outputs
+from gpu_harness import lib  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def lib():
-    lib = ca.gpu_lib()
-    assert ca.device_count() > 0
-    return lib
 
 
 def outputs_of(g, variant, reps=1):
@@ -221,7 +215,6 @@ def test_bitwise_fp32_full_size(lib, ds, oracle_mod):
         assert g_rep[k][0] <= 2.0 * c_rep[k][0] + 1e-6, k
     # BASELINE config 4 as the bench runs it: the float-internal exp/pow, gated
     # by tolerance (relL1 <= 1e-4 per field vs the restatement, <= 2x its error vs reference.h5)
-    from test_gpu_parity import fp32_gates
     fp32_gates(fast, ref, gold, c_rep)
 
 
@@ -481,12 +474,8 @@ def test_fields_alloc_reference_driver_shape(lib, ds, precision, variant):
         assert not any(getattr(df.f, n) for n in ca.AEROSOL_FIELDS)
         st = ca.make_host_state(ds, ngptot, nproma, precision)
         df.upload({k: v for k, v in st.arrays.items() if k in ca.INPUT_FIELDS or k == "plude"})
-        p = ca.Params.from_dict(ds.params)
-        ca.check(lib.cloudsc_gpu_init(0, C.byref(p)))
-        nbytes = lib.cloudsc_gpu_scratch_bytes(precision, variant, ngptot, nproma, ds.klev)
-        if nbytes > 0:
-            assert hip.hipMalloc(C.byref(ws), C.c_size_t(nbytes)) == 0
-            assert hip.hipMemset(ws, 0, C.c_size_t(256)) == 0
+        init_params(lib, ds.params)
+        ws = kseg_workspace(lib, hip, precision, variant, ngptot, nproma, ds.klev)
         ca.check(lib.cloudsc_gpu_run(0, None, precision, variant, ngptot, nproma, ds.klev, C.byref(df.f), ws))
         ca.check(lib.cloudsc_gpu_check(0, None, variant, ws))
         assert bitwise_mismatches(device_outputs(df, ngptot), ref) == {}

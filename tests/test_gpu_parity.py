@@ -16,32 +16,14 @@ import numpy as np
 import pytest
 
 import cloudsc_amd as ca
+from gpu_harness import RELL1_FP32_FAST, bitwise_mismatches, field_report, fp32_gates, oracle_outputs, rel_l1  # noqa: F401
+from gpu_harness import lib  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
 
 RELL1_FP64 = 1e-12
 MAXREL_FP64 = 1e-10
 RELL1_FP32_VS_SP_ORACLE = 1e-3
-
-
-def rel_l1(a, r):
-    a = np.asarray(a, dtype=np.float64)
-    r = np.asarray(r, dtype=np.float64)
-    den = np.abs(r).sum()
-    num = np.abs(a - r).sum()
-    return num / den if den > 0 else num
-
-
-def field_report(out, ref):
-    rep = {}
-    for _, k in ca.VALIDATED:
-        a, r = out[k], ref[k]
-        assert a.shape == r.shape, (k, a.shape, r.shape)
-        assert np.all(np.isfinite(a)), k
-        d = np.abs(a.astype(np.float64) - r.astype(np.float64))
-        mref = float(np.abs(r).max())
-        rep[k] = (rel_l1(a, r), float(d.max()), mref)
-    return rep
 
 
 def assert_close(rep, rell1, maxrel, label):
@@ -53,19 +35,6 @@ def assert_close(rep, rell1, maxrel, label):
     worst = max(rep.items(), key=lambda kv: kv[1][0])
     print("[%s] worst relL1 %s = %.3e" % (label, worst[0], worst[1][0]))
     assert not bad, "%s: fields out of tolerance:\n  " % label + "\n  ".join(bad)
-
-
-def oracle_outputs(oracle_mod, ds, ngptot, nproma, precision=ca.FP64):
-    st, _ = oracle_mod.run_oracle(ds, ngptot, nproma, precision)
-    return ca.state_outputs_to_template(st.arrays, ngptot)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    lib = ca.gpu_lib()
-    n = __import__("ctypes").c_int()
-    assert lib.cloudsc_gpu_device_count(__import__("ctypes").byref(n)) == 0 and n.value > 0
-    return lib
 
 
 def run_gpu(ds, ngptot, nproma, precision=ca.FP64, variant=ca.VARIANT_KCACHE, col_offset=0):
@@ -510,17 +479,6 @@ def test_invalid_arguments(lib, ds):
 # division is correctly rounded and no multiply-add is contracted, so the fp64
 # GPU kernels reproduce the reference kernel (and its restatement, the oracle)
 # bit for bit.  Scenario goldens W/M are the reference kernel's own outputs.
-def bitwise_mismatches(out, ref):
-    bad = {}
-    for _, k in ca.VALIDATED:
-        a = np.ascontiguousarray(out[k], dtype=np.float64).view(np.uint64)
-        r = np.ascontiguousarray(ref[k], dtype=np.float64).view(np.uint64)
-        n = int(np.count_nonzero(a != r))
-        if n:
-            bad[k] = (n, rel_l1(out[k], ref[k]))
-    return bad
-
-
 @pytest.mark.parametrize("variant", [ca.VARIANT_KCACHE, ca.VARIANT_KSEG, ca.VARIANT_SCC])
 @pytest.mark.parametrize("ngptot,nproma", [(100, 128), (1000, 128), (1000, 64), (1000, 100), (1000, 256)])
 def test_bitwise_vs_oracle(lib, ds, oracle_mod, variant, ngptot, nproma):
@@ -753,7 +711,6 @@ def test_bitwise_fp32_other_configurations(lib, ds, oracle_mod, case, variant):
 # the same size of perturbation at more sites, so the floor can under-state the
 # fast kernels' legitimate spread; the fixed 1e-4 gate on the reference state
 # and test_fp32_fast_division_range below bound the divisions directly.
-RELL1_FP32_FAST = 1e-4
 
 
 def nudge_floor(oracle_mod, s, n, nproma, seeds=(1, 2, 3, 4)):
@@ -765,19 +722,6 @@ def nudge_floor(oracle_mod, s, n, nproma, seeds=(1, 2, 3, 4)):
         o = ca.state_outputs_to_template(st.arrays, n)
         worst = max(worst, max(rel_l1(o[k], base[k]) for _, k in ca.VALIDATED))
     return worst
-
-
-def fp32_gates(out, ref, gold, cpu_vs_gold):
-    """relL1 <= 1e-4 per field vs the fp32 restatement, and vs reference.h5 no
-    worse than 2x the fp32 restatement's own error plus a floor."""
-    rep = field_report(out, ref)
-    for k, v in sorted(rep.items(), key=lambda kv: -kv[1][0])[:6]:
-        print("fp32 fast libm vs fp32 restatement %-18s relL1 %.3e" % (k, v[0]))
-    bad = {k: v[0] for k, v in rep.items() if not v[0] <= RELL1_FP32_FAST}
-    assert bad == {}, bad
-    g = field_report(out, gold)
-    for k in g:
-        assert g[k][0] <= 2.0 * cpu_vs_gold[k][0] + 1e-6, (k, g[k][0], cpu_vs_gold[k][0])
 
 
 @pytest.mark.parametrize("variant", [ca.VARIANT_KSEG, ca.VARIANT_KCACHE, ca.VARIANT_SCC, ca.VARIANT_SCC_PRIVATE])

@@ -13,6 +13,7 @@ import pytest
 
 import cloudsc_amd as ca
 import mixed_expected as mx
+from host_harness import configured
 
 
 def cpu_mixed(ds, ngptot, nproma, nthreads=4):
@@ -31,35 +32,6 @@ def test_cpu_mixed_bitwise_shapes(ds, oracle_mod, ngptot, nproma):
     exp = mx.expected(oracle_mod, ds, ngptot, nproma, key="ref100")
     assert mx.all_finite(exp)
     assert mx.mismatches(cpu_mixed(ds, ngptot, nproma), exp) == {}
-
-
-def configured(ds, case):
-    import make_fixtures as mf
-    s = ds.copy()
-    s.params = dict(s.params)
-    if case.startswith("nssopt"):
-        s.params["nssopt"] = int(case[-1])
-    elif case == "aerosol":
-        s = mf.with_aerosols(ds)
-    elif case == "aerosol_sed":
-        s = mf.with_aerosols(ds)
-        s.params["laericeauto"] = 0
-    elif case == "aerosol_auto":
-        s = mf.with_aerosols(ds)
-        s.params["laericesed"] = 0
-    elif case.startswith("ncldtop"):
-        s.params["ncldtop"] = int(case[len("ncldtop"):])
-    elif case.startswith("klev"):
-        s = mf.sliced_levels(ds, ds.klev - int(case[4:]))
-        s.params = dict(s.params)
-        s.params["ncldtop"] = 2
-    elif case in ("cold", "dry", "moist"):
-        s = mf.shifted(ds, case)
-    elif case.startswith("seed"):
-        s = mf.perturbed(ds, int(case[4:]))
-    else:
-        raise ValueError(case)
-    return s
 
 
 CONFIGS = ["nssopt0", "nssopt2", "nssopt3", "aerosol", "aerosol_sed", "aerosol_auto", "ncldtop2", "ncldtop138",

@@ -15,15 +15,10 @@ import pytest
 
 import cloudsc_amd as ca
 import mixed_expected as mx
+from gpu_harness import init_params, kseg_workspace, lib, uses_aerosols  # noqa: F401  (lib: fixture)
+from host_harness import configured
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def lib():
-    lib = ca.gpu_lib()
-    assert ca.device_count() > 0
-    return lib
 
 
 @pytest.fixture
@@ -36,21 +31,15 @@ def device_run(lib, ds, ngptot, nproma, variant, schedules=((0, 0),), precision=
     """cloudsc_gpu_run on caller-owned buffers (DeviceFields), plude restored
     before every launch; yields the outputs of each schedule.  KSEG runs on a
     workspace of cloudsc_gpu_scratch_bytes and is followed by cloudsc_gpu_check."""
-    aer = bool(ds.params.get("laericesed") or ds.params.get("laericeauto"))
-    df = ca.DeviceFields(ngptot, nproma, ds.klev, precision, place=False, aerosols=aer)
+    df = ca.DeviceFields(ngptot, nproma, ds.klev, precision, place=False, aerosols=uses_aerosols(ds))
     hip = ca._hip()
     ws = C.c_void_p()
     outs = []
     try:
         st = ca.make_host_state(ds, ngptot, nproma, precision)
         ins = {k: v for k, v in st.arrays.items() if k not in ca.OUTPUT_FIELDS}
-        p = ca.Params.from_dict(ds.params)
-        ca.check(lib.cloudsc_gpu_init(0, C.byref(p)))
-        nbytes = lib.cloudsc_gpu_scratch_bytes(precision, variant, ngptot, nproma, ds.klev)
-        assert nbytes >= 0
-        if nbytes > 0:
-            assert hip.hipMalloc(C.byref(ws), C.c_size_t(nbytes)) == 0
-            assert hip.hipMemset(ws, 0, C.c_size_t(256)) == 0
+        init_params(lib, ds.params)
+        ws = kseg_workspace(lib, hip, precision, variant, ngptot, nproma, ds.klev)
         for nseg, grid in schedules:
             df.upload(ins)
             ca.kseg_schedule(nseg, grid)
@@ -167,7 +156,6 @@ PARAM_EDGES = ("ptsphy_60", "ptsphy_900", "ptsphy_1234.567", "ptsphy_7200", "tun
 
 def case_state(ds, case):
     import make_fixtures as mf
-    from test_mixed_cpu import configured
     if case == "ref100":
         return ds
     if case in EDGES:

@@ -2,13 +2,14 @@
 no lane's arithmetic, so every comparison is on raw bits: against the fp64
 oracle, the mixed-precision contract (tests/mixed_expected.py), the fp32
 restatement, and the unpacked kernels on the same buffers."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import cloudsc_amd as ca
 import mixed_expected as mx
+from gpu_harness import NAMES, Run, oracle_columns, pattern_like, widened_bits as bits
+from gpu_harness import lib, restore_knobs  # noqa: F401  (fixtures)
+from host_harness import configured
 
 pytestmark = pytest.mark.gpu
 
@@ -24,111 +25,11 @@ SHAPES = [
 ]
 PACK_OF = {32: 2, 16: 4, 8: 8, 1: 64, 24: 2, 5: 12, 33: 1}
 KCACHES = [ca.VARIANT_KCACHE, ca.VARIANT_KSEG]
-NAMES = [k for _, k in ca.VALIDATED]           # the 20 outputs and plude
-PATTERN = 0xA5
-
-
-@pytest.fixture(scope="module")
-def lib():
-    lib = ca.gpu_lib()
-    assert ca.device_count() > 0
-    return lib
-
-
-@pytest.fixture(autouse=True)
-def restore_knobs():
-    yield
-    ca.narrow_pack(-1)
-    ca.kseg_schedule(0, 0)
-
-
-_oracle = {}
-
-
-def oracle_columns(oracle_mod, ds, ngptot, nproma, precision=ca.FP64, key="ref100"):
-    """{field: [..][ngptot]} of the restatement, computed once per shape and left unchanged."""
-    ck = (key, ngptot, nproma, precision)
-    if ck not in _oracle:
-        st, _ = oracle_mod.run_oracle(ds, ngptot, nproma, precision)
-        out = {k: np.ascontiguousarray(ca.blocks_to_columns(st.arrays[k], ngptot)) for k in NAMES}
-        for a in out.values():
-            a.setflags(write=False)
-        _oracle[ck] = out
-    return _oracle[ck]
-
-
-def bits(a):
-    """Raw bits of a field as downloaded (float64 holding the storage type's values: widening is injective)."""
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
 def differing(out, ref):
     return {k: int(np.count_nonzero(bits(out[k]) != bits(ref[k]))) for k in NAMES
             if not np.array_equal(bits(out[k]), bits(ref[k]))}
-
-
-def pattern_like(a):
-    p = np.empty_like(a)
-    p.view(np.uint8)[...] = PATTERN
-    return p
-
-
-class Run:
-    """cloudsc_gpu_run on caller-owned buffers (DeviceFields) that are
-    `extra_blocks` NPROMA blocks longer than the run needs.  Before every launch
-    the inputs are uploaded again and every output buffer, plude's padding lanes
-    and the extra blocks are filled with a byte pattern."""
-
-    def __init__(self, lib, ds, ngptot, nproma, precision=ca.FP64, extra_blocks=0):
-        self.lib, self.ds, self.ngptot, self.nproma, self.precision = lib, ds, ngptot, nproma, precision
-        self.nb = ca.nblocks_of(ngptot, nproma)
-        aer = bool(ds.params.get("laericesed") or ds.params.get("laericeauto"))
-        self.df = ca.DeviceFields((self.nb + extra_blocks) * nproma, nproma, ds.klev, precision, place=False,
-                                  aerosols=aer)
-        self.hip = ca._hip()
-        self.ws = C.c_void_p()
-        st = ca.make_host_state(ds, ngptot, nproma, precision)
-        self.host = {}
-        for name, a in st.arrays.items():
-            if getattr(self.df.f, name, None) is None:
-                continue
-            a = np.ascontiguousarray(a)
-            if name in ca.OUTPUT_FIELDS and name != "plude":
-                a = pattern_like(a)
-            if name == "plude":                     # INOUT: the pattern in the lanes past the last column
-                a = a.copy()
-                tail = ngptot - (self.nb - 1) * nproma
-                a[self.nb - 1, ..., tail:] = pattern_like(a[self.nb - 1, ..., tail:])
-            if extra_blocks:
-                a = np.concatenate([a, pattern_like(np.repeat(a[:1], extra_blocks, axis=0))], axis=0)
-            self.host[name] = a
-        p = ca.Params.from_dict(ds.params)
-        ca.check(lib.cloudsc_gpu_init(0, C.byref(p)))
-
-    def launch(self, variant, pack, schedule=(0, 0)):
-        """One step; returns {field: block-layout array of the WHOLE buffer}."""
-        lib = self.lib
-        if variant & 0xff == ca.VARIANT_KSEG and not self.ws.value:
-            nbytes = lib.cloudsc_gpu_scratch_bytes(self.precision, variant & 0xff, self.ngptot, self.nproma, self.ds.klev)
-            assert nbytes > 0
-            assert self.hip.hipMalloc(C.byref(self.ws), C.c_size_t(nbytes)) == 0
-            assert self.hip.hipMemset(self.ws, 0, C.c_size_t(256)) == 0
-        self.df.upload(self.host)
-        ca.narrow_pack(pack)
-        ca.kseg_schedule(*schedule)
-        ca.check(lib.cloudsc_gpu_run(0, None, self.precision, variant, self.ngptot, self.nproma, self.ds.klev,
-                                     C.byref(self.df.f), self.ws))
-        assert lib.cloudsc_gpu_check(0, None, variant & 0xff, self.ws) == 0
-        return {k: self.df.download(k) for k in NAMES}
-
-    def columns(self, blocks):
-        return {k: ca.blocks_to_columns(a[:self.nb], self.ngptot) for k, a in blocks.items()}
-
-    def close(self):
-        if self.ws.value:
-            self.hip.hipFree(self.ws)
-            self.ws = C.c_void_p()
-        self.df.close()
 
 
 def geometry_pack(ds, precision, variant, ngptot, nproma):
@@ -140,7 +41,7 @@ def geometry_pack(ds, precision, variant, ngptot, nproma):
 # ---------------------------------------------------------------------------
 @pytest.mark.parametrize("ngptot,nproma", SHAPES)
 def test_fp64_packed_vs_oracle_device_fields(lib, ds, oracle_mod, ngptot, nproma):
-    ref = oracle_columns(oracle_mod, ds, ngptot, nproma)
+    ref = oracle_columns(oracle_mod, ds, "ds", ngptot, nproma)
     r = Run(lib, ds, ngptot, nproma)
     try:
         for variant in KCACHES:
@@ -154,7 +55,7 @@ def test_fp64_packed_vs_oracle_device_fields(lib, ds, oracle_mod, ngptot, nproma
 @pytest.mark.parametrize("ngptot,nproma", SHAPES)
 def test_fp64_packed_vs_oracle_state(lib, ds, oracle_mod, ngptot, nproma):
     """Through GpuState: repeated steps continue the workspace's counters and flag stamps."""
-    ref = oracle_columns(oracle_mod, ds, ngptot, nproma)
+    ref = oracle_columns(oracle_mod, ds, "ds", ngptot, nproma)
     ca.narrow_pack(1)
     g = ca.GpuState(ds, ngptot, nproma, ca.FP64)
     try:
@@ -194,7 +95,7 @@ def test_mixed_packed_vs_contract(lib, ds, oracle_mod, ngptot, nproma):
 
 def test_fp32_exact_libm_packed_vs_restatement(lib, ds, oracle_mod):
     ngptot, nproma = 100, 16
-    ref = oracle_columns(oracle_mod, ds, ngptot, nproma, ca.FP32)
+    ref = oracle_columns(oracle_mod, ds, "ds", ngptot, nproma, ca.FP32)
     r = Run(lib, ds, ngptot, nproma, ca.FP32)
     try:
         for variant in KCACHES:
@@ -240,7 +141,7 @@ KSEG_SCHEDULES = ((1, 1), (1, 3), (2, 1), (2, 3), (3, 1), (3, 3))
 
 @pytest.mark.parametrize("ngptot,nproma", [(100, 16), (70, 1)])
 def test_kseg_handoffs_across_packed_groups(lib, ds, oracle_mod, ngptot, nproma):
-    ref = oracle_columns(oracle_mod, ds, ngptot, nproma)
+    ref = oracle_columns(oracle_mod, ds, "ds", ngptot, nproma)
     r = Run(lib, ds, ngptot, nproma)
     try:
         for sched in KSEG_SCHEDULES:
@@ -256,11 +157,10 @@ def test_kseg_handoffs_across_packed_groups(lib, ds, oracle_mod, ngptot, nproma)
 # aerosols, host pipeline, restore
 # ---------------------------------------------------------------------------
 def test_aerosol_kernels_packed(lib, ds, oracle_mod):
-    from test_mixed_cpu import configured
     s = configured(ds, "aerosol")
     assert s.params["laericesed"] and s.params["laericeauto"]
     ngptot, nproma = 100, 16
-    ref = oracle_columns(oracle_mod, s, ngptot, nproma, key="aerosol")
+    ref = oracle_columns(oracle_mod, s, "aerosol", ngptot, nproma)
     r = Run(lib, s, ngptot, nproma)
     try:
         ca.narrow_pack(1)
@@ -269,12 +169,12 @@ def test_aerosol_kernels_packed(lib, ds, oracle_mod):
             assert differing(r.columns(r.launch(variant, 1)), ref) == {}, variant
     finally:
         r.close()
-    assert differing(ref, oracle_columns(oracle_mod, ds, ngptot, nproma)) != {}    # the aerosol inputs matter
+    assert differing(ref, oracle_columns(oracle_mod, ds, "ds", ngptot, nproma)) != {}    # the aerosol inputs matter
 
 
 def test_host_pipeline_packed_equals_unpacked(lib, ds, oracle_mod):
     ngptot, nproma = 130, 32
-    ref = oracle_columns(oracle_mod, ds, ngptot, nproma)
+    ref = oracle_columns(oracle_mod, ds, "ds", ngptot, nproma)
     hp = ca.HostPipeline(ds, ngptot, nproma, chunk_blocks=2, nstreams=2)
     try:
         outs = {}
@@ -293,7 +193,7 @@ def test_restore_default_then_wide_blocks(lib, ds, oracle_mod):
     ca.narrow_pack(-1)
     ngptot, nproma = 130, 64
     assert ca.launch_geometry(ca.FP64, ca.VARIANT_KSEG, ngptot, nproma, ds.klev)["pack"] == 1
-    ref = oracle_columns(oracle_mod, ds, ngptot, nproma)
+    ref = oracle_columns(oracle_mod, ds, "ds", ngptot, nproma)
     r = Run(lib, ds, ngptot, nproma)
     try:
         for variant in KCACHES:

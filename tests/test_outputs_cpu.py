@@ -8,22 +8,14 @@ import numpy as np
 import pytest
 
 import cloudsc_amd as ca
+from host_harness import ALL21, DIAG, KEPT, KLEV, SENTINEL, bits, check_kept, columns, full_fields, plain_run, run_selected
 
-KLEV = 137
-DIAG = ca.DIAGNOSTIC_FLUX_FIELDS
-KEPT = ca.selected_outputs(ca.OUTPUTS_PROGNOSTIC)
-ALL21 = ca.selected_outputs(ca.OUTPUTS_ALL)
-SENTINEL = 0xA7
 SHAPES = [(300, 64), (100, 16), (70, 32), (1, 1), (300, 300)]
 
 
 @pytest.fixture(scope="module")
 def lib():
     return ca.gpu_lib()
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint8)
 
 
 def test_the_selection_names_ten_and_eleven():
@@ -40,14 +32,6 @@ def test_the_selection_names_ten_and_eleven():
 # ---------------------------------------------------------------------------
 # argument rules
 # ---------------------------------------------------------------------------
-def full_fields(without=()):
-    """A Fields with every member non-NULL but `without` (never dereferenced: the calls fail first)."""
-    f = ca.Fields()
-    for i, (n, _) in enumerate(ca.Fields._fields_):
-        setattr(f, n, None if n in without else 0x1000 + 0x100 * i)
-    return f
-
-
 def test_gpu_run_outputs_prognostic_rules_need_no_gpu(lib):
     f = full_fields()
     ws = C.c_void_p(0x10)
@@ -144,60 +128,6 @@ def test_fields_alloc_outputs_rules_need_no_gpu(lib):
 # ---------------------------------------------------------------------------
 # cloudsc_cpu_run_outputs
 # ---------------------------------------------------------------------------
-_plain = {}
-
-
-def plain_run(s, key, ngptot, nproma, precision):
-    """cloudsc_cpu_run_precision on the dataset s: {name: block-layout array}, once per case, read-only."""
-    key = (key, ngptot, nproma, precision)
-    if key not in _plain:
-        st, _ = ca.cpu_run(s, ngptot, nproma, nthreads=4, precision=precision)
-        for a in st.arrays.values():
-            a.setflags(write=False)
-        _plain[key] = st.arrays
-    return _plain[key]
-
-
-def columns(blocks, ngptot):
-    return np.ascontiguousarray(ca.blocks_to_columns(blocks, ngptot))
-
-
-def run_selected(s, ngptot, nproma, precision, outputs, diag):
-    """cloudsc_cpu_run_outputs on a fresh host state of s.  diag: "null" = the ten members NULL, "sentinel" =
-    pointing at sentinel-filled arrays, "state" = the state's own arrays.  Returns the state's arrays with the
-    ten members replaced by what the call was given (None for NULL)."""
-    st = ca.make_host_state(s, ngptot, nproma, precision)
-    # every output lane starts as sentinel bytes: padding lanes must keep them
-    for n in ALL21:
-        if n != "plude":
-            bits(st.arrays[n])[...] = SENTINEL
-    f = st.fields()
-    given = dict(st.arrays)
-    for n in DIAG:
-        if diag == "null":
-            setattr(f, n, None)
-            given[n] = None
-        elif diag == "sentinel":
-            a = np.empty_like(st.arrays[n])
-            bits(a)[...] = SENTINEL
-            setattr(f, n, a.ctypes.data)
-            given[n] = a
-    ca.cpu_run_outputs(ca.Params.from_dict(s.params), f, precision, outputs, ngptot, nproma, s.klev, nthreads=3)
-    return given
-
-
-def check_kept(got, ref, ngptot, nproma, names=KEPT):
-    bad = {}
-    for k in names:
-        if not np.array_equal(bits(columns(got[k], ngptot)), bits(columns(ref[k], ngptot))):
-            bad[k] = "differs from cloudsc_cpu_run_precision"
-        if ngptot % nproma and k != "plude":     # padding lanes of the last block keep the sentinel
-            pad = got[k][-1][..., ngptot % nproma:]
-            if not (bits(pad) == SENTINEL).all():
-                bad[k] = "padding lanes written"
-    assert bad == {}
-
-
 @pytest.mark.parametrize("diag", ["null", "sentinel"])
 @pytest.mark.parametrize("precision", [ca.FP64, ca.MIXED])
 @pytest.mark.parametrize("ngptot,nproma", SHAPES)

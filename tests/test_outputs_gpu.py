@@ -9,180 +9,12 @@ import numpy as np
 import pytest
 
 import cloudsc_amd as ca
+from gpu_harness import ALL21, CASES, DIAG, KEPT, PATTERN, PRECISIONS, VARIANTS
+from gpu_harness import Sets, columns, host_inputs, init_params, kseg_workspace, oracle_columns, prognostic_parity
+from gpu_harness import raw_bits as bits
+from gpu_harness import lib, hip, restore_knobs  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
-
-DIAG = ca.DIAGNOSTIC_FLUX_FIELDS
-KEPT = ca.selected_outputs(ca.OUTPUTS_PROGNOSTIC)
-ALL21 = ca.selected_outputs(ca.OUTPUTS_ALL)
-PATTERN = 0xC3
-PRECISIONS = {"fp64": ca.FP64, "fp32": ca.FP32, "mixed": ca.MIXED}
-VARIANTS = {"kcache": ca.VARIANT_KCACHE, "kseg": ca.VARIANT_KSEG}
-# partial last block | two sub-blocks per block under KSEG | packed by default | packed on request | one wide block
-SHAPES = [(300, 64), (200, 128), (100, 16), (70, 32), (300, 300)]
-
-
-@pytest.fixture(scope="module")
-def lib():
-    lib = ca.gpu_lib()
-    assert ca.device_count() > 0
-    return lib
-
-
-@pytest.fixture(scope="module")
-def hip():
-    h = ca._hip()
-    h.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
-    h.hipStreamCreateWithFlags.argtypes = [C.POINTER(C.c_void_p), C.c_uint]
-    h.hipStreamSynchronize.argtypes = [C.c_void_p]
-    h.hipStreamDestroy.argtypes = [C.c_void_p]
-    return h
-
-
-@pytest.fixture(autouse=True)
-def restore_knobs():
-    yield
-    ca.narrow_pack(-1)
-    ca.kseg_schedule(0, 0)
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint8)
-
-
-def columns(blocks, ngptot):
-    return np.ascontiguousarray(ca.blocks_to_columns(blocks, ngptot))
-
-
-def host_inputs(ds, ngptot, nproma, precision):
-    """Block-layout host arrays with every output (and plude's padding lanes) set to a byte pattern."""
-    st = ca.make_host_state(ds, ngptot, nproma, precision)
-    nb = ca.nblocks_of(ngptot, nproma)
-    out = {}
-    for name, a in st.arrays.items():
-        a = np.ascontiguousarray(a).copy()
-        if name in ca.OUTPUT_FIELDS:
-            a.view(np.uint8)[...] = PATTERN
-        if name == "plude":
-            tail = ngptot - (nb - 1) * nproma
-            a[nb - 1, ..., tail:].view(np.uint8)[...] = PATTERN
-        out[name] = a
-    return out
-
-
-_oracle = {}
-
-
-def oracle_columns(oracle_mod, ds, key, ngptot, nproma):
-    """The fp64 oracle's outputs as columns, once per (dataset, shape), read-only."""
-    k = (key, ngptot, nproma)
-    if k not in _oracle:
-        ost, _ = oracle_mod.run_oracle(ds, ngptot, nproma)
-        _oracle[k] = {n: columns(ost.arrays[n], ngptot) for n in ALL21}
-        for a in _oracle[k].values():
-            a.setflags(write=False)
-    return _oracle[k]
-
-
-class Sets:
-    """One problem on the device in several sets with the same inputs and pattern-filled outputs: "all"
-    (cloudsc_fields_alloc), "null" (cloudsc_fields_alloc_outputs(PROGNOSTIC): the ten members NULL) and "kept"
-    (all 21 allocated, run with PROGNOSTIC: the ten must keep the pattern)."""
-
-    def __init__(self, lib, hip, ds, ngptot, nproma, precision, which=("all", "null", "kept")):
-        self.lib, self.hip, self.ds = lib, hip, ds
-        self.ngptot, self.nproma, self.precision = ngptot, nproma, precision
-        self.aer = bool(ds.params.get("laericesed") or ds.params.get("laericeauto"))
-        self.host = host_inputs(ds, ngptot, nproma, precision)
-        self.ws = C.c_void_p()
-        self.sets = {}
-        for w in which:
-            outputs = ca.OUTPUTS_PROGNOSTIC if w == "null" else ca.OUTPUTS_ALL
-            self.sets[w] = ca.DeviceFields(ngptot, nproma, ds.klev, precision, place=False, aerosols=self.aer,
-                                           outputs=outputs)
-            self.sets[w].upload(self.host)
-        p = ca.Params.from_dict(ds.params)
-        ca.check(lib.cloudsc_gpu_init(0, C.byref(p)))
-
-    def scratch(self, variant):
-        if variant & 0xff == ca.VARIANT_KSEG and not self.ws.value:
-            nbytes = self.lib.cloudsc_gpu_scratch_bytes(self.precision, ca.VARIANT_KSEG, self.ngptot, self.nproma,
-                                                        self.ds.klev)
-            assert nbytes > 0
-            assert self.hip.hipMalloc(C.byref(self.ws), C.c_size_t(nbytes)) == 0
-            assert self.hip.hipMemset(self.ws, 0, C.c_size_t(256)) == 0
-        return self.ws
-
-    def run(self, which, variant, outputs, stream=None):
-        """One step on a set (cloudsc_gpu_run for outputs None), followed by its check."""
-        ws = self.scratch(variant)
-        f = self.sets[which].f
-        if outputs is None:
-            ca.check(self.lib.cloudsc_gpu_run(0, stream, self.precision, variant, self.ngptot, self.nproma,
-                                              self.ds.klev, C.byref(f), ws))
-        else:
-            ca.gpu_run_outputs(f, self.precision, variant, outputs, self.ngptot, self.nproma, self.ds.klev, scratch=ws,
-                               stream=stream)
-        assert self.lib.cloudsc_gpu_check(0, stream, variant & 0xff, ws) == 0
-
-    def device_mismatches(self, which, names=KEPT, against="all", stream=None):
-        """cloudsc_fields_compare of `names` of a set against the "all" set's: {member: mismatches} where not 0."""
-        a = ca.fields_subset(self.sets[which].f, names)
-        b = ca.fields_subset(self.sets[against].f, names)
-        if names is KEPT:
-            assert not any(getattr(a, n) or getattr(b, n) for n in DIAG)    # NULL in both operands
-        d = ca.compare_fields(a, b, self.ngptot, self.ds.klev, self.precision, self.nproma, self.precision,
-                              self.nproma, stream=stream)
-        assert sorted(d) == sorted(names)
-        assert all(v["compared"] > 0 for v in d.values())
-        return {k: v["mismatches"] for k, v in d.items() if v["mismatches"]}
-
-    def host_check(self, which, names=KEPT, against="all", oracle=None):
-        """The same on the host, whole arrays (padding lanes included), and the pattern bytes: padding lanes
-        of every output, and every byte of a diagnostic member that was not to be written."""
-        self.hip.hipDeviceSynchronize()
-        wrong = []
-        tail = self.ngptot % self.nproma
-        for k in names:
-            got, ref = self.sets[which].download_raw(k), self.sets[against].download_raw(k)
-            if not np.array_equal(bits(got), bits(ref)):
-                wrong.append("%s: differs (padding included)" % k)
-            if tail and not (bits(got[-1][..., tail:]) == PATTERN).all():
-                wrong.append("%s: a padding lane was written" % k)
-            if oracle is not None and not np.array_equal(bits(columns(got, self.ngptot)), bits(oracle[k])):
-                wrong.append("%s: differs from the oracle" % k)
-        if names is KEPT:
-            for k in DIAG:
-                if getattr(self.sets[which].f, k) and not (bits(self.sets[which].download_raw(k)) == PATTERN).all():
-                    wrong.append("%s: written by a PROGNOSTIC run" % k)
-        return wrong
-
-    def close(self):
-        if self.ws.value:
-            self.hip.hipFree(self.ws)
-            self.ws = C.c_void_p()
-        for s in self.sets.values():
-            s.close()
-
-
-def prognostic_parity(s, variant, oracle=None, stream=None, run_all=True):
-    """cloudsc_gpu_run on "all" (run_all False: the caller has run it), PROGNOSTIC on "null" and "kept"; the
-    eleven kept members on the device and on the host."""
-    if run_all:
-        s.run("all", variant, None, stream)
-    for w in ("null", "kept"):
-        s.run(w, variant, ca.OUTPUTS_PROGNOSTIC, stream)
-        assert not any(getattr(s.sets["null"].f, n) for n in DIAG)
-        assert all(getattr(s.sets["kept"].f, n) for n in DIAG)
-        assert s.device_mismatches(w, stream=stream) == {}, w
-        assert s.host_check(w, oracle=oracle) == [], w
-    # the step did something: the reference run wrote the diagnostic fluxes and the kept outputs
-    assert not (bits(s.sets["all"].download_raw("pfsqlf")) == PATTERN).all()
-    assert not (bits(s.sets["null"].download_raw("pfplsn")) == PATTERN).all()
-
-
-CASES = [(n, p, v) for (n, p) in SHAPES for v in VARIANTS if not (p > 256 and v == "kcache")]
-
 
 @pytest.mark.parametrize("precision", sorted(PRECISIONS))
 @pytest.mark.parametrize("ngptot,nproma,variant", CASES)
@@ -297,12 +129,9 @@ def test_fields_alloc_outputs_prognostic(lib, hip, ds, oracle_mod, place):
             assert 0 < r["peak_transient_bytes"] <= r["transient_budget_bytes"], r
         else:
             assert r["method"] == "none" and r["launches"] == 0 and r["tries"] == 0, r
-        df.upload(host_inputs(ds, ngptot, nproma, ca.FP64))
-        p = ca.Params.from_dict(ds.params)
-        ca.check(lib.cloudsc_gpu_init(0, C.byref(p)))
-        nbytes = lib.cloudsc_gpu_scratch_bytes(ca.FP64, ca.VARIANT_KSEG, ngptot, nproma, ds.klev)
-        assert hip.hipMalloc(C.byref(ws), C.c_size_t(nbytes)) == 0
-        assert hip.hipMemset(ws, 0, C.c_size_t(256)) == 0
+        df.upload(host_inputs(ds, ngptot, nproma, ca.FP64, PATTERN))
+        init_params(lib, ds.params)
+        ws = kseg_workspace(lib, hip, ca.FP64, ca.VARIANT_KSEG, ngptot, nproma, ds.klev)
         # the step of cloudsc_gpu_run needs the ten members this set does not have
         assert lib.cloudsc_gpu_run(0, None, ca.FP64, ca.VARIANT_KSEG, ngptot, nproma, ds.klev, C.byref(df.f),
                                    ws) == ca.EINVAL
@@ -334,12 +163,9 @@ def test_fields_alloc_outputs_all_is_fields_alloc(lib, hip, ds, oracle_mod):
         df = ca.DeviceFields.__new__(ca.DeviceFields)      # the upload / download helpers on this set
         df.lib, df.hip, df.f, df.tend_planes = lib, hip, f, 0
         df.ngptot, df.nproma, df.klev, df.precision, df.device = ngptot, nproma, ds.klev, ca.FP64, 0
-        df.upload(host_inputs(ds, ngptot, nproma, ca.FP64))
-        p = ca.Params.from_dict(ds.params)
-        ca.check(lib.cloudsc_gpu_init(0, C.byref(p)))
-        nbytes = lib.cloudsc_gpu_scratch_bytes(ca.FP64, ca.VARIANT_KSEG, ngptot, nproma, ds.klev)
-        assert hip.hipMalloc(C.byref(ws), C.c_size_t(nbytes)) == 0
-        assert hip.hipMemset(ws, 0, C.c_size_t(256)) == 0
+        df.upload(host_inputs(ds, ngptot, nproma, ca.FP64, PATTERN))
+        init_params(lib, ds.params)
+        ws = kseg_workspace(lib, hip, ca.FP64, ca.VARIANT_KSEG, ngptot, nproma, ds.klev)
         ca.check(lib.cloudsc_gpu_run(0, None, ca.FP64, ca.VARIANT_KSEG, ngptot, nproma, ds.klev, C.byref(f), ws))
         assert lib.cloudsc_gpu_check(0, None, ca.VARIANT_KSEG, ws) == 0
         oracle = oracle_columns(oracle_mod, ds, "ds", ngptot, nproma)

@@ -13,26 +13,20 @@ import pytest
 import cloudsc_amd as ca
 import form_state_cases as fs
 import tendbuf_cases as tb
-import test_outputs_gpu as og
+from gpu_harness import ALL21, CASES, DIAG, DeviceProblem, PATTERN, PRECISIONS, VARIANTS
+from gpu_harness import columns, host_inputs, oracle_columns, raw_bits as bits
+from gpu_harness import lib, hip, restore_knobs  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
 SURF = ca.OUTPUTS_SURFACE
-DIAG = ca.DIAGNOSTIC_FLUX_FIELDS
 SFLUX = ca.SURFACE_FLUX_FIELDS
 KEPT = ca.selected_outputs(SURF)
 FULL7 = tuple(n for n in KEPT if n not in SFLUX)
-PATTERN = og.PATTERN
 GUARD = 64
-PRECISIONS, VARIANTS, SHAPES, CASES = og.PRECISIONS, og.VARIANTS, og.SHAPES, og.CASES
-bits, columns = og.bits, og.columns
-
-lib = og.lib
-hip = og.hip
-restore_knobs = og.restore_knobs
 
 
-class SurfaceSets:
+class SurfaceSets(DeviceProblem):
     """One problem on the device in three sets with the same inputs and pattern-filled outputs:
       "all"      cloudsc_fields_alloc, run with cloudsc_gpu_run: the reference;
       "null"     cloudsc_fields_alloc_outputs(SURFACE): the ten diagnostic members NULL, the four surface members
@@ -42,22 +36,16 @@ class SurfaceSets:
     tend_planes: "null" and "guarded" keep their tendencies in two packed buffers each (the "all" set does not)."""
 
     def __init__(self, lib, hip, ds, ngptot, nproma, precision, tend_planes=0, place=False):
-        self.lib, self.hip, self.ds = lib, hip, ds
-        self.ngptot, self.nproma, self.precision, self.tend_planes = ngptot, nproma, precision, tend_planes
-        self.nb, self.dt = ca.nblocks_of(ngptot, nproma), ca.storage_dtype(precision)
-        self.aer = bool(ds.params.get("laericesed") or ds.params.get("laericeauto"))
-        self.host = og.host_inputs(ds, ngptot, nproma, precision)
-        self.ws = C.c_void_p()
-        self.own = []                                   # device buffers of this test's own
+        super().__init__(lib, hip, ds, ngptot, nproma, precision)
+        self.tend_planes = tend_planes
+        self.host = host_inputs(ds, ngptot, nproma, precision, PATTERN)
         small = np.empty((self.nb, nproma), dtype=self.dt)
         bits(small)[...] = PATTERN
         surf_host = {n: (small if n in SFLUX else a) for n, a in self.host.items()}
         self.sets = {
-            "all": ca.DeviceFields(ngptot, nproma, ds.klev, precision, place=False, aerosols=self.aer),
-            "null": ca.DeviceFields(ngptot, nproma, ds.klev, precision, place=place, aerosols=self.aer, outputs=SURF,
-                                    tend_planes=tend_planes),
-            "guarded": ca.DeviceFields(ngptot, nproma, ds.klev, precision, place=False, aerosols=self.aer,
-                                       tend_planes=tend_planes),
+            "all": self.device_fields(),
+            "null": self.device_fields(place=place, outputs=SURF, tend_planes=tend_planes),
+            "guarded": self.device_fields(tend_planes=tend_planes),
         }
         self.sets["all"].upload(self.host)
         self.upload(self.sets["null"], surf_host)
@@ -67,8 +55,6 @@ class SurfaceSets:
         self.guarded = {n: self.device_array(np.full(self.nb * nproma + GUARD, 0, dtype=self.dt), PATTERN) for n in SFLUX}
         for n in SFLUX:
             setattr(self.sets["guarded"].f, n, self.guarded[n])
-        p = ca.Params.from_dict(ds.params)
-        ca.check(lib.cloudsc_gpu_init(0, C.byref(p)))
 
     def upload(self, dset, host):
         """The host arrays into a set; a tend_planes set: its separate arrays, then tendency_tmp_* packed into
@@ -89,44 +75,10 @@ class SurfaceSets:
                                   dset.tend_planes)
         self.hip.hipDeviceSynchronize()
 
-    def device_array(self, a, pattern=None):
-        a = np.ascontiguousarray(a)
-        if pattern is not None:
-            bits(a)[...] = pattern
-        p = C.c_void_p()
-        assert self.hip.hipMalloc(C.byref(p), C.c_size_t(a.nbytes)) == 0
-        self.own.append(p.value)
-        assert self.hip.hipMemcpy(p, a.ctypes.data, a.nbytes, 1) == 0
-        return p.value
-
-    def read(self, ptr, count):
-        out = np.empty(count, dtype=self.dt)
-        self.hip.hipDeviceSynchronize()
-        assert self.hip.hipMemcpy(out.ctypes.data, C.c_void_p(ptr), out.nbytes, 2) == 0
-        return out
-
-    def scratch(self, variant):
-        if variant & 0xff == ca.VARIANT_KSEG and not self.ws.value:
-            nbytes = self.lib.cloudsc_gpu_scratch_bytes(self.precision, ca.VARIANT_KSEG, self.ngptot, self.nproma,
-                                                        self.ds.klev)
-            assert nbytes > 0
-            assert self.hip.hipMalloc(C.byref(self.ws), C.c_size_t(nbytes)) == 0
-            assert self.hip.hipMemset(self.ws, 0, C.c_size_t(256)) == 0
-        return self.ws
-
     def run(self, which, variant, outputs, stream=None):
         """One step on a set (cloudsc_gpu_run for outputs None), followed by its check."""
-        ws, d = self.scratch(variant), self.sets[which]
-        if outputs is None:
-            ca.check(self.lib.cloudsc_gpu_run(0, stream, self.precision, variant, self.ngptot, self.nproma,
-                                              self.ds.klev, C.byref(d.f), ws))
-        elif d.tend_planes:
-            ca.gpu_run_tendbuf_outputs(d.f, self.precision, variant, outputs, self.ngptot, self.nproma, self.ds.klev,
-                                       d.tend_planes, scratch=ws, stream=stream)
-        else:
-            ca.gpu_run_outputs(d.f, self.precision, variant, outputs, self.ngptot, self.nproma, self.ds.klev, scratch=ws,
-                               stream=stream)
-        assert self.lib.cloudsc_gpu_check(0, stream, variant & 0xff, ws) == 0
+        d = self.sets[which]
+        self.checked_step(d.f, variant, outputs, d.tend_planes if outputs is not None else 0, stream)
 
     def surface(self, which, name):
         """A surface member of "null" / "guarded" as [nb][nproma] (raw storage type)."""
@@ -211,18 +163,11 @@ class SurfaceSets:
         return {k: v["mismatches"] for k, v in out.items() if v["mismatches"]}
 
     def close(self):
-        if self.ws.value:
-            self.hip.hipFree(self.ws)
-            self.ws = C.c_void_p()
         for n in SFLUX:                                  # the library's own arrays back before they are freed
             setattr(self.sets["guarded"].f, n, self.profile[n])
             if self.sets["guarded"].separate is not None:
                 setattr(self.sets["guarded"].separate, n, self.profile[n])
-        for s in self.sets.values():
-            s.close()
-        for p in self.own:
-            self.hip.hipFree(C.c_void_p(p))
-        self.own = []
+        super().close()
 
 
 def surface_parity(s, variant, oracle=None, stream=None, run_all=True):
@@ -247,7 +192,7 @@ def test_run_outputs_surface_bitwise(lib, hip, ds, oracle_mod, ngptot, nproma, v
             ca.narrow_pack(1)
         geo = ca.launch_geometry(PRECISIONS[precision], VARIANTS[variant], ngptot, nproma, ds.klev)
         assert geo["pack"] == (64 // nproma if nproma <= 32 else 1)
-        oracle = og.oracle_columns(oracle_mod, ds, "ds", ngptot, nproma) if precision == "fp64" else None
+        oracle = oracle_columns(oracle_mod, ds, "ds", ngptot, nproma) if precision == "fp64" else None
         surface_parity(s, VARIANTS[variant], oracle)
     finally:
         s.close()
@@ -271,7 +216,7 @@ def test_surface_with_aerosols(lib, hip, ds, oracle_mod, variant, precision):
     for ngptot, nproma in ((300, 64), (100, 16)):
         s = SurfaceSets(lib, hip, sa, ngptot, nproma, PRECISIONS[precision])
         try:
-            oracle = og.oracle_columns(oracle_mod, sa, "aerosol", ngptot, nproma) if precision == "fp64" else None
+            oracle = oracle_columns(oracle_mod, sa, "aerosol", ngptot, nproma) if precision == "fp64" else None
             surface_parity(s, VARIANTS[variant], oracle)
         finally:
             s.close()
@@ -311,7 +256,7 @@ def test_one_workspace_serves_all_three_selections(lib, hip, ds, precision):
     try:
         v = ca.VARIANT_KSEG
         s.run("all", v, None)
-        want = {k: s.sets["all"].download_raw(k).copy() for k in og.ALL21}
+        want = {k: s.sets["all"].download_raw(k).copy() for k in ALL21}
         for w in ("null", "guarded"):
             s.run(w, v, SURF)
             assert s.host_check(w) == [], w
@@ -321,7 +266,7 @@ def test_one_workspace_serves_all_three_selections(lib, hip, ds, precision):
         assert s.host_check("null") == []
         s.sets["all"].upload(s.host)
         s.run("all", v, None)
-        for k in og.ALL21:
+        for k in ALL21:
             assert np.array_equal(bits(s.sets["all"].download_raw(k)), bits(want[k])), k
     finally:
         s.close()

@@ -12,7 +12,8 @@ import pytest
 import cloudsc_amd as ca
 import form_state_cases as fs
 import spp_cases as sp
-import test_outputs_cpu as oc
+import host_harness as oc
+from host_harness import full_spp, validation_table as oc_table
 
 NAMES = fs.NAMES
 N = fs.NGPTOT
@@ -28,14 +29,11 @@ def lib():
 
 
 def columns(blocks, ngptot=N):
-    return np.ascontiguousarray(ca.blocks_to_columns(blocks, ngptot))
+    return oc.columns(blocks, ngptot)
 
 
 def oracle_step(oracle_mod):
-    def step(s):
-        st, _ = oracle_mod.run_oracle(s, N, fs.ORACLE_NPROMA)
-        return {k: columns(st.arrays[k]) for k in NAMES}
-    return step
+    return oc.oracle_step(oracle_mod, N, fs.ORACLE_NPROMA)
 
 
 _expected = {}
@@ -193,13 +191,6 @@ def test_cpu_spp_mixed_identity(ds, scenarios, name, nproma):
 # ---------------------------------------------------------------------------
 # argument rules (no launch, no GPU)
 # ---------------------------------------------------------------------------
-def full_spp(**kw):
-    s = ca.Spp()
-    for i, n in enumerate(sp.SLOTS):
-        setattr(s, n, kw.get(n, 0x900000 + 0x100 * i))
-    return s
-
-
 def test_cpu_run_spp_rules(lib, ds):
     f = oc.full_fields()
     p = ca.Params.from_dict(ds.params)
@@ -229,36 +220,7 @@ def test_cpu_run_spp_rules(lib, ds):
 
 
 def test_gpu_run_spp_rules_need_no_gpu(lib):
-    f = oc.full_fields()
-    ws = C.c_void_p(0x10)
-
-    def run(prec=ca.FP64, variant=ca.VARIANT_KSEG, outputs=ca.OUTPUTS_PROGNOSTIC, ngptot=100, nproma=16, klev=oc.KLEV,
-            fields=f, spp=full_spp(), scratch=ws):
-        return lib.cloudsc_gpu_run_spp(0, None, prec, variant, outputs, ngptot, nproma, klev,
-                                       C.byref(fields) if fields is not None else None,
-                                       C.byref(spp) if spp is not None else None, scratch)
-    before = lib.cloudsc_last_hip_error()
-    for outputs in (ca.OUTPUTS_ALL, ca.OUTPUTS_PROGNOSTIC):
-        assert run(outputs=outputs, spp=None) == ca.EINVAL
-        assert run(outputs=outputs, spp=full_spp(**{n: None for n in sp.SLOTS})) == ca.EINVAL
-        assert run(outputs=outputs, spp=full_spp(rclcrit=f.plsm)) == ca.EINVAL
-        for variant in (ca.VARIANT_SCC, ca.VARIANT_SCC_PRIVATE, 77, ca.VARIANT_KSEG | 0x1000,
-                        ca.VARIANT_KSEG | ca.FP32_EXACT_LIBM, ca.VARIANT_KCACHE | ca.FP32_EXACT_LIBM):
-            assert run(outputs=outputs, variant=variant) == ca.EINVAL
-            assert run(outputs=outputs, prec=ca.FP32, variant=variant) == ca.EINVAL
-        assert run(outputs=outputs, prec=99) == ca.EINVAL
-        assert run(outputs=outputs, ngptot=0) == ca.EINVAL
-        assert run(outputs=outputs, nproma=0) == ca.EINVAL
-        assert run(outputs=outputs, klev=1) == ca.EINVAL
-        assert run(outputs=outputs, variant=ca.VARIANT_KCACHE, nproma=257) == ca.EINVAL
-        assert run(outputs=outputs, fields=None) == ca.EINVAL
-        assert run(outputs=outputs, scratch=None) == ca.EINVAL
-        assert run(outputs=outputs, fields=oc.full_fields(without=("pt",))) == ca.EINVAL
-    assert run(outputs=ca.OUTPUTS_SURFACE) == ca.EINVAL
-    for outputs in (2, -1, 99):
-        assert run(outputs=outputs) == ca.EINVAL
-    assert run(outputs=ca.OUTPUTS_ALL, fields=oc.full_fields(without=("pfsqlf",))) == ca.EINVAL
-    assert lib.cloudsc_last_hip_error() == before
+    oc.gpu_run_spp_rules(lib)
 
 
 # ---------------------------------------------------------------------------
@@ -284,9 +246,3 @@ def test_cli_spp_refuses_what_the_form_does_not_have():
         assert r.returncode != 0 and "VALIDATION" not in r.stdout, extra
     r = subprocess.run([exe, "1", "100", "16", "--spp", "half"], capture_output=True, text=True, timeout=120)
     assert r.returncode != 0
-
-
-def oc_table(out):
-    lines = out.splitlines()
-    start = [i for i, ln in enumerate(lines) if "Variable" in ln and "MaxRelErr" in ln][0]
-    return lines[start:]

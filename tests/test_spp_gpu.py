@@ -12,85 +12,34 @@ import pytest
 
 import cloudsc_amd as ca
 import form_state_cases as fs
+import host_harness as hh
 import spp_cases as sp
-import test_outputs_gpu as og
-import test_spp_cpu as tsc
+from gpu_harness import DIAG, DeviceProblem, KEPT, PATTERN, PRECISIONS, VARIANTS, columns, differing, host_inputs
+from gpu_harness import lib, hip, restore_knobs  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
 ALL, PROG = ca.OUTPUTS_ALL, ca.OUTPUTS_PROGNOSTIC
 NAMES = fs.NAMES
-DIAG, KEPT = og.DIAG, og.KEPT
-PRECISIONS, VARIANTS = og.PRECISIONS, og.VARIANTS
-PATTERN = og.PATTERN
 
 
-@pytest.fixture(scope="module")
-def lib():
-    lib = ca.gpu_lib()
-    assert ca.device_count() > 0
-    return lib
-
-
-@pytest.fixture(scope="module")
-def hip():
-    h = ca._hip()
-    h.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
-    return h
-
-
-@pytest.fixture(autouse=True)
-def restore_knobs():
-    yield
-    ca.narrow_pack(-1)
-    ca.kseg_schedule(0, 0)
-
-
-def columns(blocks, ngptot):
-    return np.ascontiguousarray(ca.blocks_to_columns(blocks, ngptot))
-
-
-class Dev:
+class Dev(DeviceProblem):
     """One problem on the device: a field set with all 21 outputs allocated and pattern-filled, the five
     multiplier fields, the KSEG workspace; the device's default parameter set is the state's."""
 
     def __init__(self, lib, hip, s, ngptot, nproma, precision, mult):
-        self.lib, self.hip, self.s = lib, hip, s
-        self.ngptot, self.nproma, self.precision = ngptot, nproma, precision
-        self.aer = fs.uses_aerosols(s)
-        self.host = og.host_inputs(s, ngptot, nproma, precision)
-        self.df = ca.DeviceFields(ngptot, nproma, s.klev, precision, place=False, aerosols=self.aer)
-        self.ws = C.c_void_p()
-        self.mult, self.dmult = mult, {}
-        for k, a in mult.items():
-            p = C.c_void_p()
-            assert hip.hipMalloc(C.byref(p), C.c_size_t(a.nbytes)) == 0
-            assert hip.hipMemcpy(p, a.ctypes.data, a.nbytes, 1) == 0
-            self.dmult[k] = p
-        self.spp = ca.Spp(*[self.dmult[k].value if k in self.dmult else None for k in sp.SLOTS])
-        self.init_params(s.params)
-
-    def init_params(self, params):
-        p = ca.Params.from_dict(params)
-        ca.check(self.lib.cloudsc_gpu_init(0, C.byref(p)))
-
-    def scratch(self, variant):
-        if variant == ca.VARIANT_KSEG and not self.ws.value:
-            n = self.lib.cloudsc_gpu_scratch_bytes(self.precision, variant, self.ngptot, self.nproma, self.s.klev)
-            assert n > 0 and self.hip.hipMalloc(C.byref(self.ws), C.c_size_t(n)) == 0
-            assert self.hip.hipMemset(self.ws, 0, C.c_size_t(256)) == 0
-        return self.ws
+        super().__init__(lib, hip, s, ngptot, nproma, precision)
+        self.s = s
+        self.host = host_inputs(s, ngptot, nproma, precision, PATTERN)
+        self.df = self.device_fields()
+        self.mult = mult
+        self.dmult = {k: self.device_array(a) for k, a in mult.items()}
+        self.spp = ca.Spp(*[self.dmult.get(k) for k in sp.SLOTS])
 
     def step(self, variant, outputs, spp):
         """One step on freshly uploaded inputs and pattern-filled outputs; {name: block-layout array}."""
         self.df.upload(self.host)
-        ws = self.scratch(variant)
-        k = self.s.klev
-        if spp:
-            ca.gpu_run_spp(self.df.f, self.spp, self.precision, variant, outputs, self.ngptot, self.nproma, k, scratch=ws)
-        else:
-            ca.gpu_run_outputs(self.df.f, self.precision, variant, outputs, self.ngptot, self.nproma, k, scratch=ws)
-        assert self.lib.cloudsc_gpu_check(0, None, variant, ws) == 0
+        self.checked_step(self.df.f, variant, outputs, spp=self.spp if spp else None)
         return {n: self.df.download_raw(n) for n in NAMES}
 
     def plain_per_tuple(self, variant, outputs, names):
@@ -110,9 +59,7 @@ class Dev:
         """What a step must leave alone; the list of what is wrong."""
         wrong = []
         for k, a in self.mult.items():
-            got = np.empty_like(a)
-            assert self.hip.hipMemcpy(got.ctypes.data, self.dmult[k], a.nbytes, 2) == 0
-            if not np.array_equal(sp.bits(got), sp.bits(a)):
+            if not np.array_equal(sp.bits(self.read(self.dmult[k], a)), sp.bits(a)):
                 wrong.append("multiplier %s changed" % k)
         for n in list(ca.INPUT_FIELDS) + (list(ca.AEROSOL_FIELDS) if self.aer else []):
             if n in self.host and getattr(self.df.f, n) and not np.array_equal(sp.bits(self.df.download_raw(n)), sp.bits(self.host[n])):
@@ -125,16 +72,9 @@ class Dev:
             wrong += ["%s: written by a PROGNOSTIC run" % n for n in DIAG if not (sp.bits(out[n]) == PATTERN).all()]
         return wrong
 
-    def close(self):
-        for p in list(self.dmult.values()) + [self.ws]:
-            if p.value:
-                self.hip.hipFree(p)
-        self.dmult, self.ws = {}, C.c_void_p()
-        self.df.close()
-
 
 def same(a, b, names, ngptot):
-    return [n for n in names if not np.array_equal(sp.bits(columns(a[n], ngptot)), sp.bits(columns(b[n], ngptot)))]
+    return differing({n: columns(a[n], ngptot) for n in names}, {n: columns(b[n], ngptot) for n in names}, names)
 
 
 # ---------------------------------------------------------------------------
@@ -169,10 +109,7 @@ _oracle = {}
 
 def oracle_expected(oracle_mod, name, s, ngptot):
     if (name, ngptot) not in _oracle:
-        def step(x):
-            st, _ = oracle_mod.run_oracle(x, ngptot, fs.ORACLE_NPROMA)
-            return {k: columns(st.arrays[k], ngptot) for k in NAMES}
-        e = sp.expected_mixed_tuples(step, s, ngptot, ca.FP64, NAMES)
+        e = sp.expected_mixed_tuples(hh.oracle_step(oracle_mod, ngptot, fs.ORACLE_NPROMA), s, ngptot, ca.FP64, NAMES)
         for a in e.values():
             a.setflags(write=False)
         _oracle[(name, ngptot)] = e
@@ -239,7 +176,7 @@ def test_one_kseg_workspace_for_both_forms(lib, hip, ds, scenarios, oracle_mod):
         assert same(first, last, NAMES, 100) == []
         want = oracle_expected(oracle_mod, "M", s, 100)
         assert [k for k in KEPT if not np.array_equal(sp.bits(columns(mid[k], 100)), sp.bits(want[k]))] == []
-        plain = tsc.oracle_step(oracle_mod)(s)
+        plain = hh.oracle_step(oracle_mod, 100, fs.ORACLE_NPROMA)(s)
         assert [k for k in NAMES if not np.array_equal(sp.bits(columns(first[k], 100)), sp.bits(plain[k]))] == []
     finally:
         d.close()
@@ -249,7 +186,7 @@ def test_one_kseg_workspace_for_both_forms(lib, hip, ds, scenarios, oracle_mod):
 # argument rules, the CLI
 # ---------------------------------------------------------------------------
 def test_argument_rules_on_the_device(lib, hip, ds):
-    tsc.test_gpu_run_spp_rules_need_no_gpu(lib)
+    hh.gpu_run_spp_rules(lib)
     d = Dev(lib, hip, ds, 100, 64, ca.FP32, sp.uniform_fields(100, 64, ca.FP32, sp.TUPLES[1]))
     try:
         ws = d.scratch(ca.VARIANT_KSEG)
@@ -280,5 +217,5 @@ def test_cli_spp_unit(extra):
     plain = subprocess.run(base, capture_output=True, text=True, timeout=120)
     spp = subprocess.run(base + ["--spp", "unit"], capture_output=True, text=True, timeout=120)
     assert plain.returncode == 0 and spp.returncode == 0, plain.stderr + spp.stderr
-    a, b = tsc.oc_table(spp.stdout), tsc.oc_table(plain.stdout)
+    a, b = hh.validation_table(spp.stdout), hh.validation_table(plain.stdout)
     assert a == b and len(a) == 1 + (11 if extra else 21) + 1

@@ -14,13 +14,10 @@ import cloudsc_amd as ca
 import form_state_cases as fs
 import tendbuf_cases as tb
 import tendbuf_cml_cases as cm
-import test_outputs_cpu as oc
-import test_tendbuf_cpu as tc
+import host_harness as oc
+from host_harness import CANARY, KEPT_OTHER, KLEV, host_set
 
-KLEV = 137
 PROG, SURF, ALL = ca.OUTPUTS_PROGNOSTIC, ca.OUTPUTS_SURFACE, ca.OUTPUTS_ALL
-KEPT_OTHER = ("plude", "pcovptot", "prainfrac_toprfz", "pfplsl", "pfplsn", "pfhpsl", "pfhpsn")
-CANARY = 0xC3
 
 
 @pytest.fixture(scope="module")
@@ -161,32 +158,6 @@ def test_accumulate_rules_need_no_gpu(lib, device_form):
 # ---------------------------------------------------------------------------
 # the host fused form
 # ---------------------------------------------------------------------------
-def host_set(s, ngptot, nproma, precision, tend_planes, order, outputs, loc):
-    """The host state of one fused run: BUFFER_TMP filled, the separate tendency arrays and the diagnostic
-    fluxes out of reach, tendency_loc_* NULL (loc "null") or bound to a canary-filled BUFFER_LOC ("canary");
-    with SURFACE the four flux members are surface fields.  Returns (state, fields, buf_tmp, buf_loc)."""
-    st = ca.make_host_state(s, ngptot, nproma, precision)
-    nb, dt = ca.nblocks_of(ngptot, nproma), ca.storage_dtype(precision)
-    lay = tb.layout(order, tend_planes)
-    buf_tmp = tb.empty_buffer(nb, tend_planes, s.klev, nproma, dt, tb.SENTINEL_TMP)
-    buf_loc = tb.empty_buffer(nb, tend_planes, s.klev, nproma, dt, CANARY)
-    for n in tb.TMP:
-        tb.put(buf_tmp, lay[n], st.arrays[n], ngptot)
-    for n in tb.TMP + tb.LOC + tuple(oc.DIAG):
-        st.arrays[n].view(np.uint8)[...] = oc.SENTINEL
-    if outputs == SURF:
-        for n in ca.SURFACE_FLUX_FIELDS:
-            st.arrays[n] = np.full((nb, nproma), np.nan, dtype=dt)
-    f = st.fields()
-    tb.bind(f, lay, buf_tmp, buf_loc)
-    for n in oc.DIAG:
-        setattr(f, n, None)
-    if loc == "null":
-        for n in tb.LOC:
-            setattr(f, n, None)
-    return st, f, buf_tmp, buf_loc
-
-
 def fused_host(s, ngptot, nproma, precision, tend_planes, order, outputs, loc, seed, key, cml_before=None):
     """cloudsc_cpu_run_tendbuf_cml on the state; checks everything that does not depend on the sums: the
     inputs, BUFFER_LOC, the separate arrays and the diagnostic members keep every byte, the other kept
@@ -205,9 +176,9 @@ def fused_host(s, ngptot, nproma, precision, tend_planes, order, outputs, loc, s
         assert (oc.bits(st.arrays[n]) == oc.SENTINEL).all(), n
     keep = ~cm.touched_mask(buf.shape, lay, ngptot)                           # vapour, other planes, padding lanes
     assert np.array_equal(tb.bits(buf)[keep], tb.bits(before)[keep])
-    ref = tc.plain_run(s, ngptot, nproma, precision, key)
+    ref = oc.plain_run(s, key, ngptot, nproma, precision)
     for n in KEPT_OTHER:
-        got, want = tc.columns(st.arrays[n], ngptot), tc.columns(ref[n], ngptot)
+        got, want = oc.columns(st.arrays[n], ngptot), oc.columns(ref[n], ngptot)
         if outputs == SURF and n in ca.SURFACE_FLUX_FIELDS:
             want = want[s.klev]                                               # the surface row of the profile
         assert cm.same_bits(got, want), n
@@ -221,7 +192,7 @@ SETTINGS = [(8, "reference", PROG, "null"), (11, "permuted", SURF, "canary"), (1
 @pytest.mark.parametrize("ngptot,nproma", SHAPES)
 def test_cpu_fused_fp64_is_numpy_add_of_loc(ds, ngptot, nproma):
     for i, (planes, order, outputs, loc) in enumerate(SETTINGS):
-        want_loc = tc.run_tendbuf_checked(ds, ngptot, nproma, ca.FP64, planes, order)
+        want_loc = oc.run_tendbuf_checked(ds, ngptot, nproma, ca.FP64, planes, order)
         before, after, lay = fused_host(ds, ngptot, nproma, ca.FP64, planes, order, outputs, loc, 7 + i, "ds")
         exp = cm.expected(before, lay, ngptot, want_loc, cm.add_storage)
         assert cm.same_bits(after, exp), (planes, order)
@@ -238,7 +209,7 @@ def test_cpu_fused_fp64_on_state(ds, scenarios, name):
     n = fs.NGPTOT
     for nproma, planes, order, outputs in ((64, 11, "permuted", PROG), (16, 8, "reference", SURF)):
         key = "forms:" + name
-        want_loc = tc.run_tendbuf_checked(s, n, nproma, ca.FP64, planes, order, key)
+        want_loc = oc.run_tendbuf_checked(s, n, nproma, ca.FP64, planes, order, key)
         zero = cm.make_buffer(ca.nblocks_of(n, nproma), planes, s.klev, nproma, np.float64,
                               cm.layout(order, planes), n, 0, zero=True)
         for seed, start in ((3, None), (0, zero)):
@@ -281,7 +252,7 @@ def test_cpu_fused_mixed_identity(ds, scenarios, name, ngptot, nproma):
                            s.klev, planes, nthreads=3)
     assert np.array_equal(tb.bits(after32)[m], tb.bits(buf64.astype(np.float32))[m])
     # and it is not the separate pass's rule: adding the narrowed float differs somewhere
-    loc32 = tc.run_tendbuf_checked(s, ngptot, nproma, ca.MIXED, planes, order, key)
+    loc32 = oc.run_tendbuf_checked(s, ngptot, nproma, ca.MIXED, planes, order, key)
     unfused = cm.expected(before32, lay, ngptot, loc32, cm.add_storage)
     assert not cm.same_bits(after32, unfused)
 
@@ -337,7 +308,7 @@ def expected_sides(bufs, lay, ngptot, loc):
 def test_cpu_accumulate_against_numpy(ds, precision, lpl, cpl):
     ngptot, nproma = 300, 64
     dt = ca.storage_dtype(precision)
-    loc = tc.run_tendbuf_checked(ds, ngptot, nproma, ca.FP64, 8, "reference")       # any real tendencies
+    loc = oc.run_tendbuf_checked(ds, ngptot, nproma, ca.FP64, 8, "reference")       # any real tendencies
     loc = {n: np.asarray(loc[n]).astype(dt) for n in tb.LOC}
     f, keep = loc_side(loc, ngptot, nproma, ds.klev, dt, lpl)
     c, bufs, lay = cml_side(ngptot, nproma, ds.klev, dt, cpl, 21)
@@ -358,7 +329,7 @@ def test_cpu_accumulate_against_numpy(ds, precision, lpl, cpl):
 def test_cpu_fused_fp64_is_step_plus_pass(ds, ngptot, nproma):
     planes, order = 11, "permuted"
     before, fused, lay = fused_host(ds, ngptot, nproma, ca.FP64, planes, order, PROG, "null", 5, "ds")
-    loc = tc.run_tendbuf_checked(ds, ngptot, nproma, ca.FP64, planes, order)
+    loc = oc.run_tendbuf_checked(ds, ngptot, nproma, ca.FP64, planes, order)
     f, keep = loc_side(loc, ngptot, nproma, ds.klev, np.float64, planes)
     two = before.copy()
     ca.cpu_accumulate_tendbuf(f, cm.bind(lay, two), ca.FP64, ngptot, nproma, ds.klev, planes, planes, nthreads=2)

@@ -13,45 +13,21 @@ import pytest
 
 import cloudsc_amd as ca
 import form_state_cases as fs
+import host_harness as hh
 import tendbuf_cases as tb
 import tendbuf_cml_cases as cm
-import test_outputs_cpu as oc
-import test_tendbuf_cml_cpu as tcc
-import test_tendbuf_cpu as tc
-import test_tendbuf_gpu as tg
-from test_tendbuf_gpu import Pair
+from gpu_harness import DIAG, PATTERN, PRECISIONS, Pair, VARIANTS, columns, raw_bits, validation_table
+from gpu_harness import lib, hip, restore_knobs  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
 PROG, SURF, ALL = ca.OUTPUTS_PROGNOSTIC, ca.OUTPUTS_SURFACE, ca.OUTPUTS_ALL
-KEPT_OTHER = tcc.KEPT_OTHER
-VARIANTS = tg.VARIANTS
-CANARY = tcc.CANARY
-
-
-@pytest.fixture(scope="module")
-def lib():
-    lib = ca.gpu_lib()
-    assert ca.device_count() > 0
-    return lib
-
-
-@pytest.fixture(scope="module")
-def hip():
-    h = ca._hip()
-    h.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
-    return h
-
-
-@pytest.fixture(autouse=True)
-def restore_knobs():
-    yield
-    ca.narrow_pack(-1)
-    ca.kseg_schedule(0, 0)
+KEPT_OTHER = hh.KEPT_OTHER
+CANARY = hh.CANARY
 
 
 class CmlPair(Pair):
-    """tg.Pair whose packed set also has a third device buffer, BUFFER_CML.  Only the packed set is used:
+    """Pair whose packed set also has a third device buffer, BUFFER_CML.  Only the packed set is used:
     cloudsc_gpu_run_tendbuf on it gives the device's local tendencies, the fused form runs on the same
     inputs."""
 
@@ -63,37 +39,21 @@ class CmlPair(Pair):
                 tb.put(self.buf_tmp, self.lay[n], self.host[n], ngptot)
         self.buf_loc.view(np.uint8)[...] = CANARY
         self.clay = cm.layout(order, tend_planes)
-        self.cml0 = cm.make_buffer(self.nb, tend_planes, ds.klev, nproma, ca.storage_dtype(precision), self.clay,
-                                   ngptot, seed)
-        self.dev_cml = C.c_void_p()
-        assert hip.hipMalloc(C.byref(self.dev_cml), C.c_size_t(self.cml0.nbytes)) == 0
+        self.cml0 = cm.make_buffer(self.nb, tend_planes, ds.klev, nproma, self.dt, self.clay, ngptot, seed)
+        self.dev_cml = C.c_void_p(self.device_array(np.empty_like(self.cml0)))
         plane = ds.klev * nproma * self.cml0.itemsize
         self.cml = ca.TendCml(*[self.dev_cml.value + self.clay[k] * plane for k in cm.CML])
         self.surf = {}
-
-    def close(self):
-        for p in [self.dev_cml] + list(self.surf.values()):
-            if p.value:
-                self.hip.hipFree(p)
-        self.dev_cml = C.c_void_p()
-        self.surf = {}
-        super().close()
 
     def put_cml(self, host_buf=None):
         b = self.cml0 if host_buf is None else host_buf
         assert self.hip.hipMemcpy(self.dev_cml, b.ctypes.data, b.nbytes, 1) == 0
 
-    def get(self, dev, like):
-        self.hip.hipDeviceSynchronize()
-        out = np.empty_like(like)
-        assert self.hip.hipMemcpy(out.ctypes.data, dev, out.nbytes, 2) == 0
-        return out
-
     def device_loc(self, variant):
         """{tendency_loc_*: block-layout array} and the other kept outputs of cloudsc_gpu_run_tendbuf."""
         self.fill(("packed",))
         self.run_both(variant, which=("packed",))
-        loc = self.get(self.packed.buffer_loc, self.buf_loc)
+        loc = self.read(self.packed.buffer_loc, self.buf_loc)
         out = {n: tb.take(loc, self.lay[n], n) for n in tb.LOC}
         out.update({n: self.packed.download_raw(n) for n in KEPT_OTHER})
         return out
@@ -101,30 +61,26 @@ class CmlPair(Pair):
     def fused_fields(self, outputs, loc):
         f = ca.Fields()
         C.memmove(C.byref(f), C.byref(self.packed.f), C.sizeof(ca.Fields))
-        for n in oc.DIAG:
+        for n in DIAG:
             setattr(f, n, None)
         if loc == "null":
             for n in tb.LOC:
                 setattr(f, n, None)
         if outputs == SURF:
             for n in ca.SURFACE_FLUX_FIELDS:
+                small = np.empty((self.nb, self.nproma), dtype=self.dt)
                 if n not in self.surf:
-                    p = C.c_void_p()
-                    assert self.hip.hipMalloc(C.byref(p), C.c_size_t(self.nb * self.nproma * self.cml0.itemsize)) == 0
-                    self.surf[n] = p
-                assert self.hip.hipMemset(self.surf[n], tg.PATTERN, C.c_size_t(self.nb * self.nproma * self.cml0.itemsize)) == 0
-                setattr(f, n, self.surf[n].value)
+                    self.surf[n] = self.device_array(small)
+                assert self.hip.hipMemset(self.surf[n], PATTERN, C.c_size_t(small.nbytes)) == 0
+                setattr(f, n, self.surf[n])
         return f
 
     def run_fused(self, variant, outputs=PROG, loc="null", refill=True):
         if refill:                      # plude is INOUT; BUFFER_LOC gets its canary back
             self.fill(("packed",))
         f = self.fused_fields(outputs, loc)
-        ws = self.scratch(variant)
-        ca.gpu_run_tendbuf_cml(f, self.cml, self.precision, variant, outputs, self.ngptot, self.nproma, self.ds.klev,
-                               self.tend_planes, scratch=ws)
-        assert self.lib.cloudsc_gpu_check(0, None, variant & 0xff, ws) == 0
-        return self.get(self.dev_cml, self.cml0)
+        self.checked_step(f, variant, outputs, self.tend_planes, cml=self.cml)
+        return self.read(self.dev_cml, self.cml0)
 
     def check_untouched(self, after, before, ref, outputs):
         """What does not depend on the sums; returns the list of what is wrong."""
@@ -132,23 +88,23 @@ class CmlPair(Pair):
         keep = ~cm.touched_mask(before.shape, self.clay, self.ngptot)
         if not np.array_equal(tb.bits(after)[keep], tb.bits(before)[keep]):
             wrong.append("BUFFER_CML: the vapour plane, an unbound plane or a padding lane changed")
-        if not (oc.bits(self.get(self.packed.buffer_loc, self.buf_loc)) == CANARY).all():
+        if not (raw_bits(self.read(self.packed.buffer_loc, self.buf_loc)) == CANARY).all():
             wrong.append("BUFFER_LOC was written")
-        if not cm.same_bits(self.get(self.packed.buffer_tmp, self.buf_tmp), self.buf_tmp):
+        if not cm.same_bits(self.read(self.packed.buffer_tmp, self.buf_tmp), self.buf_tmp):
             wrong.append("BUFFER_TMP changed")
-        for n in oc.DIAG:
-            if not (oc.bits(self.packed.download_raw(n)) == tg.PATTERN).all():
+        for n in DIAG:
+            if not (raw_bits(self.packed.download_raw(n)) == PATTERN).all():
                 wrong.append("%s: a diagnostic member was written" % n)
         for n in KEPT_OTHER:
             if outputs == SURF and n in ca.SURFACE_FLUX_FIELDS:
-                got = self.get(self.surf[n], np.empty((self.nb, self.nproma), dtype=self.cml0.dtype))
+                got = self.read(self.surf[n], np.empty((self.nb, self.nproma), dtype=self.cml0.dtype))
                 want = ref[n][:, self.ds.klev, :]
-                if not cm.same_bits(tc.columns(got, self.ngptot), tc.columns(want, self.ngptot)):
+                if not cm.same_bits(columns(got, self.ngptot), columns(want, self.ngptot)):
                     wrong.append("%s: the surface row differs" % n)
                 tail = self.ngptot - (self.nb - 1) * self.nproma
-                if not (oc.bits(got[self.nb - 1, tail:]) == tg.PATTERN).all():
+                if not (raw_bits(got[self.nb - 1, tail:]) == PATTERN).all():
                     wrong.append("%s: a padding lane was written" % n)
-                if not (oc.bits(self.packed.download_raw(n)) == tg.PATTERN).all():
+                if not (raw_bits(self.packed.download_raw(n)) == PATTERN).all():
                     wrong.append("%s: the profile was written" % n)
             elif not cm.same_bits(self.packed.download_raw(n), ref[n]):
                 wrong.append("%s: differs" % n)
@@ -172,7 +128,7 @@ CASES = [
 @pytest.mark.parametrize("ngptot,nproma,variant,planes,order,outputs,loc,pack", CASES)
 def test_fused_is_device_loc_plus_host_add(lib, hip, ds, ngptot, nproma, variant, planes, order, outputs, loc, pack,
                                            precision):
-    prec = tg.PRECISIONS[precision]
+    prec = PRECISIONS[precision]
     pr = CmlPair(lib, hip, ds, ngptot, nproma, prec, planes, order, seed=ngptot + nproma)
     try:
         ca.narrow_pack(pack)
@@ -182,7 +138,7 @@ def test_fused_is_device_loc_plus_host_add(lib, hip, ds, ngptot, nproma, variant
         assert pr.check_untouched(after, pr.cml0, ref, outputs) == []
         assert cm.same_bits(after, cm.expected(pr.cml0, pr.clay, ngptot, ref, cm.add_storage))
         if prec == ca.FP64:             # and the host form on the same buffer
-            st, f, buf_tmp, buf_loc = tcc.host_set(ds, ngptot, nproma, prec, planes, order, outputs, "null")
+            st, f, buf_tmp, buf_loc = hh.host_set(ds, ngptot, nproma, prec, planes, order, outputs, "null")
             host = pr.cml0.copy()
             ca.cpu_run_tendbuf_cml(ca.Params.from_dict(ds.params), f, cm.bind(pr.clay, host), prec, outputs, ngptot,
                                    nproma, ds.klev, planes, nthreads=4)
@@ -244,12 +200,12 @@ def test_fused_mixed_identity(lib, hip, ds, ngptot, nproma, variant, outputs):
 def test_device_pass_and_fused_is_step_plus_pass(lib, hip, ds, precision, lpl, cpl):
     """cloudsc_fields_accumulate_tendbuf against NumPy on whole buffers; with both sides packed (fp64, fp32),
     the fused form equals the prognostic step followed by the pass."""
-    prec, ngptot, nproma, planes = tg.PRECISIONS[precision], 300, 64, 11
+    prec, ngptot, nproma, planes = PRECISIONS[precision], 300, 64, 11
     pr = CmlPair(lib, hip, ds, ngptot, nproma, prec, planes, "permuted", seed=13)
     extra = []
     try:
         ref = pr.device_loc(ca.VARIANT_KSEG)                       # BUFFER_LOC now holds the step's tendencies
-        loc_before = pr.get(pr.packed.buffer_loc, pr.buf_loc)
+        loc_before = pr.read(pr.packed.buffer_loc, pr.buf_loc)
         pr.put_cml()
         loc = ca.fields_subset(pr.packed.f, tb.LOC)
         dt = pr.cml0.dtype
@@ -263,10 +219,10 @@ def test_device_pass_and_fused_is_step_plus_pass(lib, hip, ds, precision, lpl, c
                 setattr(loc, n, p.value)
         if cpl:
             ca.accumulate_tendbuf(loc, pr.cml, prec, ngptot, nproma, ds.klev, lpl, cpl)
-            got = pr.get(pr.dev_cml, pr.cml0)
+            got = pr.read(pr.dev_cml, pr.cml0)
             want = cm.expected(pr.cml0, pr.clay, ngptot, ref, cm.add_storage)
             assert cm.same_bits(got, want)
-            assert cm.same_bits(pr.get(pr.packed.buffer_loc, pr.buf_loc), loc_before)      # the source is only read
+            assert cm.same_bits(pr.read(pr.packed.buffer_loc, pr.buf_loc), loc_before)      # the source is only read
             if lpl and prec != ca.MIXED:
                 pr.put_cml()
                 fused = pr.run_fused(ca.VARIANT_KSEG, PROG, "null")
@@ -285,8 +241,8 @@ def test_device_pass_and_fused_is_step_plus_pass(lib, hip, ds, precision, lpl, c
             ca.accumulate_tendbuf(loc, c, prec, ngptot, nproma, ds.klev, lpl, 0)
             for k, h, p in hosts:
                 want = cm.expected(h, {j: (0 if j == k else 99) for j in cm.CML}, ngptot, ref, cm.add_storage)
-                assert cm.same_bits(pr.get(p, h), want), k
-            assert cm.same_bits(pr.get(pr.packed.buffer_loc, pr.buf_loc), loc_before)
+                assert cm.same_bits(pr.read(p, h), want), k
+            assert cm.same_bits(pr.read(pr.packed.buffer_loc, pr.buf_loc), loc_before)
     finally:
         for p in extra:
             hip.hipFree(p)
@@ -311,7 +267,7 @@ def test_kseg_forced_handoffs_and_two_launches(lib, hip, ds):
 
 @pytest.mark.parametrize("precision", ["fp64", "fp32"])
 def test_one_kseg_workspace_for_every_form(lib, hip, ds, precision):
-    prec = tg.PRECISIONS[precision]
+    prec = PRECISIONS[precision]
     pr = CmlPair(lib, hip, ds, 300, 64, prec, 11, "permuted", seed=4)
     try:
         ref = pr.device_loc(ca.VARIANT_KSEG)                        # ALL (cloudsc_gpu_run_tendbuf) on the workspace
@@ -342,7 +298,7 @@ def test_python_helper_round_trip(lib, hip, ds):
         f, c = ca.bind_tendbuf_three(f, ca.FP64, 16, ds.klev, pr.packed.buffer_tmp, pr.dev_cml.value)
         assert f.tendency_loc_t is None and (c.t, c.q, c.a, c.cld) == (pr.cml.t, pr.cml.q, pr.cml.a, pr.cml.cld)
         ca.gpu_run_tendbuf_cml(f, c, ca.FP64, ca.VARIANT_KCACHE, PROG, 100, 16, ds.klev, 8)
-        assert cm.same_bits(pr.get(pr.dev_cml, pr.cml0), cm.expected(pr.cml0, pr.clay, 100, ref, cm.add_storage))
+        assert cm.same_bits(pr.read(pr.dev_cml, pr.cml0), cm.expected(pr.cml0, pr.clay, 100, ref, cm.add_storage))
     finally:
         pr.close()
 
@@ -354,7 +310,7 @@ def test_cli_tendbuf_cml_prints_the_inplace_rows(outputs):
     got = subprocess.run(base + ["--fields", "tendbuf-cml"], capture_output=True, text=True, timeout=120)
     want = subprocess.run(base + ["--fields", "tendbuf-inplace"], capture_output=True, text=True, timeout=120)
     assert got.returncode == 0 and want.returncode == 0, got.stderr + want.stderr
-    a, b = tg.validation_table(got.stdout), tg.validation_table(want.stdout)
+    a, b = validation_table(got.stdout), validation_table(want.stdout)
     assert a == b                                   # 0 + loc: the rows of BUFFER_LOC validated in place
     assert len([ln for ln in a if "TENDENCY_LOC" in ln]) == 4 and len(a) == 1 + 11 + 1
     assert "VALIDATION: PASSED" in a[-1]

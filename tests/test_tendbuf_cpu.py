@@ -14,9 +14,8 @@ import pytest
 import cloudsc_amd as ca
 import fields_convert_cases as fc
 import tendbuf_cases as tb
-
-NAMES = [k for _, k in ca.VALIDATED]   # the 20 outputs and plude
-KLEV = 137
+from host_harness import CONV_CASES, CONV_KLEV, CONV_NGPTOT, KLEV, NAMES, Side, columns, convert, full_fields
+from host_harness import run_tendbuf_checked, same_storage
 
 
 @pytest.fixture(scope="module")
@@ -27,14 +26,6 @@ def lib():
 # ---------------------------------------------------------------------------
 # argument rules
 # ---------------------------------------------------------------------------
-def full_fields():
-    """A Fields with every member non-NULL (never dereferenced: the calls fail first)."""
-    f = ca.Fields()
-    for i, (n, _) in enumerate(ca.Fields._fields_):
-        setattr(f, n, 0x1000 + 0x100 * i)
-    return f
-
-
 def test_bind_rules_and_planes(lib):
     f = ca.Fields()
     bad = [(None, ca.FP64, 16, 5, 64, 128), (f, 99, 16, 5, 64, 128), (f, ca.FP64, 0, 5, 64, 128),
@@ -146,25 +137,6 @@ def test_cli_fields_tendbuf_refusals(extra):
 # ---------------------------------------------------------------------------
 # cloudsc_cpu_run_tendbuf
 # ---------------------------------------------------------------------------
-_plain = {}
-
-
-def plain_run(ds, ngptot, nproma, precision, key="ds"):
-    """cloudsc_cpu_run_precision on separate arrays: {name: block-layout array}, once per case (key: a name
-    for the dataset), read-only."""
-    key = (key, ngptot, nproma, precision)
-    if key not in _plain:
-        st, _ = ca.cpu_run(ds, ngptot, nproma, nthreads=4, precision=precision)
-        for a in st.arrays.values():
-            a.setflags(write=False)
-        _plain[key] = st.arrays
-    return _plain[key]
-
-
-def columns(blocks, ngptot):
-    return np.ascontiguousarray(ca.blocks_to_columns(blocks, ngptot))
-
-
 CPU_SHAPES = list(tb.SHAPES)
 
 
@@ -180,81 +152,9 @@ def test_cpu_run_tendbuf_bitwise(ds, oracle_mod, ngptot, nproma, precision, tend
             assert np.array_equal(tb.bits(columns(got[k], ngptot)), tb.bits(columns(ost.arrays[k], ngptot))), k
 
 
-def run_tendbuf_checked(ds, ngptot, nproma, precision, tend_planes, order, key="ds"):
-    """cloudsc_cpu_run_tendbuf on the dataset (key: a name for it), checked against cloudsc_cpu_run_precision
-    and for the sentinels; returns {name: block-layout array} of the 21 fields."""
-    ref = plain_run(ds, ngptot, nproma, precision, key)
-    st = ca.make_host_state(ds, ngptot, nproma, precision)
-    nb, dt = ca.nblocks_of(ngptot, nproma), ca.storage_dtype(precision)
-    lay = tb.layout(order, tend_planes)
-    buf_tmp = tb.empty_buffer(nb, tend_planes, ds.klev, nproma, dt, tb.SENTINEL_TMP)
-    buf_loc = tb.empty_buffer(nb, tend_planes, ds.klev, nproma, dt, tb.SENTINEL_LOC)
-    for n in tb.TMP:
-        tb.put(buf_tmp, lay[n], st.arrays[n], ngptot)
-    tmp_before = buf_tmp.copy()
-    f = st.fields()
-    if order == "reference":
-        ca.bind_tendbuf(f, precision, nproma, ds.klev, buf_tmp.ctypes.data, buf_loc.ctypes.data)
-    else:
-        tb.bind(f, lay, buf_tmp, buf_loc)
-    ca.cpu_run_tendbuf(ca.Params.from_dict(ds.params), f, precision, ngptot, nproma, ds.klev, tend_planes,
-                       nthreads=3)
-    assert np.array_equal(tb.bits(buf_tmp), tb.bits(tmp_before))            # inputs are only read
-    assert tb.is_sentinel(buf_loc, tb.untouched_mask(buf_loc, lay, tb.LOC, ngptot), tb.SENTINEL_LOC)
-    got = {k: tb.take(buf_loc, lay[k], k) if k in tb.LOC else st.arrays[k] for k in NAMES}
-    bad = {}
-    for k in NAMES:
-        if not np.array_equal(tb.bits(columns(got[k], ngptot)), tb.bits(columns(ref[k], ngptot))):
-            bad[k] = "differs from cloudsc_cpu_run_precision"
-    assert bad == {}
-    return got
-
-
 # ---------------------------------------------------------------------------
 # cloudsc_cpu_fields_convert_tendbuf against NumPy
 # ---------------------------------------------------------------------------
-CONV_KLEV = 3
-CONV_NGPTOT = 150
-
-
-class Side:
-    """One side of a conversion on the host: every member in block layout of `nproma` columns, the
-    tendency members in two packed buffers when tend_planes is non-zero."""
-
-    def __init__(self, precision, nproma, tend_planes, order="reference", values=True, ngptot=CONV_NGPTOT):
-        self.precision, self.nproma, self.tend_planes, self.ngptot = precision, nproma, tend_planes, ngptot
-        self.nb = ca.nblocks_of(ngptot, nproma)
-        self.arrays, self.f = {}, ca.Fields()
-        for name in fc.MEMBERS:
-            dt = fc.dtype_of(name, precision)
-            cols = fc.encoded(name, fc.rows_of(name, CONV_KLEV), ngptot).astype(dt)
-            a = fc.to_blocks(cols, nproma, dt, fc.POISON if values else bytes([tb.SENTINEL_LOC]))
-            if not values:
-                a.view(np.uint8)[...] = tb.SENTINEL_LOC
-            self.arrays[name] = a
-            setattr(self.f, name, a.ctypes.data)
-        self.lay, self.bufs = None, None
-        if tend_planes:
-            dt = ca.storage_dtype(precision)
-            self.lay = tb.layout(order, tend_planes)
-            self.bufs = [tb.empty_buffer(self.nb, tend_planes, CONV_KLEV, nproma, dt, s)
-                         for s in (tb.SENTINEL_TMP, tb.SENTINEL_LOC)]
-            if values:
-                for names, buf in ((tb.TMP, self.bufs[0]), (tb.LOC, self.bufs[1])):
-                    for n in names:
-                        tb.put(buf, self.lay[n], self.arrays[n], ngptot)
-            tb.bind(self.f, self.lay, *self.bufs)
-
-    def member(self, name):
-        """The member as a block-layout array, wherever it lives."""
-        if self.tend_planes and name in tb.TMP + tb.LOC:
-            return tb.take(self.bufs[0] if name in tb.TMP else self.bufs[1], self.lay[name], name)
-        return self.arrays[name]
-
-    def snapshot(self):
-        return [a.copy() for a in list(self.arrays.values()) + (self.bufs or [])]
-
-
 def expected_after(src, dst):
     """dst's storage after the conversion, restated: every valid lane the cast value, the rest as before."""
     out = dst.snapshot()
@@ -272,27 +172,6 @@ def expected_after(src, dst):
                 n = min(dst.nproma, dst.ngptot - b * dst.nproma)
                 out[i][b, ..., :n] = blocks[b, ..., :n]
     return out
-
-
-def convert(src, dst):
-    ca.cpu_convert_fields_tendbuf(src.f, dst.f, src.ngptot, CONV_KLEV, src.precision, src.nproma, src.tend_planes,
-                                  dst.precision, dst.nproma, dst.tend_planes, nthreads=3)
-
-
-def same_storage(got, want):
-    return all(np.array_equal(tb.bits(g), tb.bits(w)) for g, w in zip(got, want))
-
-
-# (src precision, NPROMA, planes, order) -> (dst precision, NPROMA, planes, order)
-CONV_CASES = {
-    "pack": ((ca.FP64, 64, 0, "reference"), (ca.FP64, 64, 8, "reference")),
-    "unpack": ((ca.FP64, 64, 11, "permuted"), (ca.FP64, 64, 0, "reference")),
-    "pack_reblock_24_64": ((ca.FP64, 24, 0, "reference"), (ca.FP64, 64, 11, "permuted")),
-    "unpack_reblock_24_64": ((ca.FP32, 24, 8, "permuted"), (ca.FP32, 64, 0, "reference")),
-    "pack_narrow_fp64_float": ((ca.FP64, 64, 0, "reference"), (ca.MIXED, 64, 8, "permuted")),
-    "unpack_narrow_fp64_float": ((ca.FP64, 16, 11, "reference"), (ca.MIXED, 64, 0, "reference")),
-    "repack_8_11": ((ca.FP64, 64, 8, "reference"), (ca.FP64, 24, 11, "permuted")),
-}
 
 
 @pytest.mark.parametrize("case", sorted(CONV_CASES))

@@ -8,169 +8,16 @@ import ctypes as C
 import os
 import subprocess
 
-import numpy as np
 import pytest
 
 import cloudsc_amd as ca
-import tendbuf_cases as tb
-import test_tendbuf_cpu as tc
+import host_harness as tc
+from gpu_harness import CASES, DeviceSide, PRECISIONS, Pair, VARIANTS, validation_table
+from gpu_harness import lib, hip, restore_knobs  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
-NAMES = [k for _, k in ca.VALIDATED]
-PATTERN = 0xC3
-PRECISIONS = {"fp64": ca.FP64, "fp32": ca.FP32, "mixed": ca.MIXED}
-VARIANTS = {"kcache": ca.VARIANT_KCACHE, "kseg": ca.VARIANT_KSEG}
 SETTINGS = [(8, "reference"), (11, "permuted")]
-
-
-@pytest.fixture(scope="module")
-def lib():
-    lib = ca.gpu_lib()
-    assert ca.device_count() > 0
-    return lib
-
-
-@pytest.fixture(scope="module")
-def hip():
-    h = ca._hip()
-    h.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
-    h.hipStreamCreateWithFlags.argtypes = [C.POINTER(C.c_void_p), C.c_uint]
-    h.hipStreamSynchronize.argtypes = [C.c_void_p]
-    h.hipStreamDestroy.argtypes = [C.c_void_p]
-    return h
-
-
-@pytest.fixture(autouse=True)
-def restore_knobs():
-    yield
-    ca.narrow_pack(-1)
-    ca.kseg_schedule(0, 0)
-
-
-def host_inputs(ds, ngptot, nproma, precision):
-    """Block-layout host arrays with every output (and plude's padding lanes) set to a byte pattern."""
-    st = ca.make_host_state(ds, ngptot, nproma, precision)
-    nb = ca.nblocks_of(ngptot, nproma)
-    out = {}
-    for name, a in st.arrays.items():
-        a = np.ascontiguousarray(a).copy()
-        if name in ca.OUTPUT_FIELDS and name != "plude":
-            a.view(np.uint8)[...] = PATTERN
-        if name == "plude":
-            tail = ngptot - (nb - 1) * nproma
-            a[nb - 1, ..., tail:].view(np.uint8)[...] = PATTERN
-        out[name] = a
-    return out
-
-
-class Pair:
-    """One problem twice on the device: `plain` with separate tendency arrays, `packed` with the two
-    tendency buffers of DeviceFields(tend_planes=...)."""
-
-    def __init__(self, lib, hip, ds, ngptot, nproma, precision, tend_planes, order):
-        self.lib, self.hip, self.ds = lib, hip, ds
-        self.ngptot, self.nproma, self.precision, self.tend_planes = ngptot, nproma, precision, tend_planes
-        self.nb = ca.nblocks_of(ngptot, nproma)
-        self.aer = bool(ds.params.get("laericesed") or ds.params.get("laericeauto"))
-        self.host = host_inputs(ds, ngptot, nproma, precision)
-        self.lay = tb.layout(order, tend_planes)
-        self.plain = ca.DeviceFields(ngptot, nproma, ds.klev, precision, place=False, aerosols=self.aer)
-        self.packed = ca.DeviceFields(ngptot, nproma, ds.klev, precision, place=False, aerosols=self.aer,
-                                      tend_planes=tend_planes)
-        self.ws = C.c_void_p()
-        dt = ca.storage_dtype(precision)
-        self.buf_tmp = tb.empty_buffer(self.nb, tend_planes, ds.klev, nproma, dt, tb.SENTINEL_TMP)
-        self.buf_loc = tb.empty_buffer(self.nb, tend_planes, ds.klev, nproma, dt, tb.SENTINEL_LOC)
-        for n in tb.TMP:
-            tb.put(self.buf_tmp, self.lay[n], self.host[n], ngptot)
-        assert self.buf_tmp.nbytes == self.packed.tendbuf_nbytes()
-        if order != "reference":       # the constructor bound the reference's planes
-            plane = ds.klev * nproma * self.buf_tmp.itemsize
-            for names, base in ((tb.TMP, self.packed.buffer_tmp), (tb.LOC, self.packed.buffer_loc)):
-                for n in names:
-                    setattr(self.packed.f, n, base + self.lay[n] * plane)
-        p = ca.Params.from_dict(ds.params)
-        ca.check(lib.cloudsc_gpu_init(0, C.byref(p)))
-
-    def fill(self, which=("plain", "packed")):
-        if "plain" in which:
-            self.plain.upload(self.host)
-        if "packed" in which:
-            self.packed.upload({k: v for k, v in self.host.items() if not k.startswith("tendency_")})
-            assert self.hip.hipMemcpy(self.packed.buffer_tmp, self.buf_tmp.ctypes.data, self.buf_tmp.nbytes, 1) == 0
-            assert self.hip.hipMemcpy(self.packed.buffer_loc, self.buf_loc.ctypes.data, self.buf_loc.nbytes, 1) == 0
-
-    def scratch(self, variant):
-        if variant & 0xff == ca.VARIANT_KSEG and not self.ws.value:
-            nbytes = self.lib.cloudsc_gpu_scratch_bytes(self.precision, ca.VARIANT_KSEG, self.ngptot, self.nproma,
-                                                        self.ds.klev)
-            assert nbytes > 0
-            assert self.hip.hipMalloc(C.byref(self.ws), C.c_size_t(nbytes)) == 0
-            assert self.hip.hipMemset(self.ws, 0, C.c_size_t(256)) == 0
-        return self.ws
-
-    def run_both(self, variant, stream=None, which=("plain", "packed")):
-        """cloudsc_gpu_run on `plain`, cloudsc_gpu_run_tendbuf on `packed` (each followed by its check)."""
-        ws = self.scratch(variant)
-        k = self.ds.klev
-        if "plain" in which:
-            ca.check(self.lib.cloudsc_gpu_run(0, stream, self.precision, variant, self.ngptot, self.nproma, k,
-                                              C.byref(self.plain.f), ws))
-            assert self.lib.cloudsc_gpu_check(0, stream, variant & 0xff, ws) == 0
-        if "packed" in which:
-            ca.gpu_run_tendbuf(self.packed.f, self.precision, variant, self.ngptot, self.nproma, k, self.tend_planes,
-                               scratch=ws, stream=stream)
-            assert self.lib.cloudsc_gpu_check(0, stream, variant & 0xff, ws) == 0
-
-    def device_mismatches(self, stream=None):
-        """Unpack BUFFER_LOC into the packed set's separate arrays, then cloudsc_fields_compare of its 21
-        outputs against the plain set's: {member: mismatches} where not 0."""
-        loc_src = ca.fields_subset(self.packed.f, tb.LOC)
-        loc_dst = ca.fields_subset(self.packed.separate, tb.LOC)
-        ca.convert_fields_tendbuf(loc_src, loc_dst, self.ngptot, self.ds.klev, self.precision, self.nproma,
-                                  self.tend_planes, self.precision, self.nproma, 0, stream=stream)
-        a = ca.fields_subset(self.packed.separate, NAMES)
-        b = ca.fields_subset(self.plain.f, NAMES)
-        d = ca.compare_fields(a, b, self.ngptot, self.ds.klev, self.precision, self.nproma, self.precision,
-                              self.nproma, stream=stream)
-        assert sorted(d) == sorted(NAMES)
-        assert all(v["compared"] > 0 for v in d.values())
-        return {k: v["mismatches"] for k, v in d.items() if v["mismatches"]}
-
-    def host_check(self):
-        """The same on the host, and the sentinels: returns the list of what is wrong."""
-        self.hip.hipDeviceSynchronize()
-        loc = np.empty_like(self.buf_loc)
-        tmp = np.empty_like(self.buf_tmp)
-        assert self.hip.hipMemcpy(loc.ctypes.data, self.packed.buffer_loc, loc.nbytes, 2) == 0
-        assert self.hip.hipMemcpy(tmp.ctypes.data, self.packed.buffer_tmp, tmp.nbytes, 2) == 0
-        wrong = []
-        if not np.array_equal(tb.bits(tmp), tb.bits(self.buf_tmp)):
-            wrong.append("BUFFER_TMP changed")
-        if not tb.is_sentinel(loc, tb.untouched_mask(loc, self.lay, tb.LOC, self.ngptot), tb.SENTINEL_LOC):
-            wrong.append("BUFFER_LOC: an unbound plane or a padding lane was written")
-        for k in NAMES:
-            ref = self.plain.download_raw(k)
-            if k in tb.LOC:
-                got = tb.take(loc, self.lay[k], k)
-            else:
-                got = self.packed.download_raw(k)
-                if not np.array_equal(tb.bits(got), tb.bits(ref)):    # whole arrays: padding lanes included
-                    wrong.append("%s: differs (padding included)" % k)
-            if not np.array_equal(tb.bits(tc.columns(got, self.ngptot)), tb.bits(tc.columns(ref, self.ngptot))):
-                wrong.append("%s: differs" % k)
-        return wrong
-
-    def close(self):
-        if self.ws.value:
-            self.hip.hipFree(self.ws)
-            self.ws = C.c_void_p()
-        self.plain.close()
-        self.packed.close()
-
-
-CASES = [(n, p, v) for (n, p) in tb.SHAPES for v in VARIANTS if not (p > 256 and v == "kcache")]
 
 
 @pytest.mark.parametrize("precision", sorted(PRECISIONS))
@@ -270,12 +117,6 @@ def test_run_tendbuf_refuses_scc(lib, hip, ds):
 # ---------------------------------------------------------------------------
 # the CLI
 # ---------------------------------------------------------------------------
-def validation_table(out):
-    lines = out.splitlines()
-    start = [i for i, ln in enumerate(lines) if "Variable" in ln and "MaxRelErr" in ln][0]
-    return lines[start:]
-
-
 @pytest.mark.parametrize("common,planes", [([], []), (["--variant", "kcache", "--precision", "mixed"],
                                                      ["--tend-planes", "11"])], ids=["default", "planes11_kcache_mixed"])
 def test_cli_fields_tendbuf(common, planes):
@@ -291,44 +132,6 @@ def test_cli_fields_tendbuf(common, planes):
 # ---------------------------------------------------------------------------
 # the device conversion against the host twin
 # ---------------------------------------------------------------------------
-class DeviceSide:
-    """A tc.Side mirrored on the device: plain hipMalloc copies of every array and buffer, the Fields
-    pointing at the same places in them."""
-
-    def __init__(self, hip, side):
-        self.hip, self.side, self.f = hip, side, ca.Fields()
-        self.host = list(side.arrays.values()) + (side.bufs or [])
-        self.dev = []
-        for a in self.host:
-            p = C.c_void_p()
-            assert hip.hipMalloc(C.byref(p), C.c_size_t(a.nbytes)) == 0
-            assert hip.hipMemcpy(p, a.ctypes.data, a.nbytes, 1) == 0
-            self.dev.append(p.value)
-        for name, _ in ca.Fields._fields_:
-            hp = getattr(side.f, name)
-            if hp:
-                setattr(self.f, name, self.translate(hp))
-
-    def translate(self, host_ptr):
-        for a, d in zip(self.host, self.dev):
-            if a.ctypes.data <= host_ptr < a.ctypes.data + a.nbytes:
-                return d + (host_ptr - a.ctypes.data)
-        raise AssertionError("pointer outside every array")
-
-    def snapshot(self):
-        self.hip.hipDeviceSynchronize()
-        out = []
-        for a, d in zip(self.host, self.dev):
-            b = np.empty_like(a)
-            assert self.hip.hipMemcpy(b.ctypes.data, d, b.nbytes, 2) == 0
-            out.append(b)
-        return out
-
-    def close(self):
-        for d in self.dev:
-            self.hip.hipFree(d)
-
-
 @pytest.mark.parametrize("case", sorted(tc.CONV_CASES))
 def test_device_convert_tendbuf_against_host_twin(lib, hip, case):
     s, d = tc.CONV_CASES[case]

@@ -16,10 +16,9 @@ import fields_compare_cases as cc
 import fields_convert_cases as fc
 import form_state_cases as fs
 import tendbuf_cases as tb
-import test_outputs_cpu as oc
-import test_tendbuf_cpu as tc
+import host_harness as oc
+from host_harness import KLEV, PackedSide, cpu_compare
 
-KLEV = 137
 DIAG, KEPT = oc.DIAG, oc.KEPT
 SHAPES = list(tb.SHAPES) + [(1, 1)]
 SETTINGS = [(8, "reference"), (11, "permuted")]
@@ -246,7 +245,7 @@ def run_form(s, ngptot, nproma, precision, tend_planes, order, outputs, diag, ke
     """cloudsc_cpu_run_tendbuf_outputs on the dataset, checked for the sentinels and against
     cloudsc_cpu_run_precision on separate arrays; diag: the ten diagnostic members "null" or "sentinel".
     Returns {name: block-layout array}."""
-    ref = tc.plain_run(s, ngptot, nproma, precision, key)
+    ref = oc.plain_run(s, key, ngptot, nproma, precision)
     st = ca.make_host_state(s, ngptot, nproma, precision)
     nb, dt = ca.nblocks_of(ngptot, nproma), ca.storage_dtype(precision)
     lay = tb.layout(order, tend_planes)
@@ -279,7 +278,7 @@ def run_form(s, ngptot, nproma, precision, tend_planes, order, outputs, diag, ke
     got = {k: tb.take(buf_loc, lay[k], k) if k in tb.LOC else st.arrays[k] for k in oc.ALL21}
     names = KEPT if outputs == PROG else oc.ALL21
     assert [k for k in names
-            if not np.array_equal(tb.bits(tc.columns(got[k], ngptot)), tb.bits(tc.columns(ref[k], ngptot)))] == []
+            if not np.array_equal(tb.bits(oc.columns(got[k], ngptot)), tb.bits(oc.columns(ref[k], ngptot)))] == []
     return got
 
 
@@ -292,18 +291,18 @@ def test_cpu_run_tendbuf_outputs_prognostic(ds, oracle_mod, ngptot, nproma, prec
             if precision == ca.FP64:
                 ost, _ = oracle_mod.run_oracle(ds, ngptot, nproma)
                 for k in KEPT:
-                    assert np.array_equal(tb.bits(tc.columns(got[k], ngptot)),
-                                          tb.bits(tc.columns(ost.arrays[k], ngptot))), (k, tend_planes, diag)
+                    assert np.array_equal(tb.bits(oc.columns(got[k], ngptot)),
+                                          tb.bits(oc.columns(ost.arrays[k], ngptot))), (k, tend_planes, diag)
 
 
 @pytest.mark.parametrize("precision", [ca.FP64, ca.MIXED], ids=["fp64", "mixed"])
 def test_cpu_run_tendbuf_outputs_all_is_cpu_run_tendbuf(ds, precision):
     """OUTPUTS_ALL: the bits of cloudsc_cpu_run_tendbuf, all 21 fields (the diagnostic ones written)."""
     for ngptot, nproma in ((300, 64), (100, 16)):
-        want = tc.run_tendbuf_checked(ds, ngptot, nproma, precision, 11, "permuted")
+        want = oc.run_tendbuf_checked(ds, ngptot, nproma, precision, 11, "permuted")
         got = run_form(ds, ngptot, nproma, precision, 11, "permuted", ALL, "sentinel", "ds")
         for k in oc.ALL21:
-            assert np.array_equal(tb.bits(tc.columns(got[k], ngptot)), tb.bits(tc.columns(want[k], ngptot))), k
+            assert np.array_equal(tb.bits(oc.columns(got[k], ngptot)), tb.bits(oc.columns(want[k], ngptot))), k
 
 
 @pytest.mark.parametrize("name", fs.STATES)
@@ -313,68 +312,14 @@ def test_cpu_tendbuf_prognostic_on_state(ds, scenarios, oracle_mod, name):
     n = fs.NGPTOT
     for nproma in (64, 16):
         got = run_form(s, n, nproma, ca.FP64, 11, "permuted", PROG, "null", "forms:" + name)
-        assert [k for k in KEPT if not np.array_equal(tb.bits(tc.columns(got[k], n)), tb.bits(exp[k]))] == [], nproma
+        assert [k for k in KEPT if not np.array_equal(tb.bits(oc.columns(got[k], n)), tb.bits(exp[k]))] == [], nproma
         if fs.rain_active(name):        # the carried rain flux reached its output
-            assert np.count_nonzero(tc.columns(got["pfplsl"], n)) > 0, nproma
+            assert np.count_nonzero(oc.columns(got["pfplsl"], n)) > 0, nproma
 
 
 # ---------------------------------------------------------------------------
 # cloudsc_cpu_fields_compare_tendbuf against NumPy on whole buffers
 # ---------------------------------------------------------------------------
-class PackedSide:
-    """A fields_convert_cases.HostSet whose tendency members may live in two packed buffers instead
-    (tend_planes != 0): f points there; view() is the set as the comparison must see it, read back from
-    the whole buffers."""
-
-    def __init__(self, hs, tend_planes, order="permuted"):
-        self.hs, self.tend_planes = hs, tend_planes
-        self.arrays = hs.arrays
-        self.f = hs.fields()
-        self.lay, self.bufs = None, None
-        if tend_planes:
-            dt = ca.storage_dtype(hs.precision)
-            nb = ca.nblocks_of(hs.ngptot, hs.nproma)
-            self.lay = tb.layout(order, tend_planes)
-            self.bufs = [tb.empty_buffer(nb, tend_planes, hs.klev, hs.nproma, dt, s)
-                         for s in (tb.SENTINEL_TMP, tb.SENTINEL_LOC)]
-            for names, buf in ((tb.TMP, self.bufs[0]), (tb.LOC, self.bufs[1])):
-                for n in names:
-                    if n in hs.names:
-                        tb.put(buf, self.lay[n], hs.arrays[n], hs.ngptot)
-                        hs.arrays[n].view(np.uint8)[...] = 0x3C      # the separate array is not the member now
-            bound = ca.Fields()
-            tb.bind(bound, self.lay, *self.bufs)
-            for n in tb.TMP + tb.LOC:
-                if n in hs.names:
-                    setattr(self.f, n, getattr(bound, n))
-
-    def buffer_of(self, name):
-        return self.bufs[0 if name in tb.TMP else 1]
-
-    def view(self):
-        """An object restate() reads: names, ngptot, arrays in block layout."""
-        class V:
-            pass
-        v = V()
-        v.names, v.ngptot, v.nproma = self.hs.names, self.hs.ngptot, self.hs.nproma
-        v.arrays = {}
-        for n in self.hs.names:
-            if self.tend_planes and n in tb.TMP + tb.LOC:
-                a = tb.take(self.buffer_of(n), self.lay[n], n)
-                v.arrays[n] = a.reshape(a.shape[0], -1, a.shape[-1])
-            else:
-                v.arrays[n] = self.hs.arrays[n]
-        return v
-
-
-def cpu_compare(a, b, nthreads=3):
-    diffs = cc.new_diffs()
-    ca.check(ca.gpu_lib().cloudsc_cpu_fields_compare_tendbuf(
-        nthreads, a.hs.ngptot, a.hs.klev, a.hs.precision, a.hs.nproma, a.tend_planes, C.byref(a.f), b.hs.precision,
-        b.hs.nproma, b.tend_planes, C.byref(b.f), diffs))
-    return diffs
-
-
 # (planes, NPROMA, precision) of a side
 SIDES = [(pl, np_, pr) for pl in (0, 8, 11) for np_ in (64, 16) for pr in (ca.FP64, ca.MIXED)]
 

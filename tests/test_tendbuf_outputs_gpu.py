@@ -7,6 +7,7 @@ cloudsc_fields_validate_tendbuf against the parent path (expand / validate on se
 cloudsc_fields_convert_tendbuf); and the CLI's --fields tendbuf-inplace and --outputs prognostic."""
 import ctypes as C
 import os
+import re
 import subprocess
 from fractions import Fraction
 
@@ -14,122 +15,19 @@ import numpy as np
 import pytest
 
 import cloudsc_amd as ca
+import host_harness as hh
 import tendbuf_cases as tb
-import test_outputs_cpu as oc
-import test_stdout_contract as sc
-import test_tendbuf_cpu as tc
-import test_tendbuf_gpu as tg
-from test_tendbuf_gpu import Pair
+from gpu_harness import CASES as SHAPE_CASES, DIAG, DeviceSide, KEPT, NAMES, PRECISIONS, ProgPair, VARIANTS
+from gpu_harness import oracle_columns, validation_table, without_diag
+from gpu_harness import lib, hip, restore_knobs  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
-DIAG, KEPT = oc.DIAG, oc.KEPT
 PROG, ALL = ca.OUTPUTS_PROGNOSTIC, ca.OUTPUTS_ALL
-PRECISIONS = tg.PRECISIONS
-VARIANTS = tg.VARIANTS
 # (planes, order, the ten diagnostic members of the packed set): 8 in the reference order with them NULL,
 # 11 permuted (three unbound planes) with them pointing at arrays that must keep every byte
 SETTINGS = [(8, "reference", "null"), (11, "permuted", "kept")]
-CASES = tg.CASES + [(1, 1, "kcache"), (1, 1, "kseg")]
-
-
-@pytest.fixture(scope="module")
-def lib():
-    lib = ca.gpu_lib()
-    assert ca.device_count() > 0
-    return lib
-
-
-@pytest.fixture(scope="module")
-def hip():
-    h = ca._hip()
-    h.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
-    h.hipStreamCreateWithFlags.argtypes = [C.POINTER(C.c_void_p), C.c_uint]
-    h.hipStreamSynchronize.argtypes = [C.c_void_p]
-    h.hipStreamDestroy.argtypes = [C.c_void_p]
-    return h
-
-
-@pytest.fixture(autouse=True)
-def restore_knobs():
-    yield
-    ca.narrow_pack(-1)
-    ca.kseg_schedule(0, 0)
-    ca.compare_grid(0)
-
-
-def without_diag(f):
-    g = ca.Fields()
-    C.memmove(C.byref(g), C.byref(f), C.sizeof(ca.Fields))
-    for n in DIAG:
-        setattr(g, n, None)
-    return g
-
-
-class ProgPair(Pair):
-    """tg.Pair whose packed set runs cloudsc_gpu_run_tendbuf_outputs."""
-
-    def run_form(self, variant, outputs=PROG, diag="null", stream=None):
-        ws = self.scratch(variant)
-        f = without_diag(self.packed.f) if diag == "null" else self.packed.f
-        ca.gpu_run_tendbuf_outputs(f, self.precision, variant, outputs, self.ngptot, self.nproma, self.ds.klev,
-                                   self.tend_planes, scratch=ws, stream=stream)
-        assert self.lib.cloudsc_gpu_check(0, stream, variant & 0xff, ws) == 0
-
-    def device_mismatches_inplace(self, names=KEPT, stream=None):
-        """cloudsc_fields_compare_tendbuf of the packed set, BUFFER_LOC read in place, against the plain set:
-        {member: mismatches} where not 0."""
-        a = ca.fields_subset(self.packed.f, names)
-        b = ca.fields_subset(self.plain.f, names)
-        d = ca.compare_fields_tendbuf(a, b, self.ngptot, self.ds.klev, self.precision, self.nproma, self.tend_planes,
-                                      self.precision, self.nproma, 0, stream=stream)
-        assert sorted(d) == sorted(names)
-        assert all(v["compared"] > 0 for v in d.values())
-        return {k: v["mismatches"] for k, v in d.items() if v["mismatches"]}
-
-    def host_check_form(self, outputs=PROG):
-        """The same on the host, and the sentinels: returns the list of what is wrong."""
-        self.hip.hipDeviceSynchronize()
-        loc, tmp = np.empty_like(self.buf_loc), np.empty_like(self.buf_tmp)
-        assert self.hip.hipMemcpy(loc.ctypes.data, self.packed.buffer_loc, loc.nbytes, 2) == 0
-        assert self.hip.hipMemcpy(tmp.ctypes.data, self.packed.buffer_tmp, tmp.nbytes, 2) == 0
-        wrong = []
-        if not np.array_equal(tb.bits(tmp), tb.bits(self.buf_tmp)):
-            wrong.append("BUFFER_TMP changed")
-        if not tb.is_sentinel(loc, tb.untouched_mask(loc, self.lay, tb.LOC, self.ngptot), tb.SENTINEL_LOC):
-            wrong.append("BUFFER_LOC: an unbound plane or a padding lane was written")
-        for k in (KEPT if outputs == PROG else tg.NAMES):
-            ref = self.plain.download_raw(k)
-            if k in tb.LOC:
-                got = tb.take(loc, self.lay[k], k)
-            else:
-                got = self.packed.download_raw(k)
-                if not np.array_equal(tb.bits(got), tb.bits(ref)):    # whole arrays: padding lanes included
-                    wrong.append("%s: differs (padding included)" % k)
-            if not np.array_equal(tb.bits(tc.columns(got, self.ngptot)), tb.bits(tc.columns(ref, self.ngptot))):
-                wrong.append("%s: differs" % k)
-        if outputs == PROG:
-            for k in DIAG:
-                if not (oc.bits(self.packed.download_raw(k)) == tg.PATTERN).all():
-                    wrong.append("%s: a diagnostic member was written" % k)
-        return wrong
-
-    def kept_columns(self):
-        loc = np.empty_like(self.buf_loc)
-        self.hip.hipDeviceSynchronize()
-        assert self.hip.hipMemcpy(loc.ctypes.data, self.packed.buffer_loc, loc.nbytes, 2) == 0
-        return {k: tc.columns(tb.take(loc, self.lay[k], k) if k in tb.LOC else self.packed.download_raw(k),
-                              self.ngptot) for k in KEPT}
-
-
-_oracle = {}
-
-
-def oracle_columns(oracle_mod, ds, ngptot, nproma):
-    if (ngptot, nproma) not in _oracle:
-        st, _ = oracle_mod.run_oracle(ds, ngptot, nproma)
-        _oracle[(ngptot, nproma)] = {k: tc.columns(st.arrays[k], ngptot) for k in KEPT}
-    return _oracle[(ngptot, nproma)]
+CASES = SHAPE_CASES + [(1, 1, "kcache"), (1, 1, "kseg")]
 
 
 @pytest.mark.parametrize("precision", sorted(PRECISIONS))
@@ -149,7 +47,7 @@ def test_run_tendbuf_prognostic_bitwise(lib, hip, ds, oracle_mod, ngptot, nproma
             assert pr.device_mismatches_inplace() == {}
             assert pr.host_check_form() == []
             if prec == ca.FP64:
-                got, exp = pr.kept_columns(), oracle_columns(oracle_mod, ds, ngptot, nproma)
+                got, exp = pr.kept_columns(), oracle_columns(oracle_mod, ds, "ds", ngptot, nproma)
                 assert [k for k in KEPT if not np.array_equal(tb.bits(got[k]), tb.bits(exp[k]))] == []
         finally:
             pr.close()
@@ -212,7 +110,7 @@ def test_all_prognostic_all_on_one_workspace(lib, hip, ds, precision):
         for outputs in (ALL, PROG, ALL):
             pr.fill(("packed",))
             pr.run_form(ca.VARIANT_KSEG, outputs, "kept")
-            names = KEPT if outputs == PROG else tuple(tg.NAMES)
+            names = KEPT if outputs == PROG else tuple(NAMES)
             assert pr.device_mismatches_inplace(names) == {}, outputs
             assert pr.host_check_form(outputs) == [], outputs
     finally:
@@ -299,16 +197,15 @@ def test_device_compare_tendbuf_against_host_twin(lib, hip, klev):
     against float, 11 permuted planes against 0 and against 8, planted differences, grids of 1 and 3
     workgroups: every field that must not depend on the grouping is equal."""
     import fields_compare_cases as cc
-    import test_tendbuf_outputs_cpu as tcpu
     names = list(tb.TMP + tb.LOC) + ["pt", "pfplsl", "ktype", "prainfrac_toprfz"]
     for bpl in (0, 8):
         ha, hb, pos = tall_pair(300, 64, 16, klev, ca.FP64, ca.MIXED, names)
-        a, b = tcpu.PackedSide(ha, 11), tcpu.PackedSide(hb, bpl, "reference")
+        a, b = hh.PackedSide(ha, 11), hh.PackedSide(hb, bpl, "reference")
         tb.bits(a.bufs[1])[0, sorted(set(range(11)) - {a.lay[n] + i for n in tb.LOC for i in range(tb.nplanes(n))})[0],
                            0, 0] ^= 1                                        # an unbound plane: never read
-        want = tcpu.cpu_compare(a, b)
+        want = hh.cpu_compare(a, b)
         assert sum(d.mismatches for d in want) >= len(set(pos))
-        da, db = tg.DeviceSide(hip, a), tg.DeviceSide(hip, b)
+        da, db = DeviceSide(hip, a), DeviceSide(hip, b)
         try:
             for grid in (1, 3, 0):
                 ca.compare_grid(grid)
@@ -398,29 +295,29 @@ def cli(*args):
 
 
 def test_cli_tendbuf_inplace_prints_callers_tables():
-    caller = tg.validation_table(cli("--fields", "caller"))
-    inplace = tg.validation_table(cli("--fields", "tendbuf-inplace"))
+    caller = validation_table(cli("--fields", "caller"))
+    inplace = validation_table(cli("--fields", "tendbuf-inplace"))
     assert len(inplace) == 23 and inplace == caller
-    planes = tg.validation_table(cli("--fields", "tendbuf-inplace", "--tend-planes", "11"))
+    planes = validation_table(cli("--fields", "tendbuf-inplace", "--tend-planes", "11"))
     assert planes == caller
 
 
 @pytest.mark.parametrize("common", [[], ["--variant", "kcache", "--precision", "mixed"]], ids=["default", "kcache_mixed"])
 def test_cli_outputs_prognostic(common):
-    full = tg.validation_table(cli("--fields", "caller", *common))
+    full = validation_table(cli("--fields", "caller", *common))
     assert len(full) == 23
     kept_rows = [ln for ln in full[1:-1] if ln.split()[0].lower() not in [d.lower() for d in DIAG]]
     assert len(kept_rows) == 11
     for fields in ("caller", "tendbuf", "tendbuf-inplace"):
         out = cli("--fields", fields, "--outputs", "prognostic", *common)
-        table = tg.validation_table(out)
+        table = validation_table(out)
         assert table[0] == full[0]
         assert table[1:-1] == kept_rows, fields
         assert table[-1].split("(")[0] == full[-1].split("(")[0]            # VALIDATION: PASSED / reported only
         # the JUBE patterns of tests/test_stdout_contract.py: the timing rows, and each kept field's five values
-        sc.check_timing(out, 1, 300, 64, 5)
-        for (f, col), pat in sc.result_patterns().items():
-            flags = sc.re.IGNORECASE if f.startswith("tendency") else 0
-            found = sc.re.findall(sc.jube(pat), out, flags)
+        hh.check_timing(out, 1, 300, 64, 5)
+        for (f, col), pat in hh.result_patterns().items():
+            flags = re.IGNORECASE if f.startswith("tendency") else 0
+            found = re.findall(hh.jube(pat), out, flags)
             assert len(found) == (0 if f.lower() in DIAG else 1), (fields, f, col, found)
         assert cli("--fields", fields, "--outputs", "all", *common).splitlines()[-23:] == full
