@@ -156,6 +156,18 @@ class Spp(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in SPP_SLOTS]
 
 
+class Advance(C.Structure):
+    """cloudsc_advance_t: where an advancing step stores the updated prognostics -- t, q, a [nblocks][klev][nproma]
+    and clv [nblocks][5][klev][nproma] (the vapour plane never written) in the set's storage type.  Each is the
+    set's own pt / pq / pa / pclv (in place) or another array."""
+    _fields_ = [(n, C.c_void_p) for n in ("t", "q", "a", "clv")]
+
+    @classmethod
+    def in_place(cls, f: "Fields") -> "Advance":
+        """The Advance that rewrites pt, pq, pa and pclv of f."""
+        return cls(f.pt, f.pq, f.pa, f.pclv)
+
+
 class Placement(C.Structure):
     """cloudsc_placement_t: what a placement search cost and found."""
     _fields_ = [("probe_first_ms", C.c_float), ("probe_final_ms", C.c_float), ("tries", C.c_int),
@@ -580,6 +592,15 @@ def gpu_lib(path: Optional[str] = None):
         lib.cloudsc_gpu_run_spp.argtypes = [C.c_int, C.c_void_p] + [C.c_int] * 6 + [C.POINTER(Fields), C.POINTER(Spp),
                                                                                     C.c_void_p]
         lib.cloudsc_cpu_run_spp.argtypes = [C.c_int] * 6 + [C.POINTER(Params), C.POINTER(Fields), C.POINTER(Spp)]
+    if hasattr(lib, "cloudsc_gpu_run_advance"):   # (likewise: the advancing step and its separate pass)
+        lib.cloudsc_gpu_run_advance.argtypes = [C.c_int, C.c_void_p] + [C.c_int] * 6 + [
+            C.POINTER(Fields), C.POINTER(Advance), C.c_void_p]
+        lib.cloudsc_cpu_run_advance.argtypes = [C.c_int] * 6 + [C.POINTER(Params), C.POINTER(Fields),
+                                                                C.POINTER(Advance)]
+        lib.cloudsc_fields_advance.argtypes = [C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.POINTER(Fields),
+                                                                                       C.POINTER(Advance)]
+        lib.cloudsc_cpu_fields_advance.argtypes = [C.c_int] * 5 + [C.POINTER(Params), C.POINTER(Fields),
+                                                                   C.POINTER(Advance)]
     if hasattr(lib, "cloudsc_fields_compare_outputs"):   # (likewise: the forms for a set of one output selection)
         lib.cloudsc_fields_convert_outputs.argtypes = [C.c_int, C.c_void_p] + [C.c_int] * 5 + [
             C.POINTER(Fields), C.c_int, C.c_int, C.POINTER(Fields)]
@@ -868,6 +889,43 @@ def cpu_run_spp(params: "Params", f: "Fields", spp: "Spp", precision: int, outpu
     require_blocked(f, "cpu_run_spp")
     check(gpu_lib().cloudsc_cpu_run_spp(nthreads, precision, outputs, ngptot, nproma, klev, C.byref(params),
                                         C.byref(f), C.byref(spp)))
+
+
+def gpu_run_advance(f: "Fields", adv: "Advance", precision: int, variant: int, outputs: int, ngptot: int,
+                    nproma: int, klev: int, scratch=None, device: int = 0, stream=None) -> None:
+    """cloudsc_gpu_run_advance: the step (OUTPUTS_ALL or OUTPUTS_SURFACE) with the updated prognostics X_new =
+    (X + ptsphy * tendency_tmp) + ptsphy * tendency_loc stored to `adv` instead of the seven local tendencies
+    (tendency_loc_* may be None and are never touched).  Each member of adv is the set's own state member (in
+    place: Advance.in_place(f)) or another DEVICE array.  Working type: double for fp64 and mixed (mixed =
+    float32(fp64 form(float64 inputs))), float for fp32.  Asynchronous; N calls in place integrate N steps."""
+    require_blocked(f, "gpu_run_advance")
+    check(gpu_lib().cloudsc_gpu_run_advance(device, stream, precision, variant, outputs, ngptot, nproma, klev,
+                                            C.byref(f), C.byref(adv), scratch))
+
+
+def cpu_run_advance(params: "Params", f: "Fields", adv: "Advance", precision: int, outputs: int, ngptot: int,
+                    nproma: int, klev: int, nthreads: int = 0) -> None:
+    """cloudsc_cpu_run_advance: the same on HOST memory (fp64 and mixed)."""
+    require_blocked(f, "cpu_run_advance")
+    check(gpu_lib().cloudsc_cpu_run_advance(nthreads, precision, outputs, ngptot, nproma, klev, C.byref(params),
+                                            C.byref(f), C.byref(adv)))
+
+
+def advance_fields(f: "Fields", adv: "Advance", precision: int, ngptot: int, nproma: int, klev: int,
+                   device: int = 0, stream=None) -> None:
+    """cloudsc_fields_advance: the separate pass on the device over a set whose tendency_loc_* a step has filled,
+    with ptsphy of the device's parameter set.  Equal to the fused form bit for bit in fp64 and fp32; in mixed
+    it can only take the stored (narrowed) tendency, so some elements differ in the last bit.  Asynchronous."""
+    require_blocked(f, "advance_fields")
+    check(gpu_lib().cloudsc_fields_advance(device, stream, precision, ngptot, nproma, klev, C.byref(f), C.byref(adv)))
+
+
+def cpu_advance_fields(params: "Params", f: "Fields", adv: "Advance", precision: int, ngptot: int, nproma: int,
+                       klev: int, nthreads: int = 0) -> None:
+    """cloudsc_cpu_fields_advance: the same on HOST arrays with ptsphy from `params` (all three precisions)."""
+    require_blocked(f, "cpu_advance_fields")
+    check(gpu_lib().cloudsc_cpu_fields_advance(nthreads, precision, ngptot, nproma, klev, C.byref(params), C.byref(f),
+                                               C.byref(adv)))
 
 
 def accumulate_tendbuf(loc: "Fields", cml: "TendCml", precision: int, ngptot: int, nproma: int, klev: int,

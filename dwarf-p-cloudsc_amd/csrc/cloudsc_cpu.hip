@@ -42,8 +42,9 @@ struct HostColumn {
 // PROG: the prognostic-outputs form, the ten diagnostic flux members of A never touched (flux_level);
 // SURF: the surface-fluxes form, the other four flux members surface fields written after the last level;
 // CML: the cumulative tendency form, A a KArgsCML and the local tendencies added to its planes (load_cml, store_level_cml);
-// SPP: the per-column multiplier form, A a KArgsSPP (SppCol: the multipliers read from the host fields where they are used)
-template <typename real, bool AER, bool TB, bool PROG, bool SURF, bool CML, bool SPP, typename S>
+// SPP: the per-column multiplier form, A a KArgsSPP (SppCol: the multipliers read from the host fields where they are used);
+// ADV: the advancing form, A a KArgsADV and the updated prognostics stored to its arrays (store_level_adv)
+template <typename real, bool AER, bool TB, bool PROG, bool SURF, bool CML, bool SPP, bool ADV, typename S>
 void run_block(const DevParamsSpp<real>& c, const KArgs<real, S>& A, int b, std::vector<HostColumn<real>>& col) {
   const int nproma = A.nproma, klev = A.klev;
   const int bsize = std::min(nproma, A.ngptot - b * nproma);
@@ -99,6 +100,8 @@ void run_block(const DevParamsSpp<real>& c, const KArgs<real, S>& A, int b, std:
         CmlIn<real> cm;
         load_cml(cm, A, u2, k, klev, nproma, lo);
         store_level_cml(A, u2, k, klev, nproma, lo, ls, po, cm);
+      } else if constexpr (ADV) {
+        store_level_adv(c, A, u2, u3, k, klev, nproma, lo, ls, po);
       } else {
         store_level<TB>(A, u2, u3, k, klev, nproma, lo, physics, ls, po);
       }
@@ -159,6 +162,13 @@ int cpu_run(int ngptot, int nproma, int klev, const cloudsc_params_t* params, co
     M.mult[SPP_RCLCRIT] = (const S*)spp->rclcrit; M.mult[SPP_RLCRITSNOW] = (const S*)spp->rlcritsnow;
     M.mult[SPP_RPECONS] = (const S*)spp->rpecons;
   }
+  // and so has the advancing form
+  KArgsADV<double, S> V;
+  static_cast<KArgs<double, S>&>(V) = A;
+  V.adv_t = V.adv_q = V.adv_a = V.adv_clv = nullptr;
+  if (const cloudsc_advance_t* adv = form.adv) {
+    V.adv_t = (S*)adv->t; V.adv_q = (S*)adv->q; V.adv_a = (S*)adv->a; V.adv_clv = (S*)adv->clv;
+  }
   const int nblocks = ngptot / nproma + (ngptot % nproma ? 1 : 0);
   if (nthreads <= 0) nthreads = (int)std::max(1u, std::thread::hardware_concurrency());
   const int nreq = nthreads;                 // the caller's per-thread arrays have nreq entries
@@ -179,15 +189,16 @@ int cpu_run(int ngptot, int nproma, int klev, const cloudsc_params_t* params, co
     for (int b = next.fetch_add(1); b < nblocks; b = next.fetch_add(1)) {
       // the run_block of the form: those whose bits go together (form_bits_consistent), as on the GPU
       dispatch_bools(
-          [&](auto AER, auto TB, auto PROG, auto SURF, auto CML, auto SPP) {
-            if constexpr (form_bits_consistent(form_bits(TB, PROG, SURF, CML, SPP))) {
-              if constexpr (SPP) run_block<double, AER, TB, PROG, SURF, CML, SPP>(c, M, b, col);
-              else run_block<double, AER, TB, PROG, SURF, CML, SPP>(c, A, b, col);
+          [&](auto AER, auto TB, auto PROG, auto SURF, auto CML, auto SPP, auto ADV) {
+            if constexpr (form_bits_consistent(form_bits(TB, PROG, SURF, CML, SPP, ADV))) {
+              if constexpr (ADV) run_block<double, AER, TB, PROG, SURF, CML, SPP, ADV>(c, V, b, col);
+              else if constexpr (SPP) run_block<double, AER, TB, PROG, SURF, CML, SPP, ADV>(c, M, b, col);
+              else run_block<double, AER, TB, PROG, SURF, CML, SPP, ADV>(c, A, b, col);
             }
             return 0;
           },
           aer, (bits & kFormTb) != 0, (bits & kFormProg) != 0, (bits & kFormSurf) != 0, (bits & kFormCml) != 0,
-          (bits & kFormSpp) != 0);
+          (bits & kFormSpp) != 0, (bits & kFormAdv) != 0);
       icalls++;
       igpc += std::min(nproma, ngptot - b * nproma);
     }
@@ -275,4 +286,14 @@ extern "C" int cloudsc_cpu_run_spp(int nthreads, int precision, int outputs, int
                                    const cloudsc_params_t* params, const cloudsc_fields_t* f,
                                    const cloudsc_spp_t* spp) {
   return cpu_run_form(precision, ngptot, nproma, klev, params, f, {0, outputs, nullptr, spp}, kFormSpp, {nthreads});
+}
+
+// (CLOUDSC_OUTPUTS_PROGNOSTIC alone is no form: form_bits_consistent)
+extern "C" int cloudsc_cpu_run_advance(int nthreads, int precision, int outputs, int ngptot, int nproma, int klev,
+                                       const cloudsc_params_t* params, const cloudsc_fields_t* f,
+                                       const cloudsc_advance_t* adv) {
+  cloudsc_impl::StepForm form;
+  form.outputs = outputs;
+  form.adv = adv;
+  return cpu_run_form(precision, ngptot, nproma, klev, params, f, form, kFormAdv, {nthreads});
 }

@@ -101,6 +101,7 @@ int param_set_upload(ParamSet* ps, int device, const cloudsc_params_t* p) {
   ps->device = device;
   ps->aer = p->laericesed || p->laericeauto;
   ps->ncldtop = p->ncldtop;
+  ps->ptsphy = p->ptsphy;
   return CLOUDSC_OK;
 }
 
@@ -116,6 +117,7 @@ int param_set_copy(ParamSet* dst, const ParamSet* src) {
   dst->device = src->device;
   dst->aer = src->aer;
   dst->ncldtop = src->ncldtop;
+  dst->ptsphy = src->ptsphy;
   return CLOUDSC_OK;
 }
 
@@ -137,7 +139,7 @@ bool fields_complete(const cloudsc_fields_t* f, const StepForm& form) {
   const void* const* p = (const void* const*)f;
   for (int m = 0; m < kNumFields; m++)
     if (!p[m] && kFieldTable[m].dir != CLOUDSC_FD_AEROSOL && output_selected(m, form.outputs) &&
-        !(form.cml && is_tendency_loc(m)))
+        !((form.cml || form.adv) && is_tendency_loc(m)))
       return false;
   return true;
 }
@@ -168,6 +170,7 @@ int check_step_form(const StepForm& form, unsigned need, const cloudsc_fields_t*
     }
     if (!f || !any) return CLOUDSC_EINVAL;
   }
+  if (form.adv && !advance_members_ok(f, form.adv)) return CLOUDSC_EINVAL;
   return CLOUDSC_OK;
 }
 
@@ -213,6 +216,9 @@ __device__ __forceinline__ cptr<typename F::params> params_of(cptr<typename F::f
 //   F::spp   the per-column multiplier form (cloudsc_gpu_run_spp): alone or with
 //            F::prog, the first argument a KArgsSPP, the five multiplier fields
 //            behind the KArgs;
+//   F::adv   the advancing form (cloudsc_gpu_run_advance): alone or with F::surf,
+//            the first argument a KArgsADV, the four arrays of the updated
+//            prognostics behind the KArgs; the tendency_loc_* members are never read;
 //   F::pack  narrow blocks (NPROMA <= 32) packed into full waves: a workgroup
 //            is one wave that walks PackArgs::pack consecutive blocks.
 // A kernel has exactly the arguments its form needs: Pack is PackArgs for
@@ -312,7 +318,7 @@ constexpr int kPrecisionOf = !std::is_same<real, S>::value ? CLOUDSC_MIXED : siz
 template <typename real, typename S, bool FAST>
 constexpr bool kernel_kept(int kind, bool aer, unsigned form = 0u) {
 #ifdef CLOUDSC_ONLY_KSEG
-  if (kind != CLOUDSC_VARIANT_KSEG || aer || (form & (kFormTb | kFormProg | kFormSurf | kFormCml | kFormSpp)) || sizeof(real) != CLOUDSC_ONLY_KSEG ||
+  if (kind != CLOUDSC_VARIANT_KSEG || aer || (form & (kFormTb | kFormProg | kFormSurf | kFormCml | kFormSpp | kFormAdv)) || sizeof(real) != CLOUDSC_ONLY_KSEG ||
       sizeof(S) != CLOUDSC_ONLY_KSEG)
     return false;
 #endif
@@ -333,7 +339,7 @@ struct LaunchForm {
   using product = cfg<DefaultCfg<real>::waves, DefaultCfg<real>::pf, false>;
 };
 constexpr bool cfg_table_applies(int kind, unsigned form) {
-  return !(form & (kFormTb | kFormProg | kFormSurf | kFormCml | kFormSpp)) &&
+  return !(form & (kFormTb | kFormProg | kFormSurf | kFormCml | kFormSpp | kFormAdv)) &&
          (kind == CLOUDSC_VARIANT_KSEG || !(form & kFormPack));
 }
 template <typename LF, bool TABLE, typename Fn>
@@ -354,10 +360,17 @@ int with_cfg(Fn&& f) {
 
 // the kernel arguments of a launch: a's, with tend_planes behind them in the tendency buffer form and the
 // BUFFER_CML plane starts behind that in the cumulative tendency form, or the five multiplier fields behind them
-// in the per-column multiplier form
+// in the per-column multiplier form, or the four arrays of the updated prognostics in the advancing form
 template <typename F>
 typename F::kargs kernel_args(const typename F::fields& a, const StepForm& form) {
-  if constexpr (F::spp) {
+  if constexpr (F::adv) {
+    using S = typename F::store;
+    typename F::kargs t;
+    static_cast<typename F::fields&>(t) = a;
+    const cloudsc_advance_t* adv = form.adv;
+    t.adv_t = (S*)adv->t; t.adv_q = (S*)adv->q; t.adv_a = (S*)adv->a; t.adv_clv = (S*)adv->clv;
+    return t;
+  } else if constexpr (F::spp) {
     using S = typename F::store;
     typename F::kargs t;
     static_cast<typename F::fields&>(t) = a;
@@ -689,15 +702,15 @@ int launch_v(const LaunchRequest& rq) {
   // conditions become F's members here, and only kernels that exist are instantiated
   const auto with_form = [&](auto kind_c, auto&& go) {
     return dispatch_bools(
-        [&](auto AER, auto PACK, auto TB, auto PROG, auto SURF, auto CML, auto SPP) {
-          constexpr unsigned form = form_bits(TB, PROG, SURF, CML, SPP) | (PACK ? kFormPack : 0u);
+        [&](auto AER, auto PACK, auto TB, auto PROG, auto SURF, auto CML, auto SPP, auto ADV) {
+          constexpr unsigned form = form_bits(TB, PROG, SURF, CML, SPP, ADV) | (PACK ? kFormPack : 0u);
           if constexpr (kernel_kept<real, ST, FAST>(kind_c, AER, form))
             return with_cfg<LaunchForm<real, ST, AER, FAST, form>, cfg_table_applies(kind_c, form)>(go);
           else
             return (int)CLOUDSC_EINVAL;
         },
         aer, pack > 1, (bits & kFormTb) != 0, (bits & kFormProg) != 0, (bits & kFormSurf) != 0, (bits & kFormCml) != 0,
-        (bits & kFormSpp) != 0);
+        (bits & kFormSpp) != 0, (bits & kFormAdv) != 0);
   };
   if (kind == CLOUDSC_VARIANT_KCACHE) {
     rc = with_form(std::integral_constant<int, CLOUDSC_VARIANT_KCACHE>{}, [&](auto form) {
@@ -950,6 +963,15 @@ int cloudsc_gpu_run_spp(int device, void* stream, int precision, int variant, in
                         int klev, const cloudsc_fields_t* f, const cloudsc_spp_t* spp, void* scratch) {
   return gpu_run_form(device, stream, {precision, variant, ngptot, nproma, klev}, f, scratch, {0, outputs, nullptr, spp},
                       kFormSpp);
+}
+
+// (every rule before the first HIP call; CLOUDSC_OUTPUTS_PROGNOSTIC alone is no form: form_bits_consistent)
+int cloudsc_gpu_run_advance(int device, void* stream, int precision, int variant, int outputs, int ngptot, int nproma,
+                            int klev, const cloudsc_fields_t* f, const cloudsc_advance_t* adv, void* scratch) {
+  StepForm form;
+  form.outputs = outputs;
+  form.adv = adv;
+  return gpu_run_form(device, stream, {precision, variant, ngptot, nproma, klev}, f, scratch, form, kFormAdv);
 }
 
 int cloudsc_gpu_check(int device, void* stream, int variant, void* scratch) {

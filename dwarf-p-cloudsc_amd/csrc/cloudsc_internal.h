@@ -13,7 +13,7 @@
 
 namespace cloudsc {
 // the bits of a k-caching kernel's form (KForm, cloudsc_kcache.h)
-enum : unsigned { kFormPack = 1u, kFormTb = 2u, kFormProg = 4u, kFormSurf = 8u, kFormCml = 16u, kFormSpp = 32u };
+enum : unsigned { kFormPack = 1u, kFormTb = 2u, kFormProg = 4u, kFormSurf = 8u, kFormCml = 16u, kFormSpp = 32u, kFormAdv = 64u };
 }  // namespace cloudsc
 
 namespace cloudsc_impl {
@@ -64,6 +64,7 @@ struct ParamSet {
   int device = -1;
   bool aer = false;        // LAERICESED || LAERICEAUTO: aerosol inputs are read
   int ncldtop = 0;         // NCLDTOP (KSEG segment bounds)
+  double ptsphy = 0.0;     // PTSPHY (cloudsc_fields_advance)
 };
 int check_params(const cloudsc_params_t* p);
 // (re)upload `p` into ps (allocated on first use) on `device`; synchronous
@@ -114,24 +115,27 @@ struct StepForm {
   int outputs = CLOUDSC_OUTPUTS_ALL;        // CLOUDSC_OUTPUTS_*
   const cloudsc_tend_cml_t* cml = nullptr;  // the cumulative tendency planes
   const cloudsc_spp_t* spp = nullptr;       // the per-column parameter multipliers
+  const cloudsc_advance_t* adv = nullptr;   // the advancing form: where the updated prognostics go
 };
 // a form's kForm* bits (kFormPack is the launch's own, not a form's)
-constexpr unsigned form_bits(bool tb, bool prog, bool surf, bool cml, bool spp = false) {
+constexpr unsigned form_bits(bool tb, bool prog, bool surf, bool cml, bool spp = false, bool adv = false) {
   using namespace cloudsc;
   return (tb ? kFormTb : 0u) | (prog ? kFormProg : 0u) | (surf ? kFormSurf : 0u) | (cml ? kFormCml : 0u) |
-         (spp ? kFormSpp : 0u);
+         (spp ? kFormSpp : 0u) | (adv ? kFormAdv : 0u);
 }
 constexpr unsigned form_bits(const StepForm& s) {
   return form_bits(s.tend_planes != 0, outputs_prognostic(s.outputs), outputs_surface(s.outputs), s.cml != nullptr,
-                   s.spp != nullptr);
+                   s.spp != nullptr, s.adv != nullptr);
 }
 // The support matrix, the part the bits alone decide: the surface-fluxes form is a prognostic-outputs form, the
 // cumulative tendency form a tendency buffer, prognostic-outputs form, the per-column multiplier form stands alone or
-// with the prognostic-outputs form only (KForm's static_asserts)
+// with the prognostic-outputs form only, the advancing form stands alone or with the surface-fluxes form only
+// (KForm's static_asserts)
 constexpr bool form_bits_consistent(unsigned form) {
   using namespace cloudsc;
   return (!(form & kFormSurf) || (form & kFormProg)) && (!(form & kFormCml) || ((form & kFormTb) && (form & kFormProg))) &&
-         (!(form & kFormSpp) || !(form & (kFormTb | kFormSurf | kFormCml)));
+         (!(form & kFormSpp) || !(form & (kFormTb | kFormSurf | kFormCml))) &&
+         (!(form & kFormAdv) || (!(form & (kFormTb | kFormCml | kFormSpp)) && (!(form & kFormProg) || (form & kFormSurf))));
 }
 // The support matrix: whether (variant kind, precision, fp32 exact-libm, form bits) has a GPU kernel.  MIXED runs on the
 // k-caching variants only; so do the forms, alone or combined, which fp32 has with its default exp/pow only; the SCC
@@ -158,15 +162,32 @@ int dispatch_bools(Fn&& f, bool c, Rest... rest) {
 }
 
 // every pointer the step reads or writes (aerosol inputs, with CLOUDSC_OUTPUTS_PROGNOSTIC the ten diagnostic
-// fluxes and, in the cumulative tendency form, tendency_loc_t/q/a/cld excepted) is set
+// fluxes and, in the cumulative tendency and the advancing form, tendency_loc_t/q/a/cld excepted) is set
 bool fields_complete(const cloudsc_fields_t* f, const StepForm& form = {});
 // The rules of a form that need neither a shape nor a device, the same for the GPU and the CPU entries: a known
 // selection, the bits `need` that the entry stands for, bits that go together, a plane count in range, and the
 // pointer rules of the cumulative planes -- cml's four members set, none of them a tendency_tmp_* or
 // tendency_loc_* member of f (pointer equality only) -- and of the multipliers -- at least one member of spp set,
-// none of them a member of f.  A form the entry does not stand for (bits outside `need`: a cml or an spp the
+// none of them a member of f -- and of the advancing form -- adv's four members set, each its
+// own state member of f (pt, pq, pa, pclv: in place) or no member of f at all, no two of them equal.  A form the entry does not stand for (bits outside `need`: a cml or an spp the
 // entry never passes) cannot occur.  CLOUDSC_EINVAL or CLOUDSC_OK.
 int check_step_form(const StepForm& form, unsigned need, const cloudsc_fields_t* f);
+// The pointer rules of cloudsc_advance_t, for the step's entries and for the separate pass (cloudsc_advance.hip): the
+// four members set, no two of them equal, each its own state member of f (pt, pq, pa, pclv: in place) or no member
+// of f at all.  Pointer equality only.
+inline bool advance_members_ok(const cloudsc_fields_t* f, const cloudsc_advance_t* adv) {
+  if (!f || !adv || !adv->t || !adv->q || !adv->a || !adv->clv) return false;
+  const void* const mine[4] = {adv->t, adv->q, adv->a, adv->clv};
+  const int own[4] = {CLOUDSC_M_pt, CLOUDSC_M_pq, CLOUDSC_M_pa, CLOUDSC_M_pclv};
+  const void* const* theirs = (const void* const*)f;
+  for (int i = 0; i < 4; i++) {
+    for (int j = 0; j < i; j++)
+      if (mine[i] == mine[j]) return false;
+    for (int m = 0; m < kNumFields; m++)
+      if (m != own[i] && mine[i] == theirs[m]) return false;
+  }
+  return true;
+}
 // Host record of one KSEG workspace owned by a caller that launches on it in
 // stream order (a state): after the first launch zeroes it, later launches
 // continue its ticket counter and flag stamps instead of zeroing it again.

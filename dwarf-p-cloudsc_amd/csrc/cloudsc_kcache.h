@@ -77,6 +77,14 @@ template <typename real, typename store = real>
 struct KArgsSPP : KArgs<real, store> {
   const store* mult[SPP_N];
 };
+// The kernel arguments of the "advancing" form (ADV, cloudsc_gpu_run_advance): the plain KArgs, and behind them the
+// four arrays of cloudsc_advance_t, to which the step stores the updated prognostics (store_level_adv) instead of
+// the local tendencies: tlt, tlq, tla and tlcld are never touched (they may be NULL).  Each array is the state
+// member it advances (pt, pq, pa, pclv: in place) or another array of the same shape.
+template <typename real, typename store = real>
+struct KArgsADV : KArgs<real, store> {
+  store *adv_t, *adv_q, *adv_a, *adv_clv;
+};
 
 // One k-caching kernel, described at compile time: the compute and storage
 // types, the configuration (occupancy target WAVES, load schedule PF, aerosol
@@ -89,6 +97,7 @@ struct KArgsSPP : KArgs<real, store> {
 //              stored once, after the last level, as surface fields
 //   kFormCml   the cumulative tendency form (KArgsCML, load_cml, store_level_cml): kFormTb and kFormProg
 //   kFormSpp   the per-column multiplier form (KArgsSPP, SppCol): alone or with kFormProg
+//   kFormAdv   the advancing form (KArgsADV, store_level_adv): alone or with kFormProg and kFormSurf
 // The kernel entries, the bodies below and the host's launch path all take the
 // descriptor and read its members by name.  (The bits themselves are in cloudsc_internal.h, beside the
 // support matrix that the GPU and the CPU entries share.)
@@ -100,15 +109,19 @@ struct KForm {
   static constexpr bool aer = AER, ldsc = LDSC, fast = FAST;
   static constexpr bool pack = (FORM & kFormPack) != 0, tb = (FORM & kFormTb) != 0, prog = (FORM & kFormProg) != 0;
   static constexpr bool surf = (FORM & kFormSurf) != 0, cml = (FORM & kFormCml) != 0, spp = (FORM & kFormSpp) != 0;
+  static constexpr bool adv = (FORM & kFormAdv) != 0;
   static_assert(!surf || prog, "the surface-fluxes form is a prognostic-outputs form");
   static_assert(!cml || (tb && prog), "the cumulative tendency form is a tendency buffer, prognostic-outputs form");
   static_assert(!spp || !(tb || surf || cml), "the per-column multiplier form stands alone or with the prognostic-outputs form");
+  static_assert(!adv || (!(tb || cml || spp) && prog == surf), "the advancing form stands alone or with the surface-fluxes form");
   using fields = KArgs<real, store>;   // what the bodies read: the kernel arguments, or their base in the TB form
   // the kernel's first argument
   using kargs = typename std::conditional<
-      spp, KArgsSPP<real, store>,
-      typename std::conditional<cml, KArgsCML<real, store>,
-                                typename std::conditional<tb, KArgsTB<real, store>, fields>::type>::type>::type;
+      adv, KArgsADV<real, store>,
+      typename std::conditional<
+          spp, KArgsSPP<real, store>,
+          typename std::conditional<cml, KArgsCML<real, store>,
+                                    typename std::conditional<tb, KArgsTB<real, store>, fields>::type>::type>::type>::type;
   using params = DevParamsT<real, fast, false, spp>;                                  // the parameter block
 };
 
@@ -747,6 +760,55 @@ CLOUDSC_HD void store_level_cml(const KArgs<real, S>& A, size_t u2, int k, int k
     stg_sp<kSpOpaque<real, S>>(M.cml_cld, t3 + ((size_t)m * klev + k) * nproma, lot, cm.cld[m] + po.ctend[m]);
 }
 
+// store_level of the advancing form (ADV).  The seven local tendencies are not stored: each advances the value the
+// step started from, X_new = X0 + ptsphy * loc -- one multiply and one add in `real`, each with its own rounding
+// (-ffp-contract=off), narrowed by the store where the fields are float under double -- and X_new is stored to the
+// form's own array with the outputs' write-through policy.  X0 = X + ptsphy * tendency_tmp is what init_level formed
+// and nothing since has changed: ztp1 (the Newton steps of 3.4 work on a scalar of their own), zqx0[QV] and
+// zqx0[ql..qs] (the tidy-up works on zqx) and zaorig (taken before the tidy-up and the clipping of za); physics_level
+// reads all of them through const copies.  tlt, tlq, tla and tlcld are not touched; the vapour plane behind adv_clv,
+// whose tendency is identically zero, neither.
+//
+// In place (adv_x == the state member x).  A state element [b][k][jl] is read by exactly one lane, the one that
+// owns column (b, jl), and only as part of that column's level k inputs (load_level, load_early: pt, pq, pa and
+// pclv at row k; what level k needs of level k - 1 -- t_prev, a_prev -- travels in the carried state, never through
+// memory); the same lane is the only one that stores it, here, with a value computed from that very load.  So the
+// store follows its element's one consumed load by data dependence, in every load schedule:
+//   PF 0, 2   row k is loaded at the top of level k and stored at its end;
+//   PF 1, 4   row k + 1 is in flight while level k computes and stores row k: another element.  At the last level
+//             the clamped prefetch re-reads row klev - 1 before that row's store; its value is never consumed;
+//   PF 3      the same with the early inputs of row k + 1 issued in the middle of level k;
+//   KSEG      a segment [lev0, lev1) loads rows lev0 .. lev1 (row lev1 by the last level's prefetch, never
+//             consumed) and stores rows lev0 .. lev1 - 1; the next segment of the column starts after the hand-off
+//             and loads rows >= lev1, which no earlier segment has stored.  The hand-off record carries t_prev and
+//             a_prev of row lev1 - 1 as computed, not as re-read;
+//   packed    a lane serves one column of one block of its group throughout: the argument holds lane by lane.
+// No other lane, wave or workgroup reads or writes the element, so there is no ordering to keep across lanes, and
+// a later launch on the same stream (the next time step) sees the stores as it sees any output.
+template <typename real, typename S>
+CLOUDSC_HD const KArgsADV<real, S>& adv_args_of(const KArgs<real, S>& A) {
+  return static_cast<const KArgsADV<real, S>&>(A);
+}
+template <typename real, typename P, typename S, typename LO>
+CLOUDSC_HD void store_level_adv(const P& c, const KArgs<real, S>& A, size_t u2, size_t u3, int k, int klev, int nproma,
+                                LO lane, const LevelState<real>& ls, const PhysOut<real>& po) {
+  const KArgsADV<real, S>& V = adv_args_of(A);
+  const size_t i = u2 + (size_t)k * nproma;
+  const unsigned lo = lo_full(lane), lsp = lo_spec(lane);
+  const real dt = c.ptsphy;
+  const real dtt = dt * ls.ttend, dtq = dt * ls.qtend, dta = dt * po.atend;
+  stg(V.adv_t, i, lo, ls.ztp1 + dtt);
+  stg(V.adv_q, i, lo, ls.zqx0[QV] + dtq);
+  stg(V.adv_a, i, lo, ls.zaorig + dta);
+  stg(A.pcovptot, i, lo, po.zcovptot_out);
+  stg(A.plude, i, lo, po.plude_k);   // as store_level
+#pragma unroll
+  for (int m = 0; m < 4; m++) {
+    const real dtc = dt * po.ctend[m];
+    stg_sp<kSpOpaque<real, S>>(V.adv_clv, u3 + ((size_t)m * klev + k) * nproma, lsp, ls.zqx0[m] + dtc);
+  }
+}
+
 template <typename real, bool PROG = false, typename CS>
 CLOUDSC_HD void init_carry(CS& cs) {
   cs.t_prev = cs.a_prev = cs.pap_prev = R(0.0);
@@ -779,7 +841,8 @@ __device__ __forceinline__ const auto& params_here(const PV& pv, cptr<PT> cpar) 
 // then points at a KArgsTB); F::prog: the prognostic-outputs form (flux_level); F::surf: the
 // surface-fluxes form (flux_level stores nothing; the caller stores the surface row, flux_surface);
 // F::cml: the cumulative tendency form (`ka` points at a KArgsCML; load_cml, store_level_cml);
-// F::spp: the per-column multiplier form (`ka` points at a KArgsSPP; SppCol).
+// F::spp: the per-column multiplier form (`ka` points at a KArgsSPP; SppCol);
+// F::adv: the advancing form (`ka` points at a KArgsADV; store_level_adv).
 //
 // Where F::cml issues the seven BUFFER_CML loads of level k (CLOUDSC_CML_AT): 2 = at the top of the
 // level, behind the level's own loads; 1 = in the middle of the level (the physics' mid hook), ahead
@@ -962,6 +1025,7 @@ __device__ __forceinline__ void kcache_levels(cptr<typename F::fields> ka, cptr<
       const LO los = PVR || std::is_same<LO, PackLo>::value ? launder_vgpr(lo0) : lo;
       if constexpr (F::cml && CLOUDSC_CML_AT == 0) load_cml(cm, A, u2, k, klev, nproma, los);
       if constexpr (F::cml) store_level_cml(A, u2, k, klev, nproma, los, ls, po, cm);
+      else if constexpr (F::adv) store_level_adv(c, A, u2, u3, k, klev, nproma, los, ls, po);
       else store_level<F::tb>(A, u2, u3, k, klev, nproma, los, physics, ls, po);
       flux_level<F::prog, F::surf>(c, A, uh + (size_t)(k + 1) * nproma, los, cur, ls, po, nb.paph_k, nb.paph_n, cs);
     }

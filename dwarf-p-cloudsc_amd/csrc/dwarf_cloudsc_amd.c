@@ -63,6 +63,7 @@ typedef struct {
   int tend_planes;                /* --fields tendbuf: planes per block of the two tendency buffers (0: not tendbuf) */
   int outputs, outputs_given;     /* --outputs all|prognostic|surface: CLOUDSC_OUTPUTS_* */
   int spp;                        /* --spp unit: the step through the SPP form, five all-ones multiplier fields */
+  int advance;                    /* --advance N: N advancing steps in place (cloudsc_*_run_advance); 0: not given */
   int place;                      /* placement search: 1 on, 0 off, -1 auto (on when reps > 1) */
   int narrow_pack;                /* NPROMA <= 32 packed into full waves: 1 on, 0 off, -1 the library's default */
   double energy_s;                /* --energy: seconds of back-to-back launches sampled for board power */
@@ -81,6 +82,7 @@ typedef struct {
   int cml;                        /* --fields tendbuf-cml: inplace, the step adding its tendencies to a zeroed BUFFER_CML (no BUFFER_LOC) */
   int outputs;                    /* --outputs: CLOUDSC_OUTPUTS_* */
   int spp;                        /* --spp unit: cloudsc_gpu_run_spp with five all-ones multiplier fields */
+  int advance;                    /* --advance N: the timed steps are N cloudsc_gpu_run_advance in place */
   double energy_s;
   long long col_offset;
   const cloudsc_template_t *tmpl;
@@ -166,6 +168,12 @@ static void usage(const char *prog) {
           "  --spp unit            the step through the per-column multiplier form (cloudsc_gpu_run_spp with --fields\n"
           "                        caller|levels, kseg or kcache, --outputs all|prognostic; cloudsc_cpu_run_spp with\n"
           "                        --variant cpu) on five all-ones fields: the bits of the step without the flag\n"
+          "  --advance N           N >= 1 advancing steps in place instead of the timed steps: pt, pq, pa, pclv of the\n"
+          "                        set are rewritten by each (cloudsc_gpu_run_advance with --fields caller, kseg or\n"
+          "                        kcache, --outputs all|surface; cloudsc_cpu_run_advance with --variant cpu).  With\n"
+          "                        N = 1 the fluxes, PCOVPTOT, PLUDE and PRAINFRAC_TOPRFZ are validated, the tendencies\n"
+          "                        are not stored and have no row; with N > 1 nothing is validated.  One ADVANCE line\n"
+          "                        follows the table: the steps taken and the time per step\n"
           "  --transfer            host-buffer path: block-layout arrays in host memory,\n"
           "                        H2D -> kernel -> D2H per chunk, overlapped on streams\n"
           "                        (TOTAL includes the transfers, like cloudsc_driver.cu)\n"
@@ -261,6 +269,13 @@ static int parse(int argc, char **argv, options_t *o) {
       NEEDV();
       if (!strcmp(v, "unit")) o->spp = 1;
       else { fprintf(stderr, "bad --spp %s\n", v); return -1; }
+    }
+    else if (!strcmp(a, "--advance")) {
+      NEEDV();
+      char *end;
+      const long n = strtol(v, &end, 10);
+      if (*end || n < 1 || n > 100000) { fprintf(stderr, "bad --advance %s\n", v); return -1; }
+      o->advance = (int)n;
     }
     else if (!strcmp(a, "--fp32-exact-libm")) o->exact_libm = 1;
     else if (!strcmp(a, "--chunk")) { NEEDV(); o->chunk_blocks = atoi(v); }
@@ -407,6 +422,11 @@ static void *hip_sym(const char *name) {
 /* one step of a --fields caller | tendbuf shard on the field set f (tendbuf: its tendencies in the buffers) */
 static int caller_step(const shard_t *s, int variant, int klev, const cloudsc_fields_t *f, void *ws,
                        const cloudsc_tend_cml_t *cml, const cloudsc_spp_t *spp) {
+  if (s->advance) {                                      /* --advance N: in place */
+    const cloudsc_advance_t adv = {(void *)f->pt, (void *)f->pq, (void *)f->pa, (void *)f->pclv};
+    return cloudsc_gpu_run_advance(s->device, NULL, s->precision, variant, s->outputs, s->ngptot, s->nproma, klev, f, &adv,
+                                   ws);
+  }
   if (s->spp)                                            /* --spp unit */
     return cloudsc_gpu_run_spp(s->device, NULL, s->precision, variant, s->outputs, s->ngptot, s->nproma, klev, f, spp,
                                ws);
@@ -573,13 +593,15 @@ static void shard_caller(shard_t *s) {
   if (!s->rc && s->levels) s->rc = levels_convert(s, klev, 1, &f, s->nproma, &lev, 0);
   if (!s->rc && s->levels) s->rc = levels_convert(s, klev, 1, &lev, 0, &stage, s->nproma);
   const cloudsc_fields_t *vf = s->levels ? &stage : &f;   /* the separate arrays the validation reads */
-  if (!s->rc && s->ref && (inplace || s->outputs != CLOUDSC_OUTPUTS_ALL)) {
+  int member[CLOUDSC_NVALID];
+#define VALID_MEMBER(n, N, k, d, i) CLOUDSC_IF_VALIDATED_##d(member[CLOUDSC_F_##N] = CLOUDSC_M_##n;)
+  CLOUDSC_FIELDS(VALID_MEMBER)
+#undef VALID_MEMBER
+  if (s->advance > 1) {   /* --advance N > 1: nothing has a reference after more than one step */
+    for (int id = 0; id < CLOUDSC_NVALID; id++) s->skipped[id] = 1;
+  } else if (!s->rc && s->ref && (inplace || s->outputs != CLOUDSC_OUTPUTS_ALL)) {
     /* in place: BUFFER_LOC itself.  A prognostic set: the fields cloudsc_fields_alloc_outputs allocated -- the
      * library's selection, read off the set: a validated member it left NULL has no reference array either */
-    int member[CLOUDSC_NVALID];
-#define VALID_MEMBER(n, N, k, d, i) CLOUDSC_IF_VALIDATED_##d(member[CLOUDSC_F_##N] = CLOUDSC_M_##n;)
-    CLOUDSC_FIELDS(VALID_MEMBER)
-#undef VALID_MEMBER
     cloudsc_reference_t ref = *s->ref;
     if (s->cml) {   /* 0 + loc: the cumulative planes validate as tendency_loc_* (the untouched vapour plane as zeros) */
       g.tendency_loc_t = cml.t; g.tendency_loc_a = cml.a; g.tendency_loc_q = cml.q; g.tendency_loc_cld = cml.cld;
@@ -591,6 +613,9 @@ static void shard_caller(shard_t *s) {
   } else if (!s->rc && s->ref)
     s->rc = cloudsc_fields_validate(s->device, NULL, s->precision, s->ngptot, s->nproma, klev, s->col_offset, vf, s->ref,
                                     s->stats);
+  /* --advance: the local tendencies are not stored (their arrays hold what the allocation left): no row, not gated */
+  for (int id = 0; s->advance && id < CLOUDSC_NVALID; id++)
+    if (member[id] >= CLOUDSC_M_tendency_loc_t && member[id] <= CLOUDSC_M_tendency_loc_cld) s->skipped[id] = 1;
   if (s->rc) snprintf(s->err, sizeof(s->err), "%s", cloudsc_last_hip_error());
   if (ws) dfree(ws);
   if (buf_tmp) dfree(buf_tmp);
@@ -664,7 +689,8 @@ static int run_host(const options_t *o, const cloudsc_dataset_t *ds) {
   const int cpu = o->variant == VARIANT_CPU;
   const int es = precision_bytes(o->precision);
   /* the zinfo record: cloudsc_cpu_run_threads, fp64 (cloudsc_cpu_run_outputs, --outputs surface, keeps none) */
-  const int per_thread = cpu && o->precision == CLOUDSC_FP64 && o->outputs != CLOUDSC_OUTPUTS_SURFACE && !o->spp;
+  const int per_thread = cpu && o->precision == CLOUDSC_FP64 && o->outputs != CLOUDSC_OUTPUTS_SURFACE && !o->spp &&
+                         !o->advance;
   const int nb = o->ngptot / o->nproma + (o->ngptot % o->nproma ? 1 : 0);
   const int aer = ds->params.laericesed || ds->params.laericeauto;
   cloudsc_fields_t f;
@@ -739,7 +765,12 @@ static int run_host(const options_t *o, const cloudsc_dataset_t *ds) {
     double ms = 0.0;
     if (cpu) {
       double secs = 0.0;
-      if (o->spp) {
+      if (o->advance) {   /* --advance N: in place */
+        const cloudsc_advance_t adv = {(void *)f.pt, (void *)f.pq, (void *)f.pa, (void *)f.pclv};
+        const double t0 = now();
+        rc = cloudsc_cpu_run_advance(nth, o->precision, o->outputs, o->ngptot, o->nproma, ds->klev, &ds->params, &f, &adv);
+        secs = now() - t0;
+      } else if (o->spp) {
         const double t0 = now();
         rc = cloudsc_cpu_run_spp(nth, o->precision, o->outputs, o->ngptot, o->nproma, ds->klev, &ds->params, &f, &spp);
         secs = now() - t0;
@@ -795,6 +826,10 @@ static int run_host(const options_t *o, const cloudsc_dataset_t *ds) {
         int kind = cloudsc_io_ref_kind[v];
         const double *refv = ds->ref[v];
         if (!fp[k_valid_field[v]]) continue;   /* --outputs surface: not allocated, not computed: no row */
+        /* --advance: the tendencies are not stored; after more than one step nothing has a reference */
+        if (o->advance > 1 || (o->advance && k_valid_field[v] >= CLOUDSC_M_tendency_loc_t &&
+                               k_valid_field[v] <= CLOUDSC_M_tendency_loc_cld))
+          continue;
         if (surface && k_valid_field[v] >= CLOUDSC_M_pfplsl && k_valid_field[v] <= CLOUDSC_M_pfhpsn) {
           refv += (size_t)ds->klev * ds->klon;   /* the surface row of the reference profile */
           kind = CLOUDSC_FK_SURFACE;
@@ -813,6 +848,9 @@ static int run_host(const options_t *o, const cloudsc_dataset_t *ds) {
         printf(" VALIDATION: reported only (%s vs the fp64 reference; worst relative L1 error %.3e)\n",
                precision_name(o->precision), worst);
     }
+    if (o->advance)
+      printf(" ADVANCE: steps=%d ms_per_step=%.4f in place (cloudsc_cpu_run_advance: pt, pq, pa, pclv rewritten)%s\n",
+             o->advance, total_ms / o->reps, o->advance > 1 ? "; nothing validated after more than one step" : "");
   } else {
     fprintf(stderr, "dwarf-cloudsc-amd %s: %s (%s)\n", cpu ? "--variant cpu" : "--transfer", cloudsc_strerror(rc),
             cloudsc_last_hip_error());
@@ -919,6 +957,24 @@ int main(int argc, char **argv) {
       return EXIT_FAILURE;
     }
   }
+  /* --advance: the advancing form exists for --fields caller on kseg|kcache and for --variant cpu, with the
+   * outputs all|surface: everything else is a usage error, never another step in its place.  Its N steps are the
+   * timed steps: no warm-up step moves the state first */
+  if (o.advance) {
+    const int cpu = o.variant == VARIANT_CPU;
+    const int gpu_ok = o.fields_caller == 1 && !o.fields_levels &&
+                       (o.variant == CLOUDSC_VARIANT_KSEG || o.variant == CLOUDSC_VARIANT_KCACHE);
+    if (o.transfer || o.exact_libm || o.spp || o.outputs == CLOUDSC_OUTPUTS_PROGNOSTIC || o.energy_s > 0.0 ||
+        (cpu ? o.fields_caller != 0 : !gpu_ok)) {
+      fprintf(stderr, "dwarf-cloudsc-amd: --advance goes with --fields caller and --variant kseg|kcache, or with "
+                      "--variant cpu (--outputs all|surface; no --transfer, --fp32-exact-libm, --spp, --energy, no "
+                      "tendency buffers)\n");
+      cloudsc_io_free(&ds);
+      return EXIT_FAILURE;
+    }
+    o.reps = o.advance;
+    o.warmup = 0;
+  }
   if (o.fields_caller >= 2 && !o.tend_planes) o.tend_planes = CLOUDSC_TENDBUF_PLANES_MIN;
   if (o.fields_caller && (o.transfer || o.variant == VARIANT_CPU)) {
     fprintf(stderr, "dwarf-cloudsc-amd: --fields caller runs the GPU variants on device fields (no --transfer, no "
@@ -1012,6 +1068,7 @@ int main(int argc, char **argv) {
     s->cml = o.fields_caller == 4;
     s->outputs = o.outputs;
     s->spp = o.spp;
+    s->advance = o.advance;
     s->aerosols = ds.params.laericesed || ds.params.laericeauto;
     s->tmpl = &tmpl; s->params = &ds.params; s->ref = ds.has_reference ? &ref : NULL; s->barrier = &bar;
     s->kernel_ms = (float *)calloc((size_t)o.reps, sizeof(float));
@@ -1141,6 +1198,9 @@ int main(int argc, char **argv) {
   } else {
     printf(" VALIDATION: skipped (no reference outputs loaded)\n");
   }
+  if (o.advance)
+    printf(" ADVANCE: steps=%d ms_per_step=%.4f in place (cloudsc_gpu_run_advance: pt, pq, pa, pclv rewritten)%s\n",
+           o.advance, kmax, o.advance > 1 ? "; nothing validated after more than one step" : "");
   for (int d = 0; d < nused; d++) free(sh[d].kernel_ms);
   free(sh);
   free(th);

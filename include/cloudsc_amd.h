@@ -756,6 +756,106 @@ int cloudsc_cpu_run_spp(int nthreads, int precision, int outputs, int ngptot, in
                         const cloudsc_params_t *params, const cloudsc_fields_t *host_fields,
                         const cloudsc_spp_t *spp);
 
+/* ------------------------------------------------------------------------ */
+/* The advancing step: state in, state out                                   */
+/* ------------------------------------------------------------------------ */
+/* Hosts whose microphysics interface is "state in, state out, plus surface
+ * precipitation" (level-contiguous (ncol, nlev) drivers that come in through
+ * cloudsc_fields_convert_layout) have no use for the seven local tendencies:
+ * they want the updated prognostics.  The entry points below store those
+ * instead -- fused into the step (cloudsc_gpu_run_advance: seven state stores
+ * per level replace the eight tendency stores, the vapour tendency's zeros
+ * among them; no input is read twice), or as a streaming
+ * pass over a set whose tendency_loc_* a step has filled
+ * (cloudsc_fields_advance).  An advancing step can be called on its own output:
+ * N calls integrate N time steps, with nothing in between but whatever the host
+ * does to tendency_tmp_*.
+ *
+ * The definition.  For the seven advanced quantities X in {t, q, a, cld[0..3]},
+ * with X the state member (pt, pq, pa, pclv[m]), tmp the incoming tendency
+ * (tendency_tmp_*) and loc what the ordinary step of the same precision stores
+ * in tendency_loc_* at that element:
+ *   X0    = fl( X  + fl(ptsphy * tmp) )     the step's own starting value
+ *   X_new = fl( X0 + fl(ptsphy * loc) )     one multiply, one add, each rounded
+ *                                           on its own (no multiply-add)
+ * in the working type: double for CLOUDSC_FP64 and CLOUDSC_MIXED, float for
+ * CLOUDSC_FP32.  In CLOUDSC_MIXED the fused form takes loc as the double the
+ * kernel holds BEFORE its narrowing store, so that the mixed identity out =
+ * (float) fp64_form((double) in) extends to the new state bit for bit; the
+ * separate pass can only take the stored, narrowed float (widened exactly), so
+ * in mixed the two differ in the last bit of some elements.  In fp64 and fp32
+ * they are equal bit for bit.
+ * Every level is advanced, the levels above NCLDTOP included (there loc is what
+ * the step stores there, X + ptsphy * tmp is still applied, and a -0 state
+ * becomes +0).  Nothing is clipped and no conservation fix-up is made: a
+ * slightly negative q is the caller's concern, as it is with the tendencies.
+ * The fifth (vapour) plane behind adv->clv is never written (its tendency is
+ * identically zero and the step never reads pclv's), nor are the padding lanes
+ * of a partial last block.
+ *
+ * The four members are arrays in block layout and the set's storage type: t, q
+ * and a [nblocks][klev][nproma], clv [nblocks][5][klev][nproma].  Each may be
+ * the set's own pt / pq / pa / pclv (in place) or another array, independently
+ * of the other three.  It may be no other member of the set and none of the
+ * other three (pointer equality only: overlapping arrays are the caller's to
+ * avoid). */
+typedef struct cloudsc_advance { void *t, *q, *a, *clv; } cloudsc_advance_t;   /* block layout, storage type of the set */
+
+/* cloudsc_gpu_run_outputs with the updated prognostics stored in place of the
+ * local tendencies.  tendency_loc_t/q/a/cld of device_fields are neither read
+ * nor written: they may be NULL, and a non-NULL one keeps every byte.  Every
+ * other selected output (plude, pcovptot, prainfrac_toprfz, the fluxes of the
+ * selection) has the ordinary step's bits.
+ * In place is safe because every state element is loaded by the one lane that
+ * later stores it, at its own level, before that store: pt, pq, pa and pclv are
+ * read at row k only, and what level k needs of its neighbours travels in the
+ * carried state (store_level_adv, cloudsc_kcache.h, has the argument for the
+ * prefetch schedules, the KSEG hand-off and the packed form).
+ * `outputs` is CLOUDSC_OUTPUTS_ALL or CLOUDSC_OUTPUTS_SURFACE (new state plus
+ * surface precipitation); CLOUDSC_OUTPUTS_PROGNOSTIC alone is refused.  KCACHE
+ * and KSEG, fp64, fp32 (default exp/pow) and mixed, with and without aerosols,
+ * packed and unpacked narrow blocks; one KSEG workspace serves this form and
+ * all others in any order.  The tendency-buffer, cumulative-tendency and
+ * per-column multiplier forms have no advancing twin; the device-resident
+ * state, the host pipelines and the drop-in do not have the form.
+ * CLOUDSC_EINVAL, all checked before the first HIP call: a NULL adv or a NULL
+ * member of it, a member that breaks the aliasing rule above,
+ * CLOUDSC_OUTPUTS_PROGNOSTIC or an unknown `outputs` value, CLOUDSC_VARIANT_SCC,
+ * CLOUDSC_VARIANT_SCC_PRIVATE, the option bit CLOUDSC_FP32_EXACT_LIBM and every
+ * argument error of cloudsc_gpu_run_outputs (tendency_loc_* excepted). */
+int cloudsc_gpu_run_advance(int device, void *stream, int precision, int variant, int outputs,
+                            int ngptot, int nproma, int klev,
+                            const cloudsc_fields_t *device_fields, const cloudsc_advance_t *adv, void *scratch);
+
+/* The host twin, on HOST memory through the same phase functions, fp64 and
+ * mixed as the other host forms (CLOUDSC_FP32: CLOUDSC_EINVAL): the same
+ * contract.  Needs no GPU. */
+int cloudsc_cpu_run_advance(int nthreads, int precision, int outputs, int ngptot, int nproma, int klev,
+                            const cloudsc_params_t *params, const cloudsc_fields_t *host_fields,
+                            const cloudsc_advance_t *adv);
+
+/* The separate pass, for callers that want tendencies AND state: the two lines
+ * of the definition over a set whose tendency_loc_* a step has filled, with loc
+ * the stored element.  Arithmetic in double for CLOUDSC_FP64 and CLOUDSC_MIXED
+ * (float elements are widened exactly, the result narrowed by one conversion),
+ * in float for CLOUDSC_FP32.  ptsphy is the one of the device's parameter set
+ * (cloudsc_gpu_init).  Only pt, pq, pa, pclv, tendency_tmp_* and tendency_loc_*
+ * of device_fields are looked at; the aliasing rule is the one above; vapour
+ * planes and padding lanes are neither read nor written.  One streaming launch
+ * through the field set item walker, asynchronous in `stream`, no workspace.
+ * CLOUDSC_EINVAL (before the first HIP call): an unknown precision, ngptot,
+ * nproma or klev < 1, nproma > 2^24, a NULL argument, one of the twelve members
+ * or an adv member NULL, the aliasing rule.  CLOUDSC_ENODEV: no such device.
+ * CLOUDSC_ENOINIT: cloudsc_gpu_init not called for the device. */
+int cloudsc_fields_advance(int device, void *stream, int precision, int ngptot, int nproma, int klev,
+                           const cloudsc_fields_t *device_fields, const cloudsc_advance_t *adv);
+
+/* The same on HOST arrays with ptsphy from `params`, bit for bit, in all three
+ * precisions.  Needs no GPU. */
+int cloudsc_cpu_fields_advance(int nthreads, int precision, int ngptot, int nproma, int klev,
+                               const cloudsc_params_t *params, const cloudsc_fields_t *host_fields,
+                               const cloudsc_advance_t *adv);
+
 /* cloudsc_fields_alloc for an output selection.  With CLOUDSC_OUTPUTS_ALL it is
  * cloudsc_fields_alloc.  With CLOUDSC_OUTPUTS_PROGNOSTIC the ten diagnostic
  * members are not allocated and stay NULL (10 * (klev + 1) elements per column
