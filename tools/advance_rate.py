@@ -23,18 +23,14 @@ reads nothing twice, so by bytes (a)/(b) is 1.00 or just below.  The pass reads 
 level, 28 of a step's about 56 element planes, and is a second launch: (c)/(b) should be near 1.5 and (a)/(c)
 near 0.65.  Nothing here is a pass/fail bound."""
 import argparse
-import ctypes as C
+import contextlib
 import json
-import os
-import statistics
 import sys
-import time
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(os.path.dirname(HERE), "dwarf-p-cloudsc_amd"))
-import cloudsc_amd as ca  # noqa: E402
+import rate_harness as rh
+from rate_harness import ca
 
 
 def main():
@@ -48,20 +44,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=5)
     o = ap.parse_args()
-    prec = {"fp64": ca.FP64, "mixed": ca.MIXED, "fp32": ca.FP32}[o.precision]
-    outputs = {"all": ca.OUTPUTS_ALL, "surface": ca.OUTPUTS_SURFACE}[o.outputs]
-    lib, hip = ca.gpu_lib(), ca._hip()
-    hip.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
+    prec, outputs = rh.PRECISION[o.precision], rh.OUTPUTS[o.outputs]
+    lib, hip = ca.gpu_lib(), rh.hip_api()
     if o.what != "b" and not hasattr(lib, "cloudsc_gpu_run_advance"):
         sys.exit("this library has no advancing step (only --what b runs on it)")
     ds = ca.load_dataset()
-    p = ca.Params.from_dict(ds.params)
-    ca.check(lib.cloudsc_gpu_init(0, C.byref(p)))
+    rh.gpu_init(lib, ds)
     d = ca.DeviceFields(o.ngptot, o.nproma, ds.klev, prec, outputs=outputs)
-    ws = C.c_void_p()
-    try:
-        wsb = lib.cloudsc_gpu_scratch_bytes(prec, ca.VARIANT_KSEG, o.ngptot, o.nproma, ds.klev)
-        assert hip.hipMalloc(C.byref(ws), C.c_size_t(wsb)) == 0 and hip.hipMemset(ws, 0, C.c_size_t(256)) == 0
+    with contextlib.closing(d), rh.kseg_workspace(lib, hip, prec, ca.VARIANT_KSEG, o.ngptot, o.nproma, ds.klev) as ws:
         args = (prec, ca.VARIANT_KSEG, outputs, o.ngptot, o.nproma, ds.klev)
         if o.what == "b":
             def step():
@@ -76,28 +66,10 @@ def main():
                     ca.gpu_run_outputs(d.f, *args, scratch=ws)
                     ca.advance_fields(d.f, adv, prec, o.ngptot, o.nproma, ds.klev)
         d.expand(ds)
-        for _ in range(o.warmup):
-            step()
-        ca.check(lib.cloudsc_gpu_check(0, None, ca.VARIANT_KSEG, ws))
-        ms = []
-        for _ in range(o.rounds):
-            d.expand(ds)
-            hip.hipDeviceSynchronize()
-            t0 = time.perf_counter()
-            for _ in range(o.steps):
-                step()
-            hip.hipDeviceSynchronize()
-            ms.append(1e3 * (time.perf_counter() - t0) / o.steps)
-        ca.check(lib.cloudsc_gpu_check(0, None, ca.VARIANT_KSEG, ws))
+        ms = rh.what_rounds(hip, step, o, rh.launch_check(lib, ca.VARIANT_KSEG, ws), before_round=lambda: d.expand(ds))
         finite = all(bool(np.isfinite(d.download_raw(k)[:o.ngptot // o.nproma]).all()) for k in ("pt", "pq", "pa", "pclv"))
-        print(json.dumps({"what": o.what, "precision": o.precision, "outputs": o.outputs, "ngptot": o.ngptot,
-                          "nproma": o.nproma, "steps": o.steps, "rounds": o.rounds, "finite": finite,
-                          "lib": "CLOUDSC_AMD_LIB" if os.environ.get("CLOUDSC_AMD_LIB") else "this build",
-                          "ms_per_step": [round(x, 4) for x in ms], "median_ms": round(statistics.median(ms), 4)}))
-    finally:
-        if ws.value:
-            hip.hipFree(ws)
-        d.close()
+        keys = ("what", "precision", "outputs", "ngptot", "nproma", "steps", "rounds", "finite")
+        print(json.dumps(rh.what_record(o, ms, keys, finite=finite)))
 
 
 if __name__ == "__main__":

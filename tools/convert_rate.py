@@ -11,14 +11,11 @@ bytes written, counted from the shapes (active columns only), over the time of o
 line per measurement.  Needs an MI355X; there is no CPU form of a rate."""
 import argparse
 import ctypes as C
-import json
-import os
-import sys
 
 import numpy as np
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "dwarf-p-cloudsc_amd"))
-import cloudsc_amd as ca  # noqa: E402
+import rate_harness as rh
+from rate_harness import ca
 
 INPUTS = list(ca.INPUT_FIELDS) + list(ca.INOUT_FIELDS)
 OUTPUTS = [k for _, k in ca.VALIDATED]
@@ -34,26 +31,6 @@ def moved_bytes(names, ngptot, klev, sp, dp):
     return total
 
 
-class Timer:
-    def __init__(self, hip):
-        self.hip = hip
-        self.e0, self.e1 = C.c_void_p(), C.c_void_p()
-        assert hip.hipEventCreate(C.byref(self.e0)) == 0 and hip.hipEventCreate(C.byref(self.e1)) == 0
-
-    def ms_per_launch(self, launch, reps, warmup=2):
-        for _ in range(warmup):
-            launch()
-        assert self.hip.hipDeviceSynchronize() == 0
-        assert self.hip.hipEventRecord(self.e0, None) == 0
-        for _ in range(reps):
-            launch()
-        assert self.hip.hipEventRecord(self.e1, None) == 0
-        assert self.hip.hipEventSynchronize(self.e1) == 0
-        ms = C.c_float()
-        assert self.hip.hipEventElapsedTime(C.byref(ms), self.e0, self.e1) == 0
-        return ms.value / reps
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ngptot", type=int, default=163840)
@@ -65,16 +42,9 @@ def main():
     klev = ds.klev
     if ca.device_count() < 1:
         raise SystemExit("convert_rate: no HIP device")
-    hip = ca._hip()
-    timer = Timer(hip)
-    lines = []
-
-    def emit(rec):
-        lines.append(rec)
-        print(json.dumps(rec), flush=True)
-
-    stream = ca.hbm_copy_gbps(0, 4 << 30, 10)
-    emit({"measure": "stream_copy", "gbps": round(stream, 1)})
+    hip = rh.hip_api()
+    timer, records = rh.SpanTimer(hip), rh.Records()
+    stream = records.stream_copy()
 
     # (label, src precision, src nproma, dst precision, dst nproma)
     cases = [("fp64 32->64", ca.FP64, 32, ca.FP64, 64), ("fp64 64->64", ca.FP64, 64, ca.FP64, 64),
@@ -92,9 +62,10 @@ def main():
                 nbytes = moved_bytes(names, n, klev, sp, dp)
                 gbps = nbytes / (ms * 1e-3) / 1e9
                 ms_of[(label, part)] = ms
-                emit({"measure": "convert", "case": label, "set": part, "ngptot": n, "klev": klev,
-                      "src": [PREC[sp], snp], "dst": [PREC[dp], dnp], "moved_bytes": nbytes, "ms": round(ms, 4),
-                      "gbps": round(gbps, 1), "of_stream_copy": round(gbps / stream, 3), "reps": args.reps})
+                records.emit({"measure": "convert", "case": label, "set": part, "ngptot": n, "klev": klev,
+                              "src": [PREC[sp], snp], "dst": [PREC[dp], dnp], "moved_bytes": nbytes,
+                              "ms": round(ms, 4), "gbps": round(gbps, 1), "of_stream_copy": round(gbps / stream, 3),
+                              "reps": args.reps})
         finally:
             a.close()
             b.close()
@@ -114,15 +85,11 @@ def main():
     k32 = kseg_ms(32, 1)
     geo = ca.launch_geometry(ca.FP64, ca.VARIANT_KSEG, n, 32, klev)
     t_in, t_out = ms_of[("fp64 32->64", "inputs")], ms_of[("fp64 64->32", "outputs")]
-    emit({"measure": "reblock_round_trip", "ngptot": n, "convert_inputs_32_to_64_ms": round(t_in, 4),
-          "kseg_fp64_nproma64_ms": round(k64, 4), "convert_outputs_64_to_32_ms": round(t_out, 4),
-          "sum_ms": round(t_in + k64 + t_out, 4), "kseg_fp64_nproma32_packed_ms": round(k32, 4),
-          "nproma32_default_pack": geo["pack"]})
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            for rec in lines:
-                fh.write(json.dumps(rec) + "\n")
+    records.emit({"measure": "reblock_round_trip", "ngptot": n, "convert_inputs_32_to_64_ms": round(t_in, 4),
+                  "kseg_fp64_nproma64_ms": round(k64, 4), "convert_outputs_64_to_32_ms": round(t_out, 4),
+                  "sum_ms": round(t_in + k64 + t_out, 4), "kseg_fp64_nproma32_packed_ms": round(k32, 4),
+                  "nproma32_default_pack": geo["pack"]})
+    records.write(args.out)
 
 
 if __name__ == "__main__":

@@ -15,16 +15,12 @@ operands (validate: the set's elements; the 100-column reference stays in the ca
 shapes, active columns only.  One JSON line per measurement.  Needs an MI355X."""
 import argparse
 import ctypes as C
-import json
-import os
-import sys
 import time
 
 import numpy as np
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "dwarf-p-cloudsc_amd"))
-import cloudsc_amd as ca  # noqa: E402
-from convert_rate import Timer  # noqa: E402
+import rate_harness as rh
+from rate_harness import ca
 
 OUTPUTS = [k for _, k in ca.VALIDATED]
 PREC = {ca.FP64: "fp64", ca.MIXED: "float-stored"}
@@ -50,16 +46,10 @@ def main():
     klev = ds.klev
     if ca.device_count() < 1:
         raise SystemExit("fields_compare_rate: no HIP device")
-    lib, hip = ca.gpu_lib(), ca._hip()
-    timer = Timer(hip)
-    lines = []
-
-    def emit(rec):
-        lines.append(rec)
-        print(json.dumps(rec), flush=True)
-
-    stream = ca.hbm_copy_gbps(0, 4 << 30, 10)
-    emit({"measure": "stream_copy", "gbps": round(stream, 1), "expected_of_stream_copy": EXPECTED})
+    lib, hip = ca.gpu_lib(), rh.hip_api()
+    timer, records = rh.SpanTimer(hip), rh.Records()
+    emit = records.emit
+    stream = records.stream_copy(expected_of_stream_copy=EXPECTED)
 
     def fill(df):
         for name in OUTPUTS:
@@ -128,11 +118,7 @@ def main():
     finally:
         g.close()
         lib.cloudsc_set_placement_search(-1)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            for rec in lines:
-                fh.write(json.dumps(rec) + "\n")
+    records.write(args.out)
 
 
 if __name__ == "__main__":

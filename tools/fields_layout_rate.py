@@ -31,15 +31,12 @@ fewer bytes in about the same time per element, so their GB/s should be lower th
 Needs an MI355X; there is no CPU form of a rate."""
 import argparse
 import ctypes as C
-import json
-import os
-import sys
 
 import numpy as np
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "dwarf-p-cloudsc_amd"))
-import cloudsc_amd as ca  # noqa: E402
-from convert_rate import INPUTS, OUTPUTS, PREC, Timer, moved_bytes  # noqa: E402
+import rate_harness as rh
+from convert_rate import INPUTS, OUTPUTS, PREC, moved_bytes
+from rate_harness import ca
 
 L, B = ca.LAYOUT_LEVELS, ca.LAYOUT_BLOCKED
 
@@ -59,13 +56,9 @@ def main():
     klev = ds.klev
     if ca.device_count() < 1:
         raise SystemExit("fields_layout_rate: no HIP device")
-    hip = ca._hip()
-    timer = Timer(hip)
-    lines = []
-
-    def emit(rec):
-        lines.append(rec)
-        print(json.dumps(rec), flush=True)
+    hip = rh.hip_api()
+    timer, records = rh.SpanTimer(hip), rh.Records()
+    emit = records.emit
 
     def sets(sp, sl, snp, dp, dl, dnp):
         a = ca.DeviceFields(n, snp, klev, sp, place=False, layout=sl)
@@ -95,8 +88,7 @@ def main():
                 rec["%s_%s_ms" % (label, part)] = round(r[part][0], 4)
         emit(rec)
     else:
-        stream = ca.hbm_copy_gbps(0, 4 << 30, 10)
-        emit({"measure": "stream_copy", "gbps": round(stream, 1)})
+        stream = records.stream_copy()
         plain = measure(ca.FP64, B, 64, ca.FP64, B, 64)
         for part in ("inputs", "outputs"):
             ms, nbytes, gbps = plain[part]
@@ -128,11 +120,7 @@ def main():
               "convert_inputs_l2b_ms": round(ms_of[("fp64 L->B(64)", "inputs")], 4),
               "kseg_fp64_nproma64_ms": round(k64, 4),
               "convert_outputs_b2l_ms": round(ms_of[("fp64 B(64)->L", "outputs")], 4)})
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "a" if args.ab else "w") as fh:
-            for rec in lines:
-                fh.write(json.dumps(rec) + "\n")
+    records.write(args.out, append=args.ab)
 
 
 if __name__ == "__main__":

@@ -38,55 +38,19 @@ EXPECTATION, written before the first run (nobody had measured any of this):
   search, so a difference of up to a few per cent either way would be placement, not the kernel.
   A (b)/(a) below 0.93 would be the surprise and would say that stores cost more than their bytes."""
 import argparse
+import contextlib
 import ctypes as C
-import json
-import os
-import sys
 
 import numpy as np
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "dwarf-p-cloudsc_amd"))
-import cloudsc_amd as ca  # noqa: E402
+import rate_harness as rh
+from rate_harness import ca
 
-PRECISIONS = [("fp64", ca.FP64), ("mixed", ca.MIXED), ("fp32", ca.FP32)]
 EXPECTATION = {"stores_ratio": 0.58, "bytes_ratio": 0.80, "expected": "a few per cent",
                "b_over_a_fp64": "0.95 to 0.99", "b_over_a_float_storage": "the same or closer to 1",
                "c_over_b": "1 within the spread of the rounds and of placements (a few per cent)",
                "surprise": "b_over_a below 0.93",
                "why": "see the EXPECTATION paragraph of tools/outputs_rate.py (DESIGN 3.12, 3.16.4, 3.17)"}
-
-
-class SpanTimer:
-    """One launch between two events on the default stream, waited for: milliseconds."""
-
-    def __init__(self, hip):
-        self.hip = hip
-        self.e0, self.e1 = C.c_void_p(), C.c_void_p()
-        assert hip.hipEventCreate(C.byref(self.e0)) == 0 and hip.hipEventCreate(C.byref(self.e1)) == 0
-
-    def ms(self, launch):
-        assert self.hip.hipEventRecord(self.e0, None) == 0
-        launch()
-        assert self.hip.hipEventRecord(self.e1, None) == 0
-        assert self.hip.hipEventSynchronize(self.e1) == 0
-        ms = C.c_float()
-        assert self.hip.hipEventElapsedTime(C.byref(ms), self.e0, self.e1) == 0
-        return ms.value
-
-
-def summary(v):
-    return {"median_ms": round(float(np.median(v)), 4), "min_ms": round(float(np.min(v)), 4),
-            "max_ms": round(float(np.max(v)), 4)}
-
-
-def column_bytes(klev, es, outputs):
-    """Bytes one column moves in a step: every input read once, every selected output written once."""
-    rows = {"2d": klev, "2dh": klev + 1, "3d": ca.NCLV * klev, "1d": 1}
-    read = sum(rows[k] * (4 if n == "ktype" else es) for n, k in {**ca.INPUT_FIELDS, **ca.INOUT_FIELDS}.items())
-    read -= klev * es                       # tendency_tmp_cld, pclv: four of the five species planes are read
-    read -= klev * es
-    written = sum(rows[ca.ALL_FIELDS[n]] * es for n in ca.selected_outputs(outputs))
-    return read + written
 
 
 def main():
@@ -100,34 +64,13 @@ def main():
     n, nproma = args.ngptot, args.nproma
     ds = ca.load_dataset()
     klev = ds.klev
-    if ca.device_count() < 1:
-        raise SystemExit("outputs_rate: no HIP device")
-    lib, hip = ca.gpu_lib(), ca._hip()
-    hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
-    hip.hipEventRecord.argtypes = [C.c_void_p, C.c_void_p]
-    hip.hipEventSynchronize.argtypes = [C.c_void_p]
-    hip.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
-    timer = SpanTimer(hip)
-    lines = []
+    lib, hip, timer, records, stream = rh.begin("outputs_rate", ds, EXPECTATION)
 
-    def emit(rec):
-        lines.append(rec)
-        print(json.dumps(rec), flush=True)
-
-    emit({"measure": "expectation", **EXPECTATION})
-    stream = ca.hbm_copy_gbps(0, 4 << 30, 10)
-    emit({"measure": "stream_copy", "gbps": round(stream, 1)})
-    p = ca.Params.from_dict(ds.params)
-    ca.check(lib.cloudsc_gpu_init(0, C.byref(p)))
-
-    for label, prec in PRECISIONS:
+    for label, prec in rh.PRECISIONS:
         full = ca.DeviceFields(n, nproma, klev, prec)                                       # 21 outputs, placed
         prog = ca.DeviceFields(n, nproma, klev, prec, outputs=ca.OUTPUTS_PROGNOSTIC)        # eleven, placed
-        ws = C.c_void_p()
-        try:
-            nbytes = lib.cloudsc_gpu_scratch_bytes(prec, ca.VARIANT_KSEG, n, nproma, klev)
-            assert nbytes > 0 and hip.hipMalloc(C.byref(ws), C.c_size_t(nbytes)) == 0
-            assert hip.hipMemset(ws, 0, C.c_size_t(256)) == 0
+        with contextlib.closing(prog), contextlib.closing(full), \
+                rh.kseg_workspace(lib, hip, prec, ca.VARIANT_KSEG, n, nproma, klev) as ws:     # freed: ws, full, prog
             full.expand(ds)
             prog.expand(ds)
 
@@ -140,37 +83,22 @@ def main():
             def run_c():
                 ca.gpu_run_outputs(prog.f, prec, ca.VARIANT_KSEG, ca.OUTPUTS_PROGNOSTIC, n, nproma, klev, scratch=ws)
 
-            cases = [("a", run_a), ("b", run_b), ("c", run_c)]
-            ms = {k: [] for k, _ in cases}
-            for r in range(args.warmup + args.rounds):
-                for k, fn in cases:
-                    t = timer.ms(fn)
-                    ca.check(lib.cloudsc_gpu_check(0, None, ca.VARIANT_KSEG, ws))
-                    if r >= args.warmup:
-                        ms[k].append(t)
+            ms = rh.alternate(timer.ms, [("a", run_a), ("b", run_b), ("c", run_c)], args.rounds, args.warmup,
+                              rh.launch_check(lib, ca.VARIANT_KSEG, ws))
             es = np.dtype(ca.storage_dtype(prec)).itemsize
             rec = {"measure": "kseg_outputs", "precision": label, "ngptot": n, "nproma": nproma, "klev": klev,
                    "rounds": args.rounds, "warmup": args.warmup,
-                   "a_all": summary(ms["a"]), "b_prognostic_same_set": summary(ms["b"]),
-                   "c_prognostic_own_set": summary(ms["c"]),
-                   "column_bytes_all": column_bytes(klev, es, ca.OUTPUTS_ALL),
-                   "column_bytes_prognostic": column_bytes(klev, es, ca.OUTPUTS_PROGNOSTIC),
+                   "a_all": rh.summary(ms["a"]), "b_prognostic_same_set": rh.summary(ms["b"]),
+                   "c_prognostic_own_set": rh.summary(ms["c"]),
+                   "column_bytes_all": rh.column_bytes(klev, es, ca.OUTPUTS_ALL),
+                   "column_bytes_prognostic": rh.column_bytes(klev, es, ca.OUTPUTS_PROGNOSTIC),
                    "placement_full": full.report.to_dict(), "placement_prognostic": prog.report.to_dict()}
             a, b, c = (float(np.median(ms[k])) for k in "abc")
             rec.update({"b_over_a": round(b / a, 4), "c_over_a": round(c / a, 4), "c_over_b": round(c / b, 4),
                         "a_of_stream_copy": round(rec["column_bytes_all"] * n / (a * 1e-3) / 1e9 / stream, 3),
                         "b_of_stream_copy": round(rec["column_bytes_prognostic"] * n / (b * 1e-3) / 1e9 / stream, 3)})
-            emit(rec)
-        finally:
-            if ws.value:
-                hip.hipFree(ws)
-            full.close()
-            prog.close()
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            for rec in lines:
-                fh.write(json.dumps(rec) + "\n")
+            records.emit(rec)
+    records.write(args.out)
 
 
 if __name__ == "__main__":

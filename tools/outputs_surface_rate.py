@@ -30,31 +30,17 @@ EXPECTATION, written before the first run:
   promised: the bar is that (b) is not slower than (a) beyond the spread of (a)'s own rounds.  (c) against (b)
   is a different draw of the placement search: a few per cent either way would be placement, not the kernel."""
 import argparse
-import ctypes as C
-import json
-import os
-import sys
+import contextlib
 
 import numpy as np
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "dwarf-p-cloudsc_amd"))
-import cloudsc_amd as ca  # noqa: E402
-from outputs_rate import SpanTimer, summary  # noqa: E402
+import rate_harness as rh
+from rate_harness import ca
 
-PRECISIONS = [("fp64", ca.FP64), ("mixed", ca.MIXED), ("fp32", ca.FP32)]
 EXPECTATION = {"stores_ratio_vs_prognostic": 0.715, "bytes_ratio_vs_prognostic": 0.903,
                "b_over_a_fp64": "0.95 to 0.97", "b_over_a_float_storage": "closer to 1",
                "bar": "b not slower than a beyond the spread of a's rounds; a neutral result is recorded as such",
                "c_over_b": "1 within the spread of the rounds and of placements (a few per cent)"}
-
-
-def column_bytes(klev, es, outputs):
-    """Bytes one column moves in a step: every input read once, every selected output written once."""
-    read = sum(int(np.prod(ca.field_shape(k, klev, 1))) * (4 if n == "ktype" else es)
-               for n, k in {**ca.INPUT_FIELDS, **ca.INOUT_FIELDS}.items())
-    read -= 2 * klev * es                   # tendency_tmp_cld, pclv: four of the five species planes are read
-    written = sum(int(np.prod(ca.selected_field_shape(n, klev, 1, outputs))) * es for n in ca.selected_outputs(outputs))
-    return read + written
 
 
 def main():
@@ -68,44 +54,19 @@ def main():
     n, nproma = args.ngptot, args.nproma
     ds = ca.load_dataset()
     klev = ds.klev
-    if ca.device_count() < 1:
-        raise SystemExit("outputs_surface_rate: no HIP device")
-    lib, hip = ca.gpu_lib(), ca._hip()
-    hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
-    hip.hipEventRecord.argtypes = [C.c_void_p, C.c_void_p]
-    hip.hipEventSynchronize.argtypes = [C.c_void_p]
-    hip.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
-    timer = SpanTimer(hip)
-    lines = []
+    lib, hip, timer, records, stream = rh.begin("outputs_surface_rate", ds, EXPECTATION)
 
-    def emit(rec):
-        lines.append(rec)
-        print(json.dumps(rec), flush=True)
-
-    emit({"measure": "expectation", **EXPECTATION})
-    stream = ca.hbm_copy_gbps(0, 4 << 30, 10)
-    emit({"measure": "stream_copy", "gbps": round(stream, 1)})
-    p = ca.Params.from_dict(ds.params)
-    ca.check(lib.cloudsc_gpu_init(0, C.byref(p)))
-
-    for label, prec in PRECISIONS:
+    for label, prec in rh.PRECISIONS:
         prog = ca.DeviceFields(n, nproma, klev, prec, outputs=ca.OUTPUTS_PROGNOSTIC)   # eleven outputs, placed
         surf = ca.DeviceFields(n, nproma, klev, prec, outputs=ca.OUTPUTS_SURFACE)      # seven and four small, placed
-        ws = C.c_void_p()
-        small = []
-        try:
-            nbytes = lib.cloudsc_gpu_scratch_bytes(prec, ca.VARIANT_KSEG, n, nproma, klev)
-            assert nbytes > 0 and hip.hipMalloc(C.byref(ws), C.c_size_t(nbytes)) == 0
-            assert hip.hipMemset(ws, 0, C.c_size_t(256)) == 0
+        with contextlib.closing(surf), contextlib.closing(prog), contextlib.ExitStack() as small, \
+                rh.kseg_workspace(lib, hip, prec, ca.VARIANT_KSEG, n, nproma, klev) as ws:     # freed: ws, small, prog, surf
             prog.expand(ds)
             surf.expand(ds)
             # (b): the PROGNOSTIC set's buffers, the four flux members small scratch arrays
             same = ca.fields_subset(prog.f)
             for name in ca.SURFACE_FLUX_FIELDS:
-                q = C.c_void_p()
-                assert hip.hipMalloc(C.byref(q), C.c_size_t(surf.nbytes(name))) == 0
-                small.append(q)
-                setattr(same, name, q.value)
+                setattr(same, name, small.enter_context(rh.device_buffer(hip, surf.nbytes(name))).value)
 
             def run_a():
                 ca.gpu_run_outputs(prog.f, prec, ca.VARIANT_KSEG, ca.OUTPUTS_PROGNOSTIC, n, nproma, klev, scratch=ws)
@@ -116,21 +77,15 @@ def main():
             def run_c():
                 ca.gpu_run_outputs(surf.f, prec, ca.VARIANT_KSEG, ca.OUTPUTS_SURFACE, n, nproma, klev, scratch=ws)
 
-            cases = [("a", run_a), ("b", run_b), ("c", run_c)]
-            ms = {k: [] for k, _ in cases}
-            for r in range(args.warmup + args.rounds):
-                for k, fn in cases:
-                    t = timer.ms(fn)
-                    ca.check(lib.cloudsc_gpu_check(0, None, ca.VARIANT_KSEG, ws))
-                    if r >= args.warmup:
-                        ms[k].append(t)
+            ms = rh.alternate(timer.ms, [("a", run_a), ("b", run_b), ("c", run_c)], args.rounds, args.warmup,
+                              rh.launch_check(lib, ca.VARIANT_KSEG, ws))
             es = np.dtype(ca.storage_dtype(prec)).itemsize
             rec = {"measure": "kseg_outputs_surface", "precision": label, "ngptot": n, "nproma": nproma, "klev": klev,
                    "rounds": args.rounds, "warmup": args.warmup,
-                   "a_prognostic": summary(ms["a"]), "b_surface_same_set": summary(ms["b"]),
-                   "c_surface_own_set": summary(ms["c"]),
-                   "column_bytes_prognostic": column_bytes(klev, es, ca.OUTPUTS_PROGNOSTIC),
-                   "column_bytes_surface": column_bytes(klev, es, ca.OUTPUTS_SURFACE),
+                   "a_prognostic": rh.summary(ms["a"]), "b_surface_same_set": rh.summary(ms["b"]),
+                   "c_surface_own_set": rh.summary(ms["c"]),
+                   "column_bytes_prognostic": rh.column_bytes(klev, es, ca.OUTPUTS_PROGNOSTIC),
+                   "column_bytes_surface": rh.column_bytes(klev, es, ca.OUTPUTS_SURFACE),
                    "placement_prognostic": prog.report.to_dict(), "placement_surface": surf.report.to_dict()}
             a, b, c = (float(np.median(ms[k])) for k in "abc")
             spread_a = (float(np.max(ms["a"])) - float(np.min(ms["a"]))) / a
@@ -138,19 +93,8 @@ def main():
                         "a_spread": round(spread_a, 4), "b_within_bar": bool(b <= a * (1.0 + spread_a)),
                         "a_of_stream_copy": round(rec["column_bytes_prognostic"] * n / (a * 1e-3) / 1e9 / stream, 3),
                         "b_of_stream_copy": round(rec["column_bytes_surface"] * n / (b * 1e-3) / 1e9 / stream, 3)})
-            emit(rec)
-        finally:
-            if ws.value:
-                hip.hipFree(ws)
-            for q in small:
-                hip.hipFree(q)
-            prog.close()
-            surf.close()
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            for rec in lines:
-                fh.write(json.dumps(rec) + "\n")
+            records.emit(rec)
+    records.write(args.out)
 
 
 if __name__ == "__main__":

@@ -24,18 +24,14 @@ With about 2.5 waves per SIMD to hide a load's latency behind, a few per cent wo
 that would say the waits are exposed.  fp32, whose level loop is bound by VALU issue and which keeps its
 parameter block in VGPRs, may pay more than fp64.  Nothing here is a pass/fail bound."""
 import argparse
-import ctypes as C
+import contextlib
 import json
-import os
-import statistics
 import sys
-import time
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(os.path.dirname(HERE), "dwarf-p-cloudsc_amd"))
-import cloudsc_amd as ca  # noqa: E402
+import rate_harness as rh
+from rate_harness import ca
 
 
 def main():
@@ -50,22 +46,16 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--seed", type=int, default=1)
     o = ap.parse_args()
-    prec = {"fp64": ca.FP64, "mixed": ca.MIXED, "fp32": ca.FP32}[o.precision]
-    variant = {"kseg": ca.VARIANT_KSEG, "kcache": ca.VARIANT_KCACHE}[o.variant]
-    lib, hip = ca.gpu_lib(), ca._hip()
-    hip.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
+    prec, variant = rh.PRECISION[o.precision], rh.VARIANT[o.variant]
+    lib, hip = ca.gpu_lib(), rh.hip_api()
     if o.what == "b" and not hasattr(lib, "cloudsc_gpu_run_spp"):
         sys.exit("this library has no per-column multiplier form (only --what a runs on it)")
     ds = ca.load_dataset()
-    p = ca.Params.from_dict(ds.params)
-    ca.check(lib.cloudsc_gpu_init(0, C.byref(p)))
+    rh.gpu_init(lib, ds)
     d = ca.DeviceFields(o.ngptot, o.nproma, ds.klev, prec)
-    mult, ws = [], C.c_void_p()
-    try:
+    with contextlib.closing(d), contextlib.ExitStack() as mult:
         d.expand(ds)
-        wsb = lib.cloudsc_gpu_scratch_bytes(prec, variant, o.ngptot, o.nproma, ds.klev)
-        if wsb > 0:
-            assert hip.hipMalloc(C.byref(ws), C.c_size_t(wsb)) == 0 and hip.hipMemset(ws, 0, C.c_size_t(256)) == 0
+        ws = mult.enter_context(rh.kseg_workspace(lib, hip, prec, variant, o.ngptot, o.nproma, ds.klev))
         args = (prec, variant, ca.OUTPUTS_ALL, o.ngptot, o.nproma, ds.klev)
         if o.what == "a":
             def step():
@@ -73,37 +63,14 @@ def main():
         else:
             rng = np.random.default_rng(o.seed)
             n = ca.nblocks_of(o.ngptot, o.nproma) * o.nproma
-            for _ in ca.SPP_SLOTS:
-                a = rng.uniform(0.75, 1.25, n).astype(ca.storage_dtype(prec))
-                q = C.c_void_p()
-                assert hip.hipMalloc(C.byref(q), C.c_size_t(a.nbytes)) == 0
-                assert hip.hipMemcpy(q, a.ctypes.data, a.nbytes, 1) == 0
-                mult.append(q)
-            spp = ca.Spp(*[q.value for q in mult])
+            fields = [rng.uniform(0.75, 1.25, n).astype(ca.storage_dtype(prec)) for _ in ca.SPP_SLOTS]
+            spp = ca.Spp(*[mult.enter_context(rh.device_buffer(hip, a.nbytes, fill=a)).value for a in fields])
 
             def step():
                 ca.gpu_run_spp(d.f, spp, *args, scratch=ws)
-        for _ in range(o.warmup):
-            step()
-        ca.check(lib.cloudsc_gpu_check(0, None, variant, ws))
-        ms = []
-        for _ in range(o.rounds):
-            hip.hipDeviceSynchronize()
-            t0 = time.perf_counter()
-            for _ in range(o.steps):
-                step()
-            hip.hipDeviceSynchronize()
-            ms.append(1e3 * (time.perf_counter() - t0) / o.steps)
-        ca.check(lib.cloudsc_gpu_check(0, None, variant, ws))
-        print(json.dumps({"what": o.what, "precision": o.precision, "variant": o.variant, "ngptot": o.ngptot,
-                          "nproma": o.nproma, "steps": o.steps, "rounds": o.rounds,
-                          "lib": "CLOUDSC_AMD_LIB" if os.environ.get("CLOUDSC_AMD_LIB") else "this build",
-                          "ms_per_step": [round(x, 4) for x in ms], "median_ms": round(statistics.median(ms), 4)}))
-    finally:
-        for q in mult + [ws]:
-            if q.value:
-                hip.hipFree(q)
-        d.close()
+        ms = rh.what_rounds(hip, step, o, rh.launch_check(lib, variant, ws))
+        keys = ("what", "precision", "variant", "ngptot", "nproma", "steps", "rounds")
+        print(json.dumps(rh.what_record(o, ms, keys)))
 
 
 if __name__ == "__main__":

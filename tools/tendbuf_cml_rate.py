@@ -21,16 +21,12 @@ it is latency- or issue-bound (fp32).  The separate pass moves 21 * KLEV element
 written) and is a second launch, so (c)/(a) should be near 1.40 and (b)/(c) near 0.8.  Nothing here is a
 pass/fail bound."""
 import argparse
-import ctypes as C
+import contextlib
 import json
-import os
-import statistics
 import sys
-import time
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(os.path.dirname(HERE), "dwarf-p-cloudsc_amd"))
-import cloudsc_amd as ca  # noqa: E402
+import rate_harness as rh
+from rate_harness import ca
 
 
 def main():
@@ -44,62 +40,37 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=5)
     o = ap.parse_args()
-    prec = {"fp64": ca.FP64, "mixed": ca.MIXED, "fp32": ca.FP32}[o.precision]
-    lib, hip = ca.gpu_lib(), ca._hip()
-    hip.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
+    prec = rh.PRECISION[o.precision]
+    lib, hip = ca.gpu_lib(), rh.hip_api()
     if o.what != "a" and not hasattr(lib, "cloudsc_gpu_run_tendbuf_cml"):
         sys.exit("this library has no cumulative tendency form (only --what a runs on it)")
     ds = ca.load_dataset()
-    p = ca.Params.from_dict(ds.params)
-    ca.check(lib.cloudsc_gpu_init(0, C.byref(p)))
+    rh.gpu_init(lib, ds)
     d = ca.DeviceFields(o.ngptot, o.nproma, ds.klev, prec, tend_planes=o.planes, outputs=ca.OUTPUTS_PROGNOSTIC)
-    cml_buf = C.c_void_p()
-    try:
+    with contextlib.closing(d):
         keep = []
         tmpl = ca.make_template(ds, keep)
         inputs = ca.fields_subset(d.f, [k for k in ca.INPUT_FIELDS if getattr(d.f, k, None)])
         ca.expand_fields_tendbuf(inputs, tmpl, prec, o.ngptot, o.nproma, o.planes)
-        nbytes = d.tendbuf_nbytes()
-        assert hip.hipMalloc(C.byref(cml_buf), C.c_size_t(nbytes)) == 0
-        assert hip.hipMemset(cml_buf, 0, C.c_size_t(nbytes)) == 0
-        wsb = lib.cloudsc_gpu_scratch_bytes(prec, ca.VARIANT_KSEG, o.ngptot, o.nproma, ds.klev)
-        ws = C.c_void_p()
-        assert hip.hipMalloc(C.byref(ws), C.c_size_t(wsb)) == 0 and hip.hipMemset(ws, 0, C.c_size_t(256)) == 0
-        args = (prec, ca.VARIANT_KSEG, ca.OUTPUTS_PROGNOSTIC, o.ngptot, o.nproma, ds.klev, o.planes)
-        if o.what == "a":
-            def step():
-                ca.gpu_run_tendbuf_outputs(d.f, *args, scratch=ws)
-        else:
-            cml = ca.bind_tendbuf_cml(prec, o.nproma, ds.klev, cml_buf.value)
-            loc = ca.fields_subset(d.f, ["tendency_loc_t", "tendency_loc_q", "tendency_loc_a", "tendency_loc_cld"])
-            if o.what == "b":
-                def step():
-                    ca.gpu_run_tendbuf_cml(d.f, cml, *args, scratch=ws)
-            else:
+        with rh.device_buffer(hip, d.tendbuf_nbytes(), fill=0) as cml_buf, \
+                rh.kseg_workspace(lib, hip, prec, ca.VARIANT_KSEG, o.ngptot, o.nproma, ds.klev) as ws:
+            args = (prec, ca.VARIANT_KSEG, ca.OUTPUTS_PROGNOSTIC, o.ngptot, o.nproma, ds.klev, o.planes)
+            if o.what == "a":
                 def step():
                     ca.gpu_run_tendbuf_outputs(d.f, *args, scratch=ws)
-                    ca.accumulate_tendbuf(loc, cml, prec, o.ngptot, o.nproma, ds.klev, o.planes, o.planes)
-        for _ in range(o.warmup):
-            step()
-        ca.check(lib.cloudsc_gpu_check(0, None, ca.VARIANT_KSEG, ws))
-        ms = []
-        for _ in range(o.rounds):
-            hip.hipDeviceSynchronize()
-            t0 = time.perf_counter()
-            for _ in range(o.steps):
-                step()
-            hip.hipDeviceSynchronize()
-            ms.append(1e3 * (time.perf_counter() - t0) / o.steps)
-        ca.check(lib.cloudsc_gpu_check(0, None, ca.VARIANT_KSEG, ws))
-        print(json.dumps({"what": o.what, "precision": o.precision, "ngptot": o.ngptot, "nproma": o.nproma,
-                          "planes": o.planes, "steps": o.steps, "rounds": o.rounds,
-                          "lib": "CLOUDSC_AMD_LIB" if os.environ.get("CLOUDSC_AMD_LIB") else "this build",
-                          "ms_per_step": [round(x, 4) for x in ms], "median_ms": round(statistics.median(ms), 4)}))
-        hip.hipFree(ws)
-    finally:
-        if cml_buf.value:
-            hip.hipFree(cml_buf)
-        d.close()
+            else:
+                cml = ca.bind_tendbuf_cml(prec, o.nproma, ds.klev, cml_buf.value)
+                loc = ca.fields_subset(d.f, ["tendency_loc_t", "tendency_loc_q", "tendency_loc_a", "tendency_loc_cld"])
+                if o.what == "b":
+                    def step():
+                        ca.gpu_run_tendbuf_cml(d.f, cml, *args, scratch=ws)
+                else:
+                    def step():
+                        ca.gpu_run_tendbuf_outputs(d.f, *args, scratch=ws)
+                        ca.accumulate_tendbuf(loc, cml, prec, o.ngptot, o.nproma, ds.klev, o.planes, o.planes)
+            ms = rh.what_rounds(hip, step, o, rh.launch_check(lib, ca.VARIANT_KSEG, ws))
+            keys = ("what", "precision", "ngptot", "nproma", "planes", "steps", "rounds")
+            print(json.dumps(rh.what_record(o, ms, keys)))
 
 
 if __name__ == "__main__":

@@ -37,55 +37,22 @@ EXPECTATION, written before the first run (nobody had measured any of this):
     copy rate, and 3.20 measured the comparison at 0.6-0.8 of it).  Expected (v)/(u) about 0.65-0.75, and
     (v) at 0.5-0.8 of the STREAM copy counting the bytes it reads."""
 import argparse
+import contextlib
 import ctypes as C
-import json
-import os
-import sys
-import time
 
 import numpy as np
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "dwarf-p-cloudsc_amd"))
-import cloudsc_amd as ca  # noqa: E402
+import rate_harness as rh
+from rate_harness import ca
 
 TMP = [n for n in ca.TENDENCY_FIELDS if "_tmp_" in n]
 LOC = [n for n in ca.TENDENCY_FIELDS if "_loc_" in n]
-PRECISIONS = [("fp64", ca.FP64), ("mixed", ca.MIXED), ("fp32", ca.FP32)]
 EXPECTATION = {"b_over_a": {"fp64": 0.87, "mixed": 0.94, "fp32": 0.84, "within": 0.03},
                "b_over_c": "1.00 to 1.03 (3.21 measured 1.012-1.014 on the full step)",
                "validate_inplace_over_unpack_validate": "0.65 to 0.75",
                "validate_inplace_of_stream_copy": "0.5 to 0.8",
                "surprise": "b_over_a above 0.97, or b_over_c above 1.05",
                "why": "see the EXPECTATION paragraph of tools/tendbuf_outputs_rate.py (DESIGN 3.20, 3.21, 3.22)"}
-
-
-class SpanTimer:
-    """One launch between two events on the default stream, waited for: milliseconds."""
-
-    def __init__(self, hip):
-        self.hip = hip
-        self.e0, self.e1 = C.c_void_p(), C.c_void_p()
-        assert hip.hipEventCreate(C.byref(self.e0)) == 0 and hip.hipEventCreate(C.byref(self.e1)) == 0
-
-    def ms(self, launch):
-        assert self.hip.hipEventRecord(self.e0, None) == 0
-        launch()
-        assert self.hip.hipEventRecord(self.e1, None) == 0
-        assert self.hip.hipEventSynchronize(self.e1) == 0
-        ms = C.c_float()
-        assert self.hip.hipEventElapsedTime(C.byref(ms), self.e0, self.e1) == 0
-        return ms.value
-
-
-def host_ms(call):
-    t0 = time.perf_counter()
-    call()
-    return 1e3 * (time.perf_counter() - t0)
-
-
-def summary(v):
-    return {"median_ms": round(float(np.median(v)), 4), "min_ms": round(float(np.min(v)), 4),
-            "max_ms": round(float(np.max(v)), 4)}
 
 
 def validated_bytes(klev, es):
@@ -106,36 +73,15 @@ def main():
     n, nproma, tp = args.ngptot, args.nproma, args.tend_planes
     ds = ca.load_dataset()
     klev = ds.klev
-    if ca.device_count() < 1:
-        raise SystemExit("tendbuf_outputs_rate: no HIP device")
-    lib, hip = ca.gpu_lib(), ca._hip()
-    hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
-    hip.hipEventRecord.argtypes = [C.c_void_p, C.c_void_p]
-    hip.hipEventSynchronize.argtypes = [C.c_void_p]
-    hip.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
-    timer = SpanTimer(hip)
-    lines = []
-
-    def emit(rec):
-        lines.append(rec)
-        print(json.dumps(rec), flush=True)
-
-    emit({"measure": "expectation", **EXPECTATION})
-    stream = ca.hbm_copy_gbps(0, 4 << 30, 10)
-    emit({"measure": "stream_copy", "gbps": round(stream, 1)})
-    p = ca.Params.from_dict(ds.params)
-    ca.check(lib.cloudsc_gpu_init(0, C.byref(p)))
+    lib, hip, timer, records, stream = rh.begin("tendbuf_outputs_rate", ds, EXPECTATION)
     keep = []
     ref = ca.make_reference(ds, keep)
 
-    for label, prec in PRECISIONS:
+    for label, prec in rh.PRECISIONS:
         df = ca.DeviceFields(n, nproma, klev, prec, tend_planes=tp)     # outputs placed; buffers plain hipMalloc
-        ws = C.c_void_p()
-        try:
-            nbytes = lib.cloudsc_gpu_scratch_bytes(prec, ca.VARIANT_KSEG, n, nproma, klev)
-            assert nbytes > 0 and hip.hipMalloc(C.byref(ws), C.c_size_t(nbytes)) == 0
-            assert hip.hipMemset(ws, 0, C.c_size_t(256)) == 0
-            df.expand(ds)                                               # the separate arrays
+        with contextlib.closing(df), rh.kseg_workspace(lib, hip, prec, ca.VARIANT_KSEG, n, nproma, klev) as ws:
+            check = rh.launch_check(lib, ca.VARIANT_KSEG, ws)
+            df.expand(ds)                                              # the separate arrays
             ca.convert_fields_tendbuf(ca.fields_subset(df.separate, TMP), ca.fields_subset(df.f, TMP), n, klev, prec,
                                       nproma, 0, prec, nproma, tp)      # BUFFER_TMP filled
             loc_buf, loc_sep = ca.fields_subset(df.f, LOC), ca.fields_subset(df.separate, LOC)
@@ -151,24 +97,18 @@ def main():
                 ca.gpu_run_outputs(df.separate, prec, ca.VARIANT_KSEG, ca.OUTPUTS_PROGNOSTIC, n, nproma, klev,
                                    scratch=ws)
 
-            cases = [("a", run_a), ("b", run_b), ("c", run_c)]
-            ms = {k: [] for k, _ in cases}
-            for r in range(args.warmup + args.rounds):
-                for k, fn in cases:
-                    t = timer.ms(fn)
-                    ca.check(lib.cloudsc_gpu_check(0, None, ca.VARIANT_KSEG, ws))
-                    if r >= args.warmup:
-                        ms[k].append(t)
+            ms = rh.alternate(timer.ms, [("a", run_a), ("b", run_b), ("c", run_c)], args.rounds, args.warmup, check)
             a, b, c = (float(np.median(ms[k])) for k in "abc")
-            emit({"measure": "kseg_tendbuf_outputs", "precision": label, "ngptot": n, "nproma": nproma, "klev": klev,
-                  "tend_planes": tp, "rounds": args.rounds, "warmup": args.warmup,
-                  "a_tendbuf_all": summary(ms["a"]), "b_tendbuf_prognostic": summary(ms["b"]),
-                  "c_separate_prognostic": summary(ms["c"]), "b_over_a": round(b / a, 4), "b_over_c": round(b / c, 4),
-                  "b_over_a_expected": EXPECTATION["b_over_a"][label], "placement": df.report.to_dict()})
+            records.emit({"measure": "kseg_tendbuf_outputs", "precision": label, "ngptot": n, "nproma": nproma,
+                          "klev": klev, "tend_planes": tp, "rounds": args.rounds, "warmup": args.warmup,
+                          "a_tendbuf_all": rh.summary(ms["a"]), "b_tendbuf_prognostic": rh.summary(ms["b"]),
+                          "c_separate_prognostic": rh.summary(ms["c"]), "b_over_a": round(b / a, 4),
+                          "b_over_c": round(b / c, 4), "b_over_a_expected": EXPECTATION["b_over_a"][label],
+                          "placement": df.report.to_dict()})
 
             # all 21 outputs in both places: one full step on the buffers, BUFFER_LOC unpacked once
             run_a()
-            ca.check(lib.cloudsc_gpu_check(0, None, ca.VARIANT_KSEG, ws))
+            check()
             stats_sep = (ca.Stats * len(ca.VALIDATED))()
 
             def val_inplace():
@@ -179,30 +119,16 @@ def main():
                 ca.check(lib.cloudsc_fields_validate(0, None, prec, n, nproma, klev, 0, C.byref(df.separate),
                                                      C.byref(ref), stats_sep))
 
-            vcases = [("v", val_inplace), ("u", val_unpack)]
-            vms = {k: [] for k, _ in vcases}
-            for r in range(args.warmup + args.rounds):
-                for k, fn in vcases:
-                    t = host_ms(fn)
-                    if r >= args.warmup:
-                        vms[k].append(t)
+            vms = rh.alternate(rh.host_ms, [("v", val_inplace), ("u", val_unpack)], args.rounds, args.warmup)
             v, u = (float(np.median(vms[k])) for k in "vu")
             es = np.dtype(ca.storage_dtype(prec)).itemsize
             vb = validated_bytes(klev, es)
-            emit({"measure": "validate_tendbuf", "precision": label, "ngptot": n, "nproma": nproma, "klev": klev,
-                  "tend_planes": tp, "rounds": args.rounds, "warmup": args.warmup,
-                  "v_inplace": summary(vms["v"]), "u_unpack_then_validate": summary(vms["u"]),
-                  "v_over_u": round(v / u, 4), "u_minus_v_ms": round(u - v, 4), "validated_column_bytes": vb,
-                  "v_of_stream_copy": round(vb * n / (v * 1e-3) / 1e9 / stream, 3)})
-        finally:
-            if ws.value:
-                hip.hipFree(ws)
-            df.close()
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            for rec in lines:
-                fh.write(json.dumps(rec) + "\n")
+            records.emit({"measure": "validate_tendbuf", "precision": label, "ngptot": n, "nproma": nproma,
+                          "klev": klev, "tend_planes": tp, "rounds": args.rounds, "warmup": args.warmup,
+                          "v_inplace": rh.summary(vms["v"]), "u_unpack_then_validate": rh.summary(vms["u"]),
+                          "v_over_u": round(v / u, 4), "u_minus_v_ms": round(u - v, 4), "validated_column_bytes": vb,
+                          "v_of_stream_copy": round(vb * n / (v * 1e-3) / 1e9 / stream, 3)})
+    records.write(args.out)
 
 
 if __name__ == "__main__":

@@ -30,45 +30,19 @@ EXPECTATION, written before the first run (nobody had measured any of this):
     fp64, half of that for float storage.
   - so (b) should beat (c) clearly, by ~0.7 ms or more in fp64, even if it is 16 % slower than (a)."""
 import argparse
+import contextlib
 import ctypes as C
-import json
-import os
-import sys
 
 import numpy as np
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "dwarf-p-cloudsc_amd"))
-import cloudsc_amd as ca  # noqa: E402
+import rate_harness as rh
+from rate_harness import ca
 
 TMP = [n for n in ca.TENDENCY_FIELDS if "_tmp_" in n]
 LOC = [n for n in ca.TENDENCY_FIELDS if "_loc_" in n]
-PRECISIONS = [("fp64", ca.FP64), ("mixed", ca.MIXED), ("fp32", ca.FP32)]
 EXPECTATION = {"b_over_a": "1.00 to 1.16, most likely a few percent above 1", "c_minus_a_ms_fp64": "about 1.0",
                "c_minus_a_ms_float_storage": "about 0.5", "b_beats_c": True,
                "why": "see the EXPECTATION paragraph of tools/tendbuf_rate.py (DESIGN 3.12, 3.16.1, 3.19)"}
-
-
-class SpanTimer:
-    """One launch sequence between two events on the default stream, waited for: milliseconds."""
-
-    def __init__(self, hip):
-        self.hip = hip
-        self.e0, self.e1 = C.c_void_p(), C.c_void_p()
-        assert hip.hipEventCreate(C.byref(self.e0)) == 0 and hip.hipEventCreate(C.byref(self.e1)) == 0
-
-    def ms(self, launch):
-        assert self.hip.hipEventRecord(self.e0, None) == 0
-        launch()
-        assert self.hip.hipEventRecord(self.e1, None) == 0
-        assert self.hip.hipEventSynchronize(self.e1) == 0
-        ms = C.c_float()
-        assert self.hip.hipEventElapsedTime(C.byref(ms), self.e0, self.e1) == 0
-        return ms.value
-
-
-def summary(v):
-    return {"median_ms": round(float(np.median(v)), 4), "min_ms": round(float(np.min(v)), 4),
-            "max_ms": round(float(np.max(v)), 4)}
 
 
 def main():
@@ -83,34 +57,12 @@ def main():
     n, nproma, tp = args.ngptot, args.nproma, args.tend_planes
     ds = ca.load_dataset()
     klev = ds.klev
-    if ca.device_count() < 1:
-        raise SystemExit("tendbuf_rate: no HIP device")
-    lib, hip = ca.gpu_lib(), ca._hip()
-    hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
-    hip.hipEventRecord.argtypes = [C.c_void_p, C.c_void_p]
-    hip.hipEventSynchronize.argtypes = [C.c_void_p]
-    hip.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
-    timer = SpanTimer(hip)
-    lines = []
+    lib, hip, timer, records, stream = rh.begin("tendbuf_rate", ds, EXPECTATION)
 
-    def emit(rec):
-        lines.append(rec)
-        print(json.dumps(rec), flush=True)
-
-    emit({"measure": "expectation", **EXPECTATION})
-    stream = ca.hbm_copy_gbps(0, 4 << 30, 10)
-    emit({"measure": "stream_copy", "gbps": round(stream, 1)})
-    p = ca.Params.from_dict(ds.params)
-    ca.check(lib.cloudsc_gpu_init(0, C.byref(p)))
-
-    for label, prec in PRECISIONS:
+    for label, prec in rh.PRECISIONS:
         df = ca.DeviceFields(n, nproma, klev, prec, tend_planes=tp)     # outputs placed; buffers plain hipMalloc
-        ws = C.c_void_p()
-        try:
+        with contextlib.closing(df), rh.kseg_workspace(lib, hip, prec, ca.VARIANT_KSEG, n, nproma, klev) as ws:
             sep, buf = df.separate, df.f
-            nbytes = lib.cloudsc_gpu_scratch_bytes(prec, ca.VARIANT_KSEG, n, nproma, klev)
-            assert nbytes > 0 and hip.hipMalloc(C.byref(ws), C.c_size_t(nbytes)) == 0
-            assert hip.hipMemset(ws, 0, C.c_size_t(256)) == 0
             assert hip.hipMemset(df.buffer_tmp, 0, C.c_size_t(df.tendbuf_nbytes())) == 0
             assert hip.hipMemset(df.buffer_loc, 0, C.c_size_t(df.tendbuf_nbytes())) == 0
             df.expand(ds)                                               # the separate arrays
@@ -129,34 +81,20 @@ def main():
                 run_a()
                 ca.convert_fields_tendbuf(loc_sep, loc_buf, n, klev, prec, nproma, 0, prec, nproma, tp)
 
-            cases = [("a", run_a), ("b", run_b), ("c", run_c)]
-            ms = {k: [] for k, _ in cases}
-            for r in range(args.warmup + args.rounds):
-                for k, fn in cases:
-                    t = timer.ms(fn)
-                    ca.check(lib.cloudsc_gpu_check(0, None, ca.VARIANT_KSEG, ws))
-                    if r >= args.warmup:
-                        ms[k].append(t)
+            ms = rh.alternate(timer.ms, [("a", run_a), ("b", run_b), ("c", run_c)], args.rounds, args.warmup,
+                              rh.launch_check(lib, ca.VARIANT_KSEG, ws))
             es = np.dtype(ca.storage_dtype(prec)).itemsize
             conv_bytes = 2 * 2 * 8 * klev * n * es          # two conversions, read + write, 8 planes each
             rec = {"measure": "kseg_tendbuf", "precision": label, "ngptot": n, "nproma": nproma, "klev": klev,
                    "tend_planes": tp, "rounds": args.rounds, "warmup": args.warmup,
-                   "a_plain": summary(ms["a"]), "b_tendbuf": summary(ms["b"]), "c_unpack_run_pack": summary(ms["c"]),
-                   "conversion_bytes": conv_bytes}
+                   "a_plain": rh.summary(ms["a"]), "b_tendbuf": rh.summary(ms["b"]),
+                   "c_unpack_run_pack": rh.summary(ms["c"]), "conversion_bytes": conv_bytes}
             a, b, c = (float(np.median(ms[k])) for k in "abc")
             rec.update({"b_over_a": round(b / a, 4), "c_over_a": round(c / a, 4), "c_minus_a_ms": round(c - a, 4),
                         "b_minus_c_ms": round(b - c, 4),
                         "conversions_of_stream_copy": round(conv_bytes / ((c - a) * 1e-3) / 1e9 / stream, 3) if c > a else None})
-            emit(rec)
-        finally:
-            if ws.value:
-                hip.hipFree(ws)
-            df.close()
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            for rec in lines:
-                fh.write(json.dumps(rec) + "\n")
+            records.emit(rec)
+    records.write(args.out)
 
 
 if __name__ == "__main__":
