@@ -622,6 +622,14 @@ def gpu_lib(path: Optional[str] = None):
     lib.cloudsc_debug_set_kseg_schedule.argtypes = [C.c_int, C.c_int]
     lib.cloudsc_gpu_launch_geometry.argtypes = [C.c_int] * 6 + [C.POINTER(LaunchGeometry)]
     lib.cloudsc_debug_set_narrow_pack.argtypes = [C.c_int]
+    if hasattr(lib, "cloudsc_batch_create"):   # (likewise: the batched step)
+        # batch, device, precision, outputs, nsets, ngptot, nproma, klev, sets[nsets], params[nsets] or NULL
+        lib.cloudsc_batch_create.argtypes = [C.POINTER(C.c_void_p)] + [C.c_int] * 7 + [C.POINTER(Fields),
+                                                                                      C.POINTER(Params)]
+        lib.cloudsc_gpu_run_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        lib.cloudsc_batch_nsets.argtypes = [C.c_void_p]
+        lib.cloudsc_batch_destroy.argtypes = [C.c_void_p]
+        lib.cloudsc_batch_launch_geometry.argtypes = [C.c_int] * 6 + [C.POINTER(LaunchGeometry)]
     lib.cloudsc_debug_host_pipeline_mapping.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.cloudsc_debug_host_pinned.argtypes = [C.c_void_p, C.c_longlong]
     lib.cloudsc_debug_fp32_libm.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong]
@@ -654,6 +662,77 @@ def launch_geometry(precision: int, variant: int, ngptot: int, nproma: int, klev
     g = LaunchGeometry()
     check(gpu_lib().cloudsc_gpu_launch_geometry(precision, variant, ngptot, nproma, klev, int(bool(laer)), C.byref(g)))
     return g.to_dict()
+
+
+BATCH_MAX_SETS = 65535
+
+
+def batch_launch_geometry(precision: int, nsets: int, ngptot: int, nproma: int, klev: int, laer: bool = False) -> dict:
+    """What Batch.run would launch: launch_geometry of one set (KCACHE) with units and workgroups times nsets."""
+    g = LaunchGeometry()
+    check(gpu_lib().cloudsc_batch_launch_geometry(precision, nsets, ngptot, nproma, klev, int(bool(laer)), C.byref(g)))
+    return g.to_dict()
+
+
+class Batch:
+    """cloudsc_batch_create / cloudsc_gpu_run_batch: `sets` (Fields of DEVICE pointers, or DeviceFields) of one
+    shape run in ONE KCACHE launch, set i under params[i] (dicts keyed like Dataset.params) or, with params=None,
+    all of them under the device's set (cloudsc_gpu_init).  Every selected output of set i has the bits
+    gpu_run_outputs gives for that set alone under params[i].  Sets may share input members; the members the
+    step writes (plude included) are exclusive.  The batch keeps its DeviceFields alive; the table and the
+    parameter sets are uploaded once, here."""
+
+    def __init__(self, sets, precision: int, outputs: int, ngptot: int, nproma: int, klev: int, params=None,
+                 device: int = 0):
+        self.lib = gpu_lib()
+        self.h = None
+        self.sets = list(sets)            # references: the device memory must outlive the batch
+        self.device = device
+        fs = [s.f if isinstance(s, DeviceFields) else s for s in self.sets]
+        for f in fs:
+            require_blocked(f, "Batch")
+        if params is not None and len(params) != len(fs):
+            raise ValueError("Batch: one parameter set per field set (%d sets, %d parameter sets)"
+                             % (len(fs), len(params)))
+        arr = (Fields * max(len(fs), 1))()
+        for i, f in enumerate(fs):
+            C.memmove(C.byref(arr, i * C.sizeof(Fields)), C.byref(f), C.sizeof(Fields))
+        par = None
+        if params is not None:
+            par = (Params * max(len(fs), 1))()
+            for i, d in enumerate(params):
+                p = d if isinstance(d, Params) else Params.from_dict(d)
+                C.memmove(C.byref(par, i * C.sizeof(Params)), C.byref(p), C.sizeof(Params))
+        h = C.c_void_p()
+        check(self.lib.cloudsc_batch_create(C.byref(h), device, precision, outputs, len(fs), ngptot, nproma, klev,
+                                            arr, par))
+        self.h = h
+
+    @property
+    def nsets(self) -> int:
+        return self.lib.cloudsc_batch_nsets(self.h)
+
+    def run(self, variant: int = None, stream=None) -> None:
+        """One launch for every set, asynchronous on `stream` (None = the default stream); VARIANT_KCACHE only."""
+        check(self.lib.cloudsc_gpu_run_batch(self.h, stream, VARIANT_KCACHE if variant is None else variant))
+
+    def close(self) -> None:
+        if getattr(self, "h", None):
+            self.lib.cloudsc_batch_destroy(self.h)
+            self.h = None
+        self.sets = []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def kseg_spin_limit(limit: int = -1) -> None:

@@ -72,6 +72,14 @@ int check_params(const cloudsc_params_t* p) {
   return CLOUDSC_OK;
 }
 
+size_t param_block_bytes() { return kParamBlockBytes; }
+void param_block_fill(char* blk, const cloudsc_params_t& p) {
+  const DevParamsSpp<double> dp = fold_params<double>(p);
+  const DevParamsSpp<float> sp = fold_params<float>(p);
+  std::memcpy(blk, &dp, sizeof(dp));
+  std::memcpy(blk + kSpOffset, &sp, sizeof(sp));
+}
+
 int param_set_upload(ParamSet* ps, int device, const cloudsc_params_t* p) {
   int rc = check_params(p);
   if (rc) return rc;
@@ -81,10 +89,7 @@ int param_set_upload(ParamSet* ps, int device, const cloudsc_params_t* p) {
     if (e != hipSuccess) { ps->dev = nullptr; hip_fail(e, "hipMalloc(params)"); return CLOUDSC_ENOMEM; }
   }
   std::vector<char> blk(kParamBlockBytes, 0);
-  const DevParamsSpp<double> dp = fold_params<double>(*p);
-  const DevParamsSpp<float> sp = fold_params<float>(*p);
-  std::memcpy(blk.data(), &dp, sizeof(dp));
-  std::memcpy(blk.data() + kSpOffset, &sp, sizeof(sp));
+  param_block_fill(blk.data(), *p);
   // hipMemcpy from pageable memory may return before the bytes have reached the
   // device, and the launches that read them run on non-blocking streams, which
   // do not wait for the null stream: a state created right after another one's
@@ -230,6 +235,27 @@ __global__ void __launch_bounds__(256, F::waves) kcache_entry(const typename F::
   (void)a;
   libm_tables_to_lds<typename F::real>();
   const cptr<typename F::fields> ka = (cptr<typename F::fields>)__builtin_amdgcn_kernarg_segment_ptr();
+  cloudsc_kcache_body<F>(ka, params_of<F>(ka), g...);
+}
+// The batched one-shot kernel (cloudsc_gpu_run_batch): kcache_entry over a device table of
+// kernel-argument structs, one per member (field set), kBatchEntryStride<F> bytes apart.  The member index is
+// blockIdx.y, the grid dimension the one-shot launch leaves free -- a workgroup id, so it arrives in a scalar
+// register and is wave-uniform by construction -- and blockIdx.x is the block (F::pack: the group) within the
+// member, exactly as in kcache_entry.  `ka` points at the member's entry instead of at the kernarg segment; the
+// body reads it, and the parameter block its `par` points at, through the same constant-address-space pointer,
+// with scalar loads, so each member runs under its own parameter set.  Packed: the wave of workgroup (g, m)
+// walks blocks g * pack .. g * pack + pack - 1 of member m and pack_lane switches off the lanes whose block is
+// past that member's nblocks, so a wave never runs into the next member.  Plain forms only: F::kargs is F::fields.
+constexpr size_t kBatchEntryStride = (sizeof(KArgs<double>) + 63) & ~(size_t)63;   // whole scalar-cache lines
+static_assert(sizeof(KArgs<float>) == sizeof(KArgs<double>) && sizeof(KArgs<double, float>) == sizeof(KArgs<double>),
+              "one entry size for every precision: pointers and three ints");
+template <typename F, typename... Pack>
+__global__ void __launch_bounds__(256, F::waves) kcache_batch_entry(const char* table, const Pack... g) {
+  static_assert(sizeof...(Pack) == (F::pack ? 1 : 0), "PackArgs exactly when the form is packed");
+  static_assert(std::is_same<typename F::kargs, typename F::fields>::value, "the batch runs the plain forms");
+  libm_tables_to_lds<typename F::real>();
+  const cptr<typename F::fields> ka =
+      (cptr<typename F::fields>)(const typename F::fields*)(table + (size_t)blockIdx.y * kBatchEntryStride);
   cloudsc_kcache_body<F>(ka, params_of<F>(ka), g...);
 }
 template <typename F, typename... Pack>
@@ -756,7 +782,67 @@ int launch(int precision, const LaunchRequest& rq) {
   }
 }
 
+// The batched KCACHE launch (kcache_batch_entry): the grid of launch_kcache in x, the members in y.  The packing
+// decision is the one-shot launch's, taken here, at each run; the kernels are the product configuration's.
+template <typename real, bool FAST, typename ST = real>
+int launch_batch_v(hipStream_t st, const BatchLaunch& b) {
+  const bool aer = b.aer;
+  const unsigned bits = form_bits(false, outputs_prognostic(b.outputs), outputs_surface(b.outputs), false);
+  if (!kernel_kept<real, ST, FAST>(CLOUDSC_VARIANT_KCACHE, aer, bits)) return CLOUDSC_EINVAL;
+  const int nblocks = b.ngptot / b.nproma + (b.ngptot % b.nproma ? 1 : 0);
+  const int pack = narrow_pack_factor(kPrecisionOf<real, ST>, CLOUDSC_VARIANT_KCACHE, b.nproma, b.klev, aer);
+  const PackArgs pk{pack, nblocks, (nblocks + pack - 1) / pack};
+  const int rc = dispatch_bools(
+      [&](auto AER, auto PACK, auto PROG, auto SURF) {
+        constexpr unsigned form = form_bits(false, PROG, SURF, false) | (PACK ? kFormPack : 0u);
+        if constexpr (kernel_kept<real, ST, FAST>(CLOUDSC_VARIANT_KCACHE, AER, form)) {
+          using F = typename LaunchForm<real, ST, AER, FAST, form>::product;
+          static_assert(!F::ldsc, "the product configuration carries its state in registers");
+          const char* table = (const char*)b.table;
+          if constexpr (F::pack)
+            hipLaunchKernelGGL((kcache_batch_entry<F, PackArgs>), dim3(pk.ngroups, b.nsets), dim3(64), 0, st, table, pk);
+          else
+            hipLaunchKernelGGL((kcache_batch_entry<F>), dim3(nblocks, b.nsets), dim3(b.nproma), 0, st, table);
+          return (int)CLOUDSC_OK;
+        } else {
+          return (int)CLOUDSC_EINVAL;
+        }
+      },
+      aer, pack > 1, (bits & kFormProg) != 0, (bits & kFormSurf) != 0);
+  if (rc) return rc;
+  HIPCHK(hipGetLastError());
+  return CLOUDSC_OK;
+}
+
+template <typename real, typename ST>
+void batch_entry_fill(void* entry, const cloudsc_fields_t* f, int ngptot, int nproma, int klev, const void* block) {
+  const KArgs<real, ST> a = make_kargs<real, ST>(
+      f, ngptot, nproma, klev, (const DevParams<real>*)((const char*)block + (sizeof(real) == 8 ? 0 : kSpOffset)));
+  static_assert(sizeof(a) <= kBatchEntryStride, "an entry holds the kernel arguments");
+  std::memcpy(entry, &a, sizeof(a));
+}
+
 }  // namespace
+
+namespace cloudsc_impl {
+size_t batch_entry_stride() { return kBatchEntryStride; }
+void batch_make_entry(int precision, void* entry, const cloudsc_fields_t* f, int ngptot, int nproma, int klev,
+                      const void* param_block) {
+  switch (precision) {
+    case CLOUDSC_FP64: return batch_entry_fill<double, double>(entry, f, ngptot, nproma, klev, param_block);
+    case CLOUDSC_FP32: return batch_entry_fill<float, float>(entry, f, ngptot, nproma, klev, param_block);
+    default: return batch_entry_fill<double, float>(entry, f, ngptot, nproma, klev, param_block);
+  }
+}
+int launch_kcache_batch(void* stream, const BatchLaunch& b) {
+  switch (b.precision) {
+    case CLOUDSC_FP64: return launch_batch_v<double, false>((hipStream_t)stream, b);
+    case CLOUDSC_FP32: return launch_batch_v<float, true>((hipStream_t)stream, b);
+    case CLOUDSC_MIXED: return launch_batch_v<double, false, float>((hipStream_t)stream, b);
+    default: return CLOUDSC_EINVAL;
+  }
+}
+}  // namespace cloudsc_impl
 
 // ---------------------------------------------------------------------------
 // C ABI: low level
@@ -804,7 +890,7 @@ long long cloudsc_gpu_scratch_bytes(int precision, int variant, int ngptot, int 
 
 namespace cloudsc_impl {
 // the checks of validate_run_args that need no device
-static int validate_shape_args(int precision, int variant, int ngptot, int nproma, int klev) {
+int validate_shape_args(int precision, int variant, int ngptot, int nproma, int klev) {
   if (!precision_storage_bytes(precision)) return CLOUDSC_EINVAL;
   if (variant != CLOUDSC_VARIANT_KCACHE && variant != CLOUDSC_VARIANT_SCC && variant != CLOUDSC_VARIANT_KSEG &&
       variant != CLOUDSC_VARIANT_SCC_PRIVATE)

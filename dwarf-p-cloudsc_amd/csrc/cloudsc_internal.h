@@ -81,6 +81,26 @@ int hip_fail(hipError_t e, const char* what);
 void set_error_text(const char* text);
 // device / precision / variant / size checks shared by every entry point
 int validate_run_args(int device, int precision, int variant, int ngptot, int nproma, int klev);
+// the checks of validate_run_args that need no device (`variant`: a kind, without option bits)
+int validate_shape_args(int precision, int variant, int ngptot, int nproma, int klev);
+
+// ---- the batched KCACHE launch (cloudsc_batch.hip owns the table, cloudsc_gpu.hip the kernels) ----
+// a parameter set's device block: its size, and its host image (the fp64 mirror, then the fp32 one)
+size_t param_block_bytes();
+void param_block_fill(char* block, const cloudsc_params_t& p);
+// One entry of a batch's device table: the kernel arguments cloudsc_gpu_run_outputs would pass for f, with `par`
+// pointing into the device parameter block `param_block`; entries are batch_entry_stride() bytes apart
+size_t batch_entry_stride();
+void batch_make_entry(int precision, void* entry, const cloudsc_fields_t* f, int ngptot, int nproma, int klev,
+                      const void* param_block);
+struct BatchLaunch {
+  int precision, outputs, nsets, ngptot, nproma, klev;
+  bool aer;            // LAERICESED || LAERICEAUTO of every member's parameters
+  const void* table;   // device: nsets entries
+};
+// one launch on `stream`, no upload, no allocation; the caller has set the device
+int launch_kcache_batch(void* stream, const BatchLaunch& b);
+
 // The ten diagnostic flux members pfsqlf ... pfsqitur (consecutive in cloudsc_fields_t): running sums of
 // section 8 that nothing in the step reads back; CLOUDSC_OUTPUTS_PROGNOSTIC leaves them out
 constexpr bool is_flux_diagnostic(int member) { return member >= CLOUDSC_M_pfsqlf && member <= CLOUDSC_M_pfsqitur; }

@@ -64,6 +64,7 @@ typedef struct {
   int outputs, outputs_given;     /* --outputs all|prognostic|surface: CLOUDSC_OUTPUTS_* */
   int spp;                        /* --spp unit: the step through the SPP form, five all-ones multiplier fields */
   int advance;                    /* --advance N: N advancing steps in place (cloudsc_*_run_advance); 0: not given */
+  int batch;                      /* --batch N: N caller-owned sets of <ngptot> columns each, one batched launch per step; 0: not given */
   int place;                      /* placement search: 1 on, 0 off, -1 auto (on when reps > 1) */
   int narrow_pack;                /* NPROMA <= 32 packed into full waves: 1 on, 0 off, -1 the library's default */
   double energy_s;                /* --energy: seconds of back-to-back launches sampled for board power */
@@ -83,6 +84,7 @@ typedef struct {
   int outputs;                    /* --outputs: CLOUDSC_OUTPUTS_* */
   int spp;                        /* --spp unit: cloudsc_gpu_run_spp with five all-ones multiplier fields */
   int advance;                    /* --advance N: the timed steps are N cloudsc_gpu_run_advance in place */
+  int batch;                      /* --batch N: ngptot is N sets of ngptot / N columns, stepped by one cloudsc_gpu_run_batch */
   double energy_s;
   long long col_offset;
   const cloudsc_template_t *tmpl;
@@ -174,6 +176,9 @@ static void usage(const char *prog) {
           "                        N = 1 the fluxes, PCOVPTOT, PLUDE and PRAINFRAC_TOPRFZ are validated, the tendencies\n"
           "                        are not stored and have no row; with N > 1 nothing is validated.  One ADVANCE line\n"
           "                        follows the table: the steps taken and the time per step\n"
+          "  --batch N             --fields caller --variant kcache: N field sets of <ngptot> columns each (set i the\n"
+          "                        columns from i * <ngptot>), all stepped by one cloudsc_gpu_run_batch launch; every set\n"
+          "                        is validated and the table is that of the N * <ngptot> columns together\n"
           "  --transfer            host-buffer path: block-layout arrays in host memory,\n"
           "                        H2D -> kernel -> D2H per chunk, overlapped on streams\n"
           "                        (TOTAL includes the transfers, like cloudsc_driver.cu)\n"
@@ -276,6 +281,13 @@ static int parse(int argc, char **argv, options_t *o) {
       const long n = strtol(v, &end, 10);
       if (*end || n < 1 || n > 100000) { fprintf(stderr, "bad --advance %s\n", v); return -1; }
       o->advance = (int)n;
+    }
+    else if (!strcmp(a, "--batch")) {
+      NEEDV();
+      char *end;
+      const long n = strtol(v, &end, 10);
+      if (*end || n < 1 || n > CLOUDSC_BATCH_MAX_SETS) { fprintf(stderr, "bad --batch %s\n", v); return -1; }
+      o->batch = (int)n;
     }
     else if (!strcmp(a, "--fp32-exact-libm")) o->exact_libm = 1;
     else if (!strcmp(a, "--chunk")) { NEEDV(); o->chunk_blocks = atoi(v); }
@@ -627,8 +639,80 @@ static void shard_caller(shard_t *s) {
   cloudsc_fields_free(s->device, &lev);
 }
 
+/* ---- --fields caller --batch N: N caller-owned sets of ngptot / N columns each, set i expanded from the template's
+ * columns at col_offset + i * (ngptot / N), all of them stepped by one cloudsc_gpu_run_batch per rep under the
+ * device's parameter set, each validated on the device and the statistics combined (double-double sums): the
+ * table of one set of ngptot columns. ---- */
+static void shard_batch(shard_t *s) {
+  const int klev = s->tmpl->klev, n = s->batch, per = s->ngptot / n;
+  const int alloc_flags = (s->place_on ? 0 : CLOUDSC_PLACE_NONE) | (s->aerosols ? CLOUDSC_ALLOC_AEROSOLS : 0);
+  cloudsc_fields_t *f = (cloudsc_fields_t *)calloc((size_t)n, sizeof(*f));
+  cloudsc_batch_t *batch = NULL;
+  int nalloc = 0;
+  s->rc = f ? CLOUDSC_OK : CLOUDSC_ENOMEM;
+  for (int i = 0; i < n && !s->rc; i++) {
+    s->rc = cloudsc_fields_alloc_outputs(s->device, s->precision, per, s->nproma, klev, alloc_flags, s->outputs, &f[i],
+                                         &s->place);
+    if (!s->rc) nalloc = i + 1;
+    if (!s->rc)
+      s->rc = cloudsc_fields_expand(s->device, NULL, s->precision, per, s->nproma, s->col_offset + (long long)i * per,
+                                    s->tmpl, &f[i]);
+  }
+  if (!s->rc)
+    s->rc = cloudsc_batch_create(&batch, s->device, s->precision, s->outputs, n, per, s->nproma, klev, f, NULL);
+  /* plude is INOUT: expanded again before every step, outside the timing */
+  for (int r = 0; r < s->warmup + s->reps; r++) {
+    const int timed = r >= s->warmup;
+    if (r == s->warmup) { pthread_barrier_wait(s->barrier); s->t_start = s->t_end = now(); }
+    for (int i = 0; i < n && !s->rc && r; i++) {
+      cloudsc_fields_t plude;
+      memset(&plude, 0, sizeof(plude));
+      plude.plude = f[i].plude;
+      s->rc = cloudsc_fields_expand(s->device, NULL, s->precision, per, s->nproma, s->col_offset + (long long)i * per,
+                                    s->tmpl, &plude);
+    }
+    if (!s->rc) s->rc = cloudsc_gpu_check(s->device, NULL, CLOUDSC_VARIANT_KCACHE, NULL);   /* the expansion is done */
+    const double k0 = now();
+    if (!s->rc) s->rc = cloudsc_gpu_run_batch(batch, NULL, s->variant);
+    if (!s->rc) s->rc = cloudsc_gpu_check(s->device, NULL, CLOUDSC_VARIANT_KCACHE, NULL);
+    if (timed) {
+      s->kernel_ms[r - s->warmup] = (float)(1e3 * (now() - k0));   /* launch to the check's return, on the host clock */
+      s->t_end += now() - k0;
+    }
+  }
+  if (!s->reps) { pthread_barrier_wait(s->barrier); s->t_start = s->t_end = now(); }
+  pthread_barrier_wait(s->barrier);
+  int member[CLOUDSC_NVALID];
+#define VALID_MEMBER(n, N, k, d, i) CLOUDSC_IF_VALIDATED_##d(member[CLOUDSC_F_##N] = CLOUDSC_M_##n;)
+  CLOUDSC_FIELDS(VALID_MEMBER)
+#undef VALID_MEMBER
+  for (int i = 0; i < n && !s->rc && s->ref; i++) {
+    /* a validated member the selection left NULL has no reference array either (as shard_caller) */
+    cloudsc_reference_t ref = *s->ref;
+    cloudsc_stats_t st[CLOUDSC_NVALID];
+    memset(st, 0, sizeof(st));
+    for (int id = 0; id < CLOUDSC_NVALID; id++)
+      if (!((const void *const *)&f[i])[member[id]]) { ref.field[id] = NULL; s->skipped[id] = 1; }
+    if (s->outputs != CLOUDSC_OUTPUTS_ALL)
+      s->rc = cloudsc_fields_validate_tendbuf(s->device, NULL, s->precision, per, s->nproma, klev, 0, s->outputs,
+                                              s->col_offset + (long long)i * per, &f[i], &ref, st);
+    else
+      s->rc = cloudsc_fields_validate(s->device, NULL, s->precision, per, s->nproma, klev,
+                                      s->col_offset + (long long)i * per, &f[i], s->ref, st);
+    for (int id = 0; id < CLOUDSC_NVALID && !s->rc; id++) {
+      if (i == 0) s->stats[id] = st[id];
+      else cloudsc_stats_combine(&s->stats[id], &st[id]);
+    }
+  }
+  if (s->rc) snprintf(s->err, sizeof(s->err), "%s", cloudsc_last_hip_error());
+  if (batch) cloudsc_batch_destroy(batch);
+  for (int i = 0; i < nalloc; i++) cloudsc_fields_free(s->device, &f[i]);
+  free(f);
+}
+
 static void *shard_main(void *arg) {
   shard_t *s = (shard_t *)arg;
+  if (s->batch) { shard_batch(s); return NULL; }
   if (s->caller) { shard_caller(s); return NULL; }
   cloudsc_gpu_state_t *st = NULL;
   s->rc = cloudsc_state_create(&st, s->device, s->precision, s->ngptot, s->nproma, s->col_offset, s->tmpl,
@@ -975,6 +1059,16 @@ int main(int argc, char **argv) {
     o.reps = o.advance;
     o.warmup = 0;
   }
+  /* --batch: N plain caller-owned sets in one KCACHE launch on one device; everything else is a usage error, never
+   * another step in its place */
+  if (o.batch && (o.fields_caller != 1 || o.fields_levels || o.variant != CLOUDSC_VARIANT_KCACHE || o.transfer ||
+                  o.exact_libm || o.spp || o.advance || o.ngpus != 1 || o.energy_s > 0.0 ||
+                  (long long)o.batch * o.ngptot > INT_MAX)) {
+    fprintf(stderr, "dwarf-cloudsc-amd: --batch goes with --fields caller and --variant kcache (one device; no --spp, "
+                    "--advance, --transfer, --fp32-exact-libm or --energy)\n");
+    cloudsc_io_free(&ds);
+    return EXIT_FAILURE;
+  }
   if (o.fields_caller >= 2 && !o.tend_planes) o.tend_planes = CLOUDSC_TENDBUF_PLANES_MIN;
   if (o.fields_caller && (o.transfer || o.variant == VARIANT_CPU)) {
     fprintf(stderr, "dwarf-cloudsc-amd: --fields caller runs the GPU variants on device fields (no --transfer, no "
@@ -1027,10 +1121,13 @@ int main(int argc, char **argv) {
   cloudsc_reference_t ref;
   cloudsc_io_template(&ds, &tmpl);
   cloudsc_io_reference(&ds, &ref);
-  const int nblocks = o.ngptot / o.nproma + (o.ngptot % o.nproma ? 1 : 0);
+  /* --batch N: from here on NGPTOT is the columns of the N sets together, NGPBLKS their blocks */
+  const int set_cols = o.ngptot;
+  if (o.batch) o.ngptot *= o.batch;
+  const int nblocks = (o.batch ? o.batch : 1) * (set_cols / o.nproma + (set_cols % o.nproma ? 1 : 0));
   /* NPROMA blocks per wave of the launches (1 = unpacked; narrow blocks: --narrow-pack) */
   cloudsc_launch_geometry_t geo;
-  if (cloudsc_gpu_launch_geometry(o.precision, o.variant, o.ngptot, o.nproma, ds.klev,
+  if (cloudsc_gpu_launch_geometry(o.precision, o.variant, set_cols, o.nproma, ds.klev,
                                   ds.params.laericesed || ds.params.laericeauto, &geo) != CLOUDSC_OK)
     geo.pack = 1;
   printf(" CLOUDSC-AMD: %s, variant %s, %d device(s); state: %s (KLON=%d, KLEV=%d); pack=%d\n",
@@ -1069,6 +1166,7 @@ int main(int argc, char **argv) {
     s->outputs = o.outputs;
     s->spp = o.spp;
     s->advance = o.advance;
+    s->batch = o.batch;
     s->aerosols = ds.params.laericesed || ds.params.laericeauto;
     s->tmpl = &tmpl; s->params = &ds.params; s->ref = ds.has_reference ? &ref : NULL; s->barrier = &bar;
     s->kernel_ms = (float *)calloc((size_t)o.reps, sizeof(float));
@@ -1198,6 +1296,9 @@ int main(int argc, char **argv) {
   } else {
     printf(" VALIDATION: skipped (no reference outputs loaded)\n");
   }
+  if (o.batch)
+    printf(" BATCH: sets=%d columns_per_set=%d ms_per_launch=%.4f (one cloudsc_gpu_run_batch per step)\n", o.batch,
+           set_cols, kmax);
   if (o.advance)
     printf(" ADVANCE: steps=%d ms_per_step=%.4f in place (cloudsc_gpu_run_advance: pt, pq, pa, pclv rewritten)%s\n",
            o.advance, kmax, o.advance > 1 ? "; nothing validated after more than one step" : "");

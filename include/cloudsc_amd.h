@@ -883,6 +883,63 @@ long long cloudsc_gpu_scratch_bytes(int precision, int variant, int ngptot, int 
  * launches (the state and pipeline APIs do).  Other variants: only the sync. */
 int cloudsc_gpu_check(int device, void *stream, int variant, void *scratch);
 
+/* ---- batched step: many caller-owned field sets in one launch ----
+ * An ensemble host has several members of 8-32 k columns each, every member in
+ * its own device allocations and usually under its own parameter set.  One
+ * KCACHE launch per member leaves most of the card idle (a step fills it at
+ * about 131 k columns) and the launches of one stream serialise.  A batch runs
+ * `nsets` field sets of one shape in ONE launch, each set under its own
+ * parameter set.
+ *
+ * cloudsc_batch_create builds the kernel arguments of every set exactly as
+ * cloudsc_gpu_run_outputs(KCACHE) would and uploads them, once and
+ * synchronously, as one device table; the caller may free `sets` and `params`
+ * (host arrays of nsets elements) when it returns.  params == NULL: every set
+ * runs under the device's set (cloudsc_gpu_init is required, CLOUDSC_ENOINIT)
+ * as it is at the time of each run; otherwise set i runs under params[i],
+ * converted as cloudsc_gpu_init converts them, and no cloudsc_gpu_init is needed.
+ * cloudsc_gpu_run_batch is one launch, asynchronous in `stream`, with no upload
+ * and no allocation; cloudsc_gpu_check(device, stream, KCACHE, NULL) waits for it.
+ *
+ * Contract: every selected output of set i has, bit for bit, what
+ * cloudsc_gpu_run_outputs(KCACHE, same precision and outputs) gives for that
+ * set alone after cloudsc_gpu_init(device, &params[i]) -- fp64, fp32 (default
+ * exp/pow) and mixed; CLOUDSC_OUTPUTS_ALL, PROGNOSTIC and SURFACE; packed and
+ * unpacked narrow blocks (cloudsc_debug_set_narrow_pack, read at each run);
+ * with aerosols (LAERICESED || LAERICEAUTO, then of every set's parameters, and
+ * picrit_aer, pre_ice, pnice required in every set) or without.  plude is
+ * updated in place, so two runs of one batch differ as two cloudsc_gpu_run do.
+ *
+ * Aliasing (pointer equality only): sets may share any input member -- "one
+ * state, N parameter sets".  The members the step writes (the selected outputs
+ * and plude) are exclusive: none may equal any other non-NULL member of its
+ * own set or any non-NULL member of another set.
+ *
+ * CLOUDSC_VARIANT_KCACHE only: KSEG's workspace and hand-off records are per
+ * set.  The tendency-buffer, cumulative, per-column multiplier and advancing
+ * forms, cloudsc_state_*, the host pipelines and the drop-in have no batch.
+ *
+ * CLOUDSC_EINVAL, all before the first HIP call: batch or sets NULL; nsets < 1
+ * or > CLOUDSC_BATCH_MAX_SETS; ngptot or nproma < 1, nproma > 256 (KCACHE; so
+ * also > 2^24), klev < 2; an unknown precision or `outputs`; a required member
+ * NULL in any set; one of picrit_aer, pre_ice, pnice set in some sets and not in
+ * others; with params: an invalid set, sets that disagree on LAERICESED ||
+ * LAERICEAUTO, aerosol parameters without the three aerosol members; the
+ * aliasing rule.  cloudsc_gpu_run_batch: batch NULL, or a variant other than
+ * CLOUDSC_VARIANT_KCACHE (KSEG, SCC, SCC_PRIVATE, unknown, or with
+ * CLOUDSC_FP32_EXACT_LIBM) -- checked before the batch is looked at.
+ * CLOUDSC_ENODEV, CLOUDSC_ENOINIT, CLOUDSC_ENOMEM, CLOUDSC_EHIP as elsewhere. */
+/* the member index is the launch's second grid dimension, which holds at most 65535 */
+#define CLOUDSC_BATCH_MAX_SETS 65535
+typedef struct cloudsc_batch cloudsc_batch_t;
+int cloudsc_batch_create(cloudsc_batch_t **batch, int device, int precision, int outputs,
+                         int nsets, int ngptot, int nproma, int klev,
+                         const cloudsc_fields_t *sets,      /* host array[nsets] of device pointers */
+                         const cloudsc_params_t *params);   /* NULL: the device's set; else array[nsets] */
+int cloudsc_gpu_run_batch(cloudsc_batch_t *batch, void *stream, int variant);
+int cloudsc_batch_nsets(const cloudsc_batch_t *batch);      /* CLOUDSC_EINVAL for NULL */
+int cloudsc_batch_destroy(cloudsc_batch_t *batch);          /* waits for the device; NULL is CLOUDSC_OK */
+
 /* Diagnostic: the number of polls a KSEG consumer makes before it gives up
  * (default 2^24, restored by a negative value).  0 makes every hand-off fail
  * without polling -- used by the tests of the error path. */
@@ -913,6 +970,11 @@ typedef struct cloudsc_launch_geometry {
  * cloudsc_debug_set_kseg_schedule, never more than segments x units. */
 int cloudsc_gpu_launch_geometry(int precision, int variant, int ngptot, int nproma, int klev,
                                 int laer, cloudsc_launch_geometry_t *out);
+/* The same for the launch of a batch (cloudsc_gpu_run_batch, KCACHE): the geometry of one
+ * set, with `units` and `workgroups` times nsets -- the grid is (workgroups of a set) x nsets.
+ * CLOUDSC_EINVAL: nsets out of range, and what cloudsc_gpu_launch_geometry returns it for. */
+int cloudsc_batch_launch_geometry(int precision, int nsets, int ngptot, int nproma, int klev, int laer,
+                                  cloudsc_launch_geometry_t *out);
 
 /* Process-wide: 1 pack blocks of nproma <= 32, 0 never, negative = the default
  * (per width, as measured: DESIGN.md §3.18).  Packing needs every lane offset
